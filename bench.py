@@ -7,9 +7,16 @@ all-reduce". One process per GPU (``python -m torch.distributed.run --nproc-per-
 batch). Each rank is one Krum worker; the default topology is the sharded ("robust ZeRO")
 exchange: bucketed all-to-all of bf16 gradients overlapped with backward -> per-shard MFMA Gram
 -> all-reduce of the n x n Gram -> Krum weights -> fused weighted-sum + SGD-momentum update of
-the fp32 master shard -> all-gather of bf16 parameters. After the timed Krum run, the same
-model/batch runs with the plain mean all-reduce baseline (DDP-equivalent, same fused optimizer)
-and ``agg_overhead_vs_allreduce`` = (t_krum - t_allreduce) / t_allreduce is reported.
+the fp32 master shard -> all-gather of bf16 parameters.
+
+A plain run (``bench.py --gpus N --steps K --warmup W``) sets up, warms up, times the K steps of
+that Krum run and prints the result line; ``--dump-outputs DIR`` also writes what the last timed
+step returned (see ``dump_outputs``). Everything below that is called a *block* or a *baseline*
+runs only with ``--full``; without it the keys of those blocks are absent (or null).
+
+``--full``: after the timed Krum run, the same model/batch runs with the plain mean all-reduce
+baseline (DDP-equivalent, same fused optimizer) and ``agg_overhead_vs_allreduce`` =
+(t_krum - t_allreduce) / t_allreduce is reported.
 
 Data: synthetic ImageNet-shaped batches (random bf16 images, random labels) generated on
 device; random-init weights. Every timed step runs the full forward, backward, exchange,
@@ -100,7 +107,18 @@ def parse():
                     help="launch a spin_kernel between warmup and timed steps (prof_summary --after)")
     ap.add_argument("--no-miopen-find", action="store_true",
                     help="disable MIOpen find mode (torch.backends.cudnn.benchmark) for convs")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline run also time the mean all-reduce baseline, the "
+                         "virtual-worker Krum block (N = 1) and the batch-256 block, and report "
+                         "their keys in the result line (a plain run times the headline only)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last timed step of the headline "
+                         "run returned (loss, updated parameters, aggregation weights, BatchNorm "
+                         "buffers) as DIR/<name>.npy")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def default_f(n: int) -> int:
@@ -137,8 +155,43 @@ class _HostEvent:
         return (other.t - self.t) * 1e3
 
 
+DUMP_MAX_BYTES = 64 * 10**6      # --dump-outputs: all files together stay under this
+DUMP_PARAM_SAMPLE = 4 * 2**20    # parameters kept (16 MiB) when all of them are over half of it
+DUMP_SEED = 20240607
+
+
+def dump_outputs(path: str, loss: torch.Tensor, model, eng) -> None:
+    """Write what the last timed step handed back as ``path/<name>.npy``:
+
+    * ``loss``         float64 [1], the step's mean loss over the workers;
+    * ``params``       float32, the updated parameters in ``model.parameters()`` order (each in
+                       its logical element order, so the file does not depend on the bucket
+                       layout). When all of them would exceed the size budget, the elements at
+                       ``DUMP_PARAM_SAMPLE`` positions drawn once from a CPU generator seeded
+                       with ``DUMP_SEED`` (sorted, the same for every run of one model);
+    * ``agg_weights``  float32 [n], the rule's weight per worker row;
+    * ``buffers``      float32, the floating-point module buffers (BatchNorm running statistics)
+                       in ``model.buffers()`` order.
+    """
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    with torch.no_grad():
+        flat = torch.cat([p.detach().reshape(-1).float() for p in model.parameters()])
+        bufs = [b.detach().reshape(-1).float() for b in model.buffers() if b.is_floating_point()]
+        bufs = torch.cat(bufs) if bufs else torch.zeros(0, device=flat.device)
+        w = eng.w[: eng.n].detach().float()
+        if 4 * (flat.numel() + bufs.numel() + w.numel()) > DUMP_MAX_BYTES // 2:
+            g = torch.Generator().manual_seed(DUMP_SEED)
+            idx = torch.randint(0, flat.numel(), (DUMP_PARAM_SAMPLE,), generator=g).sort().values
+            flat = flat[idx.to(flat.device)]
+        out = {"loss": loss.detach().double().reshape(1), "params": flat, "agg_weights": w,
+               "buffers": bufs}
+        for name, t in out.items():
+            np.save(os.path.join(path, name + ".npy"), t.cpu().numpy())
+
+
 def run(args, rule: str, topology: str, steps: int, warmup: int, info, *, V: int = 1,
-        batch: int = 0, f: int = -1):
+        batch: int = 0, f: int = -1, dump: str = ""):
     from consensusml_amd.parallel.dist import barrier
     from consensusml_amd import TrainConfig
     from consensusml_amd.trainer.trainer import ConsensusTrainer
@@ -236,6 +289,8 @@ def run(args, rule: str, topology: str, steps: int, warmup: int, info, *, V: int
         res["replicas_identical"] = bool(torch.equal(hi, lo))
         res["world_size_seen"] = dist.get_world_size()
         res["dist_backend"] = dist.get_backend()
+    if dump and info.rank == 0:
+        dump_outputs(dump, loss, model, eng)
     tr.close()
     del tr, eng, model, batches
     torch.cuda.empty_cache()
@@ -286,17 +341,20 @@ def main():
     # warmup steps, plus one tuning step when --warmup 0) and cached for the run.
     torch.backends.cudnn.benchmark = not args.no_miopen_find
     n = info.world
-    main_res = run(args, args.rule, args.topology, args.steps, args.warmup, info)
+    main_res = run(args, args.rule, args.topology, args.steps, args.warmup, info,
+                   dump=args.dump_outputs or "")
     ms = main_res["dt"] / args.steps * 1e3
     value = n * args.batch * args.steps / main_res["dt"]
     overhead = None
     base = None
-    if not args.no_baseline:
+    if args.full and not args.no_baseline:
         bsteps = args.baseline_steps if args.baseline_steps > 0 else args.steps
         base = run(args, "mean", "allreduce", bsteps, args.warmup, info)
         base["ms"] = base["dt"] / bsteps * 1e3
         overhead = (ms - base["ms"]) / base["ms"]
     V = args.virtual_workers if args.virtual_workers >= 0 else (8 if n == 1 else 0)
+    if not args.full:
+        V = 0
     virt = {}
     if V > 1:
         vsteps = args.virtual_steps if args.virtual_steps > 0 else args.steps
@@ -323,7 +381,7 @@ def main():
             f"{tag}_loss_finite": kr["finite"] and mn["finite"],
         }
     small = {}
-    if args.b256_batch > 0 and args.b256_batch != args.batch:
+    if args.full and args.b256_batch > 0 and args.b256_batch != args.batch:
         sb = args.b256_batch
         ks = run(args, args.rule, args.topology, args.b256_steps, args.warmup, info, batch=sb)
         ar = run(args, "mean", "allreduce", args.b256_steps, args.warmup, info, batch=sb)
@@ -357,6 +415,7 @@ def main():
             "warmup": args.warmup,
             "ms_per_step": round(ms, 3),
             "higher_is_better": True,
+            "full": args.full,
             "scaling": "weak",
             "vs_baseline": None,
             "dtype": "bf16",

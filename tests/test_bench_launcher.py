@@ -10,7 +10,7 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TINY = ["--dist-backend", "gloo", "--model", "mlp", "--batch", "8", "--steps", "2",
-        "--warmup", "1", "--no-miopen-find", "--b256-batch", "0"]
+        "--warmup", "1", "--no-miopen-find", "--full", "--b256-batch", "0"]
 
 
 def _bench(args, env=None, timeout=300):
@@ -38,6 +38,27 @@ def test_self_launch_world_size(n):
     assert r["config"]["parallelism"] == f"dp{n}" and r["config"]["global_batch"] == 8 * n
     if n >= 4:   # Krum with a real Byzantine budget
         assert r["config"]["f"] == 1 and r["selection"]["selected_last_step"] >= 1
+
+
+def test_plain_run_dumps_repeatable_outputs(tmp_path):
+    """A plain run (no --full) times the headline only, and --dump-outputs writes the same
+    float arrays on every run with the same arguments (same inputs, same initial weights)."""
+    import numpy as np
+    plain = [a for a in TINY if a != "--full"]
+    dumps = []
+    for d in ("a", "b"):
+        out = _bench(["--gpus", "1", *plain, "--steps", "3", "--dump-outputs", str(tmp_path / d)])
+        assert out.returncode == 0, out.stderr[-3000:]
+        r = _line(out.stdout)
+        assert r["steps"] == 3 and r["ms_per_step"] > 0 and r["full"] is False
+        assert sum(r["selection"]["selection_counts"]) == 3 + 1     # engine steps: timed + warmup
+        assert r["allreduce_ms_per_step"] is None and "mean/allreduce" not in out.stderr
+        dumps.append({p.stem: np.load(p) for p in (tmp_path / d).iterdir()})
+    assert set(dumps[0]) == {"loss", "params", "agg_weights", "buffers"}
+    for k, a in dumps[0].items():
+        assert a.dtype in (np.float32, np.float64) and np.isfinite(a).all()
+        np.testing.assert_array_equal(a, dumps[1][k])
+    assert dumps[0]["params"].size == r["config"]["params"] and dumps[0]["loss"].shape == (1,)
 
 
 def test_world_size_mismatch_fails():

@@ -67,15 +67,12 @@ def test_select_cli_counts_with_reference_cohort(tmp_path):
     import os
     import numpy as np
     import pandas as pd
-    ref = "/root/reference"
-    clin = os.path.join(ref, "Clinical_Data", "AML_dataframe.csv")
-    if not os.path.exists(clin):
-        import pytest
-        pytest.skip("reference files not present")
+    ref = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference")
+    clin = os.path.join(ref, "AML_dataframe.csv.gz")
     from consensusml_amd.select.__main__ import main
     from consensusml_amd.select.data import target_aml_cohort
-    tr = os.path.join(ref, "JSmith_code", "TARGET_AML_Training_Samples.csv")
-    te = os.path.join(ref, "JSmith_code", "TARGET_AML_Testing_Samples.csv")
+    tr = os.path.join(ref, "TARGET_AML_Training_Samples.csv")
+    te = os.path.join(ref, "TARGET_AML_Testing_Samples.csv")
     co = target_aml_cohort(clin, tr, te)
     usis = list(co.index)
     g = np.random.default_rng(0)

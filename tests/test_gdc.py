@@ -1,5 +1,6 @@
 """C01 GDC acquisition without network: fake opener for paging / downloads, and the reference's own
-manifest rebuilt from its ID-map CSV (`Manifest_Data/*.csv`, plain CSV)."""
+manifest rebuilt from its ID-map CSV (`Manifest_Data/*.csv`, plain CSV; copies of both tables
+are under tests/golden/reference)."""
 import hashlib
 import json
 import os
@@ -9,7 +10,7 @@ import pytest
 
 from consensusml_amd.select import gdc
 
-REF = "/root/reference/Manifest_Data"
+REF = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference")
 ENT = ["entity_id", "case_id", "entity_submitter_id", "entity_type"]
 
 
@@ -34,10 +35,9 @@ def _pager(hits, page):
     return opener, calls
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference manifests not present")
 def test_manifest_matches_reference():
-    idm = pd.read_csv(os.path.join(REF, "GCD_TARGET_Data_Manifest_AML_NBL_WT_RT.csv"))
-    ref = pd.read_csv(os.path.join(REF, "TARGET_Manifest_RNAseq_Counts.csv"))
+    idm = pd.read_csv(os.path.join(REF, "GCD_TARGET_Data_Manifest_AML_NBL_WT_RT.csv.gz"))
+    ref = pd.read_csv(os.path.join(REF, "TARGET_Manifest_RNAseq_Counts.csv.gz"))
     hits = _hits_from_idmap(idm)
     # one suspect file mapped to two samples must be dropped
     bad = dict(hits[0], file_id="dup", associated_entities=hits[0]["associated_entities"] * 2)

@@ -1,5 +1,7 @@
-"""Parity with numbers the reference itself records, computed from the reference's own files
-(read-only, /root/reference): the TARGET-AML cohort tables and chi-square balance tests of
+"""Parity with numbers the reference itself records, computed from copies of the reference's own
+data files (tests/golden/reference: its clinical table `Clinical_Data/AML_dataframe.csv`, its
+training / testing sample lists, and the header plus first five rows of its
+`standouttable.csv`): the TARGET-AML cohort tables and chi-square balance tests of
 `composite_code/rnotebook/cml_targetaml_seanalysis.Rmd:422-474` (golden values pasted there as
 comments: risk-group counts, 137 samples after filtering, gender / age tables, p = 0.8044 and
 p = 0.6591), and the column schema of the reference's standard output table."""
@@ -7,15 +9,12 @@ import os
 
 import numpy as np
 import pandas as pd
-import pytest
 
-REF = "/root/reference"
-CLIN = os.path.join(REF, "Clinical_Data", "AML_dataframe.csv")
-TRAIN = os.path.join(REF, "JSmith_code", "TARGET_AML_Training_Samples.csv")
-TEST = os.path.join(REF, "JSmith_code", "TARGET_AML_Testing_Samples.csv")
-STAND = os.path.join(REF, "composite_code", "rnotebook", "data", "standouttable.csv")
-
-pytestmark = pytest.mark.skipif(not os.path.exists(CLIN), reason="reference files not present")
+REF = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference")
+CLIN = os.path.join(REF, "AML_dataframe.csv.gz")
+TRAIN = os.path.join(REF, "TARGET_AML_Training_Samples.csv")
+TEST = os.path.join(REF, "TARGET_AML_Testing_Samples.csv")
+STAND = os.path.join(REF, "standouttable_head.csv")
 
 
 def test_target_aml_cohort_tables_and_chisq():

@@ -37,6 +37,7 @@ STAND = os.path.join(REF, "standouttable.csv")
 # also run on GPU boxes without /root/reference
 FIXTURE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "fixtures",
                        "reference_subset.npz")
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference")
 HAVE_RDA = os.path.exists(SE)
 
 pytestmark = pytest.mark.skipif(not (HAVE_RDA or os.path.exists(FIXTURE)),
@@ -65,6 +66,33 @@ def ref():
             "source": "fixture"}
 
 
+def _golden_tables():
+    """The container's gene table (stored CSV) and its label / split columns (from the fixture's
+    y / train / test arrays; the sample names are not stored, so rows are named by position)."""
+    rd = pd.read_csv(os.path.join(GOLDEN, "deg_container_row_data.csv.gz"), index_col=0,
+                     dtype={"seqnames": str}, float_precision="round_trip")
+    z = np.load(FIXTURE)
+    split = np.full(len(z["y"]), "", dtype=object)
+    split[z["train"]], split[z["test"]] = "train", "test"
+    cd = pd.DataFrame({"deg.risk": z["y"], "exptset.seahack": split},
+                      index=[f"sample{i:03d}" for i in range(len(z["y"]))])
+    return rd, cd
+
+
+def _container():
+    """The reference's DEG container: read from its .rda where that is present, else rebuilt from
+    the committed data (the fixture's matrix, labels and split + the container's gene table,
+    tests/golden/reference/deg_container_row_data.csv.gz, written by tools/make_ref_fixture.py)."""
+    from consensusml_amd.select.data import ExpressionSet
+    if HAVE_RDA:
+        return ExpressionSet.from_rdata(SE)
+    z = np.load(FIXTURE)
+    rd, cd = _golden_tables()
+    assert list(rd.index) == [str(g) for g in z["genes"]]
+    return ExpressionSet({"logcpm": torch.from_numpy(z["X"]).t().contiguous()}, list(rd.index),
+                         list(cd.index), rd, cd)
+
+
 def test_fixture_matches_rda():
     """The committed fixture is exactly what the data-only reader extracts from the reference."""
     if not (HAVE_RDA and os.path.exists(FIXTURE)):
@@ -75,6 +103,17 @@ def test_fixture_matches_rda():
     np.testing.assert_array_equal(z["X"], es.assays["logcpm"].t().contiguous().numpy()
                                   .astype(np.float32))
     assert [str(g) for g in z["genes"]] == list(es.genes)
+    # ... and so are the container's tables stored as CSV
+    rd, cd = _golden_tables()
+    assert list(rd.index) == list(es.genes) and len(cd) == len(es.samples)
+    assert list(rd.columns) == list(es.row_data.columns)
+    for c in ("logFC", "AveExpr", "t", "p.unadj", "p.adj.bh", "b"):
+        np.testing.assert_array_equal(rd[c].to_numpy(), es.row_data[c].to_numpy())
+    for c in ("hgnc_id", "hgnc_symbol", "ensembl_gene_id"):
+        assert list(rd[c].fillna("")) == list(es.row_data[c].fillna(""))
+    assert list(cd["exptset.seahack"]) == list(es.col_data["exptset.seahack"])
+    np.testing.assert_array_equal(cd["deg.risk"].to_numpy(),
+                                  pd.to_numeric(es.col_data["deg.risk"]).to_numpy())
 
 
 @needs_rda
@@ -184,15 +223,13 @@ def test_rf_importance_parity(ref):
     assert len(top(ours) & top(imp2k)) >= 36
 
 
-@needs_rda
 def test_pipeline_on_reference_container_with_resume(tmp_path, monkeypatch):
     """The reference analysis run from its own DEG container, interrupted after the SVM stage
     and resumed: the finished stage is not recomputed (its result list and table columns are
     reloaded), and the outputs keep the reference's standard-table layout."""
     from consensusml_amd.select import pipeline as P
     from consensusml_amd.select import results as RS
-    from consensusml_amd.select.data import ExpressionSet
-    es = ExpressionSet.from_rdata(SE)
+    es = _container()
     kw = dict(label_col="deg.risk", split_col="exptset.seahack", deg_from_container=True,
               out_dir=str(tmp_path), lasso_reps=3, rf_trees=(100,), max_genes=400,
               xgb_configs=P.REF_XGB[:2])

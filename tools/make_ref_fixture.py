@@ -3,7 +3,8 @@
 data-only R reader; nothing in the files is executed): the analysis container's log-CPM matrix
 (1984 DEGs x 137 samples), labels, train/test split, gene ids, the standard-table columns the
 parity tests compare against (rfnb_*, xg*_imp, svm1_weights, DE statistics) and lasso rep 1's
-lambda.min / test error / nonzero coefficients. GPU boxes have no /root/reference; with this
+lambda.min / test error / nonzero coefficients; and, under tests/golden/reference, the container's
+gene table as CSV. Where the reference tree is absent, with this
 fixture tests/test_reference_rdata_parity.py runs there too.
 
   python tools/make_ref_fixture.py [--ref /root/reference/composite_code/rnotebook/data]
@@ -27,6 +28,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--ref", default="/root/reference/composite_code/rnotebook/data")
     ap.add_argument("--out", default=os.path.join(ROOT, "tests", "fixtures", "reference_subset.npz"))
+    ap.add_argument("--golden", default=os.path.join(ROOT, "tests", "golden", "reference"))
     a = ap.parse_args()
     from consensusml_amd.select import rdata as R
     from consensusml_amd.select.data import ExpressionSet
@@ -49,6 +51,11 @@ def main():
         lasso_genes=np.array(list(R.names(nz)), dtype="U32"),
         lasso_coef=np.asarray(nz.values, dtype=np.float64))
     print("wrote", a.out, os.path.getsize(a.out), "bytes")
+    # the container's gene table (annotation + DE statistics): with the matrix, labels and split
+    # above it rebuilds the container without the .rda
+    os.makedirs(a.golden, exist_ok=True)
+    es.row_data.to_csv(os.path.join(a.golden, "deg_container_row_data.csv.gz"))
+    print("wrote", a.golden)
 
 
 if __name__ == "__main__":
