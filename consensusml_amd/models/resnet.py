@@ -477,9 +477,12 @@ class ResNet(nn.Module):
         # (PerfPolicy.batch_wlayouts) instead of one per conv
         blocks = [b for layer in (self.layer1, self.layer2, self.layer3, self.layer4)
                   for b in layer]
+        # (not while an engine's parameter exchange for any of them is still in flight: each
+        # layer's weights are only waited for when that layer's forward begins, so for this
+        # forward every conv makes its own layouts, after that wait)
+        ws = [b.conv2.weight for b in blocks] + [b.conv1.weight for b in blocks]
         batched = (pol.batch_wlayouts and self.training and torch.is_grad_enabled()
-                   and fconv.prefetch_wlayouts([b.conv2.weight for b in blocks]
-                                               + [b.conv1.weight for b in blocks]))
+                   and not fconv.params_pending(self, ws) and fconv.prefetch_wlayouts(ws))
         try:
             x = self.layer4(self.layer3(self.layer2(self.layer1(x))))
         finally:

@@ -23,6 +23,7 @@ Gradients: data gradient as a hipBLASLt GEMM (stride 1, per-shape policy of
 """
 from __future__ import annotations
 
+import weakref
 from typing import Optional, Tuple, Dict
 
 import torch
@@ -806,6 +807,30 @@ def prefetch_wlayouts(ws) -> bool:
 
 def clear_wlayouts() -> None:
     _WL_BATCH.clear()
+
+
+# model -> its engine's "are these parameters still being exchanged" query. An engine that lets a
+# parameter exchange run into the next forward (parallel.engine: per-unit waits in forward
+# pre-hooks) registers it; a model asks before it reads weights of units whose forward has not
+# begun (the batched layout launch above). No entry -- no engine, or one that never leaves an
+# exchange in flight -- means nothing is ever pending.
+_PENDING_QUERY = weakref.WeakKeyDictionary()
+
+
+def set_pending_query(model: torch.nn.Module, query) -> None:
+    """Register ``query(params) -> bool`` (a bound method, held weakly) for ``model``; None
+    removes it."""
+    if query is None:
+        _PENDING_QUERY.pop(model, None)
+    else:
+        _PENDING_QUERY[model] = weakref.WeakMethod(query)
+
+
+def params_pending(model: torch.nn.Module, params) -> bool:
+    """True if an exchange that will overwrite any of ``params`` of ``model`` is in flight."""
+    ref = _PENDING_QUERY.get(model)
+    query = ref() if ref is not None else None
+    return query is not None and query(params)
 
 
 def cached_wt(w: torch.Tensor) -> Optional[torch.Tensor]:

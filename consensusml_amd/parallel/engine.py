@@ -41,6 +41,7 @@ import torch.distributed as dist
 from ..config import TrainConfig
 from ..ops import kernels as K
 from ..ops import worker_grads as WG
+from ..ops.conv import set_pending_query
 from ..perf import policy as _P
 from ..ops.native import lib
 from .dist import DistInfo
@@ -346,6 +347,19 @@ class ConsensusEngine:
         self._prefetch_hooks.append(root.register_forward_pre_hook(self._root_pre))
         self._invoked: set = set()
         self._learned = False
+        # a model that reads parameters of several units ahead of their forwards (ResNet's
+        # batched weight-layout launch) asks this first (ops.conv.params_pending)
+        self._pid = pid
+        set_pending_query(root, self.params_pending)
+
+    def params_pending(self, params) -> bool:
+        """True while the exchange of a bucket holding any of ``params`` is still in flight: the
+        values must not be read before the owning unit's forward pre-hook has waited."""
+        if not self._ag_works:
+            return False
+        bucket_of = self.flat.bucket_of
+        return any(bucket_of[self._pid[id(p)]] in self._ag_works
+                   for p in params if id(p) in self._pid)
 
     def _wait_ag(self, bi: int) -> None:
         w = self._ag_works.pop(bi, None)
@@ -1130,6 +1144,8 @@ class ConsensusEngine:
         for h in self._prefetch_hooks:
             h.remove()
         self._prefetch_hooks = []
+        if self.param_prefetch:
+            set_pending_query(self.flat.model, None)
         for h in self._hooks:
             h.remove()
         self._hooks = []
