@@ -8,11 +8,12 @@ from consensusml_amd.ops import kernels as K
 
 pytestmark = pytest.mark.gpu
 
+COMBOS = [("weighted", "sgd"), ("weighted", "adamw"), ("sorted", "sgd"), ("sorted", "adamw")]
 
-@pytest.mark.parametrize("combine,opt_kind", [("weighted", "sgd"), ("weighted", "adamw"),
-                                              ("sorted", "sgd"), ("sorted", "adamw")])
-@pytest.mark.parametrize("ragged", [False, True])
-def test_multi_equals_per_bucket(cuda, combine, opt_kind, ragged):
+
+def _multi_vs_per_bucket(cuda, combine, opt_kind, ragged, pick=None):
+    """``pick``: Bulyan's selection -- the n rows are taken through ``rows`` from a larger X
+    whose other rows are NaN."""
     torch.manual_seed(0)
     n = 8
     lens = [4096, 12288, 808 if ragged else 800, 20000]
@@ -21,6 +22,16 @@ def test_multi_equals_per_bucket(cuda, combine, opt_kind, ragged):
         offs.append(offs[-1] + L)
     total = sum(lens)
     Xs = [torch.randn(n, L, device=cuda).bfloat16() for L in lens]
+    rows = None
+    if pick is not None:
+        rows = torch.tensor(pick, dtype=torch.int32, device=cuda)
+        full = []
+        for X in Xs:
+            F = torch.full((max(pick) + 2, X.shape[1]), float("nan"), device=cuda,
+                           dtype=torch.bfloat16)
+            F[rows.long()] = X
+            full.append(F)
+        Xs = full
     w = torch.rand(n, device=cuda)
     w[3] = 0.0
     opt = K.OptArgs(kind=opt_kind, lr=0.05, momentum=0.9 if opt_kind == "sgd" else 0.0,
@@ -29,6 +40,8 @@ def test_multi_equals_per_bucket(cuda, combine, opt_kind, ragged):
         dict(combine=combine, n=n, lo=2, cnt=4)
     if combine == "weighted":
         kw["w"] = w
+    if rows is not None:
+        kw["rows"] = rows
 
     def state():
         g = torch.Generator(device=cuda).manual_seed(1)
@@ -49,3 +62,20 @@ def test_multi_equals_per_bucket(cuda, combine, opt_kind, ragged):
         assert torch.equal(b1, b2)
     for x, y in zip(p1, p2):
         assert torch.equal(x, y)
+    return m2
+
+
+@pytest.mark.parametrize("combine,opt_kind", COMBOS)
+@pytest.mark.parametrize("ragged", [False, True])
+def test_multi_equals_per_bucket(cuda, combine, opt_kind, ragged):
+    _multi_vs_per_bucket(cuda, combine, opt_kind, ragged)
+
+
+@pytest.mark.parametrize("combine,opt_kind", COMBOS)
+@pytest.mark.parametrize("ragged", [False, True])
+def test_multi_equals_per_bucket_rows(cuda, combine, opt_kind, ragged):
+    """The same through ``rows`` (a non-monotonic pick of 8 rows of a larger X): equal to the per-bucket
+    launches, and to the run without ``rows`` on the same 8 rows in the same order."""
+    m = _multi_vs_per_bucket(cuda, combine, opt_kind, ragged, pick=(9, 2, 11, 0, 5, 7, 4, 12))
+    assert torch.isfinite(m).all()
+    assert torch.equal(m, _multi_vs_per_bucket(cuda, combine, opt_kind, ragged))
