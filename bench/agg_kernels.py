@@ -8,6 +8,10 @@ For n workers x D coordinates (bf16), times (HIP events, median of reps):
   trimmed_sgd    trimmed mean (trim f) fused with SGD-momentum
   krum_sgd       weighted combine (one-hot Krum weights: 1 row read) fused with SGD-momentum
   mean_sgd       weighted combine of all n rows fused with SGD-momentum
+  --mixed adds   nnm_matrix (the mixing matrix from G, one wave) and median_mixed_sgd /
+                 trimmed_mixed_sgd: the same fused updates with the nearest-neighbour pre-mix
+                 y = M x per coordinate ahead of the sort (agg.pre=nnm), and their ratio to the
+                 plain sorted kernels from the same process
 and the PyTorch equivalents (torch.median / sort / matmul / foreach) for comparison. Reports
 achieved HBM GB/s from the bytes each kernel must move. One JSON line per (n, D).
 """
@@ -47,6 +51,8 @@ def main():
     ap.add_argument("--D", type=int, nargs="*", default=[25_557_032, 109_514_304])
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--no-torch", action="store_true")
+    ap.add_argument("--mixed", action="store_true",
+                    help="also time the mixed sorted kernel (agg.pre=nnm) next to the plain one")
     ap.add_argument("--json-out", default=None)
     a = ap.parse_args()
     from consensusml_amd.ops import kernels as K
@@ -75,6 +81,19 @@ def main():
             lo2, cnt2 = K.sorted_range("trimmed_mean", n, f if 2 * f < n else 0)
             res["trimmed_sgd_ms"] = timeit(lambda: K.agg_update(
                 X, combine="sorted", lo=lo2, cnt=cnt2, opt=opt, master=master, s1=mom, param_out=p), a.reps)
+            if a.mixed:
+                K.gram(X, out=G)
+                fm = max(0, (n - 1) // 3)
+                M = torch.empty(n, n, device=dev)
+                res["nnm_matrix_ms"] = timeit(lambda: K.robust_weights(
+                    G, "nnm_only", n, f=fm, w_out=w, pre="nnm", mix_out=M), a.reps)
+                res["nnm_f"] = fm
+                res["median_mixed_sgd_ms"] = timeit(lambda: K.agg_update(
+                    X, combine="sorted", lo=lo, cnt=cnt, opt=opt, master=master, s1=mom,
+                    param_out=p, mix=M), a.reps)
+                res["trimmed_mixed_sgd_ms"] = timeit(lambda: K.agg_update(
+                    X, combine="sorted", lo=lo2, cnt=cnt2, opt=opt, master=master, s1=mom,
+                    param_out=p, mix=M), a.reps)
             K.robust_weights(G, "krum", n, f=f, w_out=w)
             res["krum_sgd_ms"] = timeit(lambda: K.agg_update(
                 X, combine="weighted", w=w, opt=opt, master=master, s1=mom, param_out=p), a.reps)
@@ -90,6 +109,14 @@ def main():
             res["trimmed_sgd_GBps"] = gbs(n * D * 2 + state, res["trimmed_sgd_ms"])
             res["krum_sgd_GBps"] = gbs(D * 2 + state, res["krum_sgd_ms"])
             res["mean_sgd_GBps"] = gbs(n * D * 2 + state, res["mean_sgd_ms"])
+            if a.mixed:
+                for k in ("median", "trimmed"):
+                    res[f"{k}_mixed_sgd_GBps"] = gbs(n * D * 2 + state, res[f"{k}_mixed_sgd_ms"])
+                    res[f"{k}_mixed_over_plain"] = round(
+                        res[f"{k}_mixed_sgd_ms"] / res[f"{k}_sgd_ms"], 3)
+                # the mix: n^2 fp32 FMAs per coordinate
+                res["median_mixed_mix_TFLOPs"] = round(
+                    2.0 * n * n * D / (res["median_mixed_sgd_ms"] * 1e-3) / 1e12, 2)
             g2 = res["gram_ms"] + res["gram_centered_ms"]   # both Gram passes (engine default)
             res["krum_total_ms"] = round(g2 + res["weights_krum_ms"] + res["krum_sgd_ms"], 4)
             res["geomed_total_ms"] = round(g2 + res["weights_geomed_ms"] + res["mean_sgd_ms"], 4)

@@ -23,6 +23,10 @@ diverged (non-finite), and for Krum / Multi-Krum how often a Byzantine worker wa
 
   python bench/robustness.py --task mlp --steps 200 --jsonl out.jsonl --md out.md
   python bench/robustness.py --task resnet_tiny --rules krum,median --attacks alie
+  python bench/robustness.py --task mlp --pre nnm      # nearest-neighbour mixing before each rule
+
+``--pre nnm`` (agg.pre) skips mean and bulyan, which have no mixed form, and leaves out the
+Byzantine selection fraction: the selections then index mixed rows, not workers.
 """
 from __future__ import annotations
 
@@ -67,7 +71,7 @@ def rule_f(rule: str, n: int, f: int) -> int:
 
 def make_config(task: str, rule: str, attack: str, n: int = 8, f: int = 2,
                 steps: Optional[int] = None, dtype: str = "bf16", tau: float = 1.0,
-                seed: int = 2019):
+                seed: int = 2019, pre: str = "none"):
     from consensusml_amd import TrainConfig
     t = TASKS[task]
     cfg = TrainConfig()
@@ -88,6 +92,7 @@ def make_config(task: str, rule: str, attack: str, n: int = 8, f: int = 2,
     cfg.agg.rule = rule
     cfg.agg.f = rule_f(rule, n, f)
     cfg.agg.tau = tau
+    cfg.agg.pre = pre
     cfg.topology.kind = "sharded"
     cfg.optim.name = "sgd"
     cfg.optim.lr = t["lr"]
@@ -116,14 +121,15 @@ def fault_desc(cfg) -> str:
 
 def run_one(task: str, rule: str, attack: str, n: int = 8, f: int = 2,
             steps: Optional[int] = None, device: Optional[torch.device] = None,
-            dtype: Optional[str] = None, tau: float = 1.0, seed: int = 2019) -> Dict[str, object]:
+            dtype: Optional[str] = None, tau: float = 1.0, seed: int = 2019,
+            pre: str = "none") -> Dict[str, object]:
     from consensusml_amd.parallel.dist import DistInfo
     from consensusml_amd.trainer.trainer import ConsensusTrainer
     if device is None:
         device = torch.device("cuda:0" if torch.cuda.is_available() else "cpu")
     if dtype is None:
         dtype = "bf16" if device.type == "cuda" else "fp32"
-    cfg = make_config(task, rule, attack, n, f, steps, dtype, tau, seed)
+    cfg = make_config(task, rule, attack, n, f, steps, dtype, tau, seed, pre)
     tr = ConsensusTrainer(cfg, info=DistInfo(0, 1, 0, device, "none"))
     t0 = time.perf_counter()
     res = tr.fit(cfg.steps, log_every=0)
@@ -140,7 +146,9 @@ def run_one(task: str, rule: str, attack: str, n: int = 8, f: int = 2,
            "dtype": dtype, "device": device.type,
            "initial_loss": hist[0], "final_train_loss": final, "eval_loss": ev["loss"],
            "eval_accuracy": ev["accuracy"], "diverged": not finite, "wall_s": round(wall, 2)}
-    if rule in ("krum", "multi_krum"):
+    if pre != "none":
+        out["pre"] = pre
+    if rule in ("krum", "multi_krum") and pre == "none":
         tot = sum(sel)
         out["byzantine_selected_frac"] = (sum(sel[b] for b in byz) / tot) if tot else 0.0
     if rule == "centered_clip":
@@ -158,8 +166,9 @@ def markdown(rows: List[Dict[str, object]]) -> str:
         rules = [u for u in RULES if any(r["rule"] == u for r in rs)]
         params = {r["attack"]: r["attack_params"] for r in rs}
         r0 = rs[0]
+        pre = f", agg.pre={r0['pre']}" if r0.get("pre") else ""
         lines.append(f"### {task}: n = {r0['n']} workers, {r0.get('f', 2)} Byzantine, "
-                     f"{r0['steps']} steps, {r0['dtype']} on {r0['device']}")
+                     f"{r0['steps']} steps, {r0['dtype']} on {r0['device']}{pre}")
         lines.append("")
         lines.append("Held-out accuracy / final training loss (mean of the last 10 steps); "
                      "`DIV` = diverged (non-finite).")
@@ -200,12 +209,17 @@ def main():
     ap.add_argument("--dtype", default=None)
     ap.add_argument("--jsonl", default=None)
     ap.add_argument("--md", default=None)
+    ap.add_argument("--pre", choices=("none", "nnm"), default="none",
+                    help="pre-aggregation (agg.pre); nnm skips mean and bulyan")
     a = ap.parse_args()
     dev = torch.device(a.device) if a.device else None
     rows = []
     for rule in a.rules.split(","):
+        if a.pre != "none" and rule in ("mean", "bulyan"):
+            continue
         for attack in a.attacks.split(","):
-            r = run_one(a.task, rule, attack, a.n, a.f, a.steps or None, dev, a.dtype, a.tau)
+            r = run_one(a.task, rule, attack, a.n, a.f, a.steps or None, dev, a.dtype, a.tau,
+                        pre=a.pre)
             rows.append(r)
             line = json.dumps(r)
             print(line, flush=True)

@@ -19,6 +19,7 @@ import yaml
 RULES = ("mean", "median", "trimmed_mean", "krum", "multi_krum", "geomed", "bulyan", "centered_clip")
 TOPOLOGIES = ("allreduce", "allgather", "sharded", "gossip")
 GOSSIP_GRAPHS = ("ring", "exp", "exp_all")
+PRE = ("none", "nnm")
 FAULTS = ("none", "sign_flip", "gaussian", "scaled", "zero", "nan", "alie", "ipm")
 
 
@@ -39,6 +40,11 @@ class AggConfig:
                   uncentered pass first to pick it
     gram_two_pass every step: uncentered pass -> medoid -> centered pass (+ a second Gram
                   all-reduce in the sharded topology); the round-3 scheme
+    pre           pre-aggregation, one of PRE. ``nnm``: nearest-neighbour mixing (Allouah et al.
+                  2023) -- each worker row is replaced by the mean of its n - f nearest rows
+                  (itself included, distances from the Gram matrix) before the rule runs.
+                  allgather / sharded topologies; every rule but mean and bulyan; coordinate
+                  rules with n <= 32
     """
     rule: str = "mean"
     f: int = 0
@@ -51,10 +57,21 @@ class AggConfig:
     clip_iters: int = 3
     centered_gram: bool = True
     gram_two_pass: bool = False
+    pre: str = "none"
 
     def validate(self, n: int) -> None:
         if self.rule not in RULES:
             raise ValueError(f"unknown aggregation rule {self.rule!r}; choose from {RULES}")
+        if self.pre not in PRE:
+            raise ValueError(f"unknown pre-aggregation {self.pre!r}; choose from {PRE}")
+        if self.pre == "nnm":
+            if self.rule in ("mean", "bulyan"):
+                raise ValueError(f"agg.pre=nnm is not implemented for rule {self.rule!r}")
+            if n <= 2 * self.f:
+                raise ValueError(f"agg.pre=nnm needs n > 2f (n={n}, f={self.f})")
+            if self.rule in ("median", "trimmed_mean") and n > 32:
+                raise ValueError(f"agg.pre=nnm with {self.rule} supports at most 32 workers "
+                                 f"(n={n})")
         # the HIP kernels keep one worker row per lane of a 64-wide wave; centered clipping adds
         # the previous aggregate as row n
         limit = 63 if self.rule == "centered_clip" else 64
@@ -190,6 +207,9 @@ class TrainConfig:
     def validate(self, n_workers: int) -> "TrainConfig":
         self.agg.validate(n_workers)
         self.topology.validate()
+        if self.agg.pre != "none" and self.topology.kind in ("gossip", "allreduce"):
+            raise ValueError(f"agg.pre={self.agg.pre} needs the allgather or sharded topology "
+                             f"(got {self.topology.kind!r}: no worker rows to mix)")
         self.fault.validate()
         return self
 

@@ -17,8 +17,9 @@ from . import reference as ref
 from .native import lib
 
 RULE_IDS = {"mean": 0, "krum": 1, "multi_krum": 2, "geomed": 3, "centered_clip": 4,
-            "bulyan_select": 5}
+            "bulyan_select": 5, "nnm_only": 6}
 COORD_RULES = ("median", "trimmed_mean")
+PRE_IDS = {"none": 0, "nnm": 1}
 GRAM_RULES = ("krum", "multi_krum", "geomed", "centered_clip")
 GOSSIP_MAX_NBRS = 8   # neighbour buffers one gossip_mix_k launch reads (kMaxNbrs, gossip_fault.hip)
 
@@ -68,28 +69,35 @@ def agg_update(X: torch.Tensor, *, combine: str, lo: int = 0, cnt: int = 1,
                n: Optional[int] = None, D: Optional[int] = None, opt: Optional[OptArgs] = None,
                master: Optional[torch.Tensor] = None, s1: Optional[torch.Tensor] = None,
                s2: Optional[torch.Tensor] = None, param_out: Optional[torch.Tensor] = None,
-               gout: Optional[torch.Tensor] = None) -> None:
+               gout: Optional[torch.Tensor] = None,
+               mix: Optional[torch.Tensor] = None) -> None:
     """Aggregate worker rows and apply the optimizer in one pass (in place on the state).
 
     combine='sorted'   mean of sorted ranks [lo, lo+cnt) per coordinate
     combine='weighted' sum_i w_i x_i (w None -> all ones)
+    mix                sorted combine only: fp32 [n, n] on X's device, a linear pre-mix of the
+                       rows per coordinate, y_i = sum_j mix[i, j] x_j in fp32, before the sort
+                       (n <= 32). A zero entry contributes nothing even where x_j is NaN / inf.
     """
     X = _as2d(X)
     n = n if n is not None else (rows.numel() if rows is not None else X.shape[0])
     D = D if D is not None else X.shape[1]
     opt = opt or OptArgs(kind="none")
+    _check_mix(mix, combine, n)
     if X.is_cuda:
         bc1 = 1.0 - opt.beta1 ** opt.step
         bc2 = 1.0 - opt.beta2 ** opt.step
         lib().agg_update(X, n, D, rows, 0 if combine == "sorted" else 1, lo, cnt, w, opt.opt_id(),
                          master, s1, s2, param_out, gout, opt.lr, opt.momentum, opt.weight_decay,
                          opt.beta1, opt.beta2, opt.eps, opt.lr / bc1, 1.0 / math.sqrt(bc2),
-                         opt.gscale, opt.nesterov, opt.first)
+                         opt.gscale, opt.nesterov, opt.first, mix)
         return
     # ---- CPU reference path
     Xr = X[rows.long()] if rows is not None else X[:n]
     Xr = Xr[:, :D].float()
     if combine == "sorted":
+        if mix is not None:
+            Xr = ref.mix_rows(mix[:n, :n].float().cpu(), Xr, torch.float32)
         S, _ = torch.sort(ref._sanitize(Xr), dim=0)
         g = S[lo:lo + cnt].mean(0)
     else:
@@ -118,6 +126,18 @@ def agg_update(X: torch.Tensor, *, combine: str, lo: int = 0, cnt: int = 1,
         param_out[:D].copy_(master[:D].to(param_out.dtype))
 
 
+def _check_mix(mix: Optional[torch.Tensor], combine: str, n: int) -> None:
+    if mix is None:
+        return
+    if combine != "sorted":
+        raise ValueError("mix is a pre-mix of the sorted combine only")
+    if n > 32:
+        raise ValueError(f"the mixed sorted combine supports at most 32 rows (n={n})")
+    if mix.dtype != torch.float32 or tuple(mix.shape) != (n, n) or not mix.is_contiguous():
+        raise ValueError(f"mix must be a contiguous fp32 [{n}, {n}] tensor, got "
+                         f"{mix.dtype} {tuple(mix.shape)}")
+
+
 # --------------------------------------------------------------------------- Gram + weights
 class GramWorkspace:
     """Per-device cache of the split-K partial buffer of the Gram kernel."""
@@ -138,11 +158,13 @@ def agg_update_multi(segs, *, combine: str, lo: int = 0, cnt: int = 1,
                      w: Optional[torch.Tensor] = None, rows: Optional[torch.Tensor] = None,
                      n: int, opt: Optional[OptArgs] = None, master: Optional[torch.Tensor] = None,
                      s1: Optional[torch.Tensor] = None, s2: Optional[torch.Tensor] = None,
-                     gout: Optional[torch.Tensor] = None) -> None:
+                     gout: Optional[torch.Tensor] = None,
+                     mix: Optional[torch.Tensor] = None) -> None:
     """``agg_update`` over several segments in ONE launch on GPU (the sharded engine's buckets).
     ``segs``: (X [rows, >= D], D, off, param_out) -- worker rows, element count, offset into the
     shared master / s1 / s2 / gout vectors, and the segment's parameters."""
     opt = opt or OptArgs(kind="none")
+    _check_mix(mix, combine, n)
     if segs and segs[0][0].is_cuda and len(segs) <= 16:
         bc1 = 1.0 - opt.beta1 ** opt.step
         bc2 = 1.0 - opt.beta2 ** opt.step
@@ -151,13 +173,13 @@ def agg_update_multi(segs, *, combine: str, lo: int = 0, cnt: int = 1,
                                rows, 0 if combine == "sorted" else 1, lo, cnt, w, opt.opt_id(),
                                master, s1, s2, gout, opt.lr, opt.momentum, opt.weight_decay,
                                opt.beta1, opt.beta2, opt.eps, opt.lr / bc1, 1.0 / math.sqrt(bc2),
-                               opt.gscale, opt.nesterov, opt.first)
+                               opt.gscale, opt.nesterov, opt.first, mix)
         return
     sl = lambda t, o, d: None if t is None else t[o:o + d]   # noqa: E731
     for X, D, off, pout in segs:
         agg_update(X, combine=combine, lo=lo, cnt=cnt, w=w, rows=rows, n=n, D=D, opt=opt,
                    master=sl(master, off, D), s1=sl(s1, off, D), s2=sl(s2, off, D),
-                   param_out=pout, gout=sl(gout, off, D))
+                   param_out=pout, gout=sl(gout, off, D), mix=mix)
 
 
 def gram(X: torch.Tensor, rows: Optional[torch.Tensor] = None, n: Optional[int] = None,
@@ -225,8 +247,17 @@ def robust_weights(G: torch.Tensor, rule: str, n: int, f: int = 0, m: Optional[i
                    w_out: Optional[torch.Tensor] = None, scores: Optional[torch.Tensor] = None,
                    sel: Optional[torch.Tensor] = None, guard: bool = False,
                    center_out: Optional[torch.Tensor] = None,
-                   sel_counts: Optional[torch.Tensor] = None) -> torch.Tensor:
+                   sel_counts: Optional[torch.Tensor] = None, pre: str = "none",
+                   mix_out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Weights over worker rows (fp32 [n] or [n+1] for centered clipping) from the Gram matrix.
+
+    ``pre='nnm'``: nearest-neighbour mixing first. M = ``reference.nnm_matrix(G, n, f)`` (fp32
+    [n, n] into ``mix_out``), the rule runs on the Gram of the mixed rows M G M^T, and the
+    returned weights are M^T w -- weights over the ORIGINAL rows whose weighted sum is the
+    rule's aggregate of the mixed rows. ``scores``, ``sel`` and ``sel_counts`` then refer to the
+    mixed rows; the guard, the non-finite row count and ``center_out`` keep reading the unmixed
+    G. Rule ``'nnm_only'`` (the coordinate rules' mixing matrix) writes only ``mix_out`` (the
+    identity on a tripped guard) and leaves the weights alone.
 
     In the same launch (weights.hip): ``sel_counts`` += (w > 0); ``center_out`` = the medoid of
     G (the next step's Gram center); ``guard`` (G from a pass centered on the previous step's
@@ -237,15 +268,36 @@ def robust_weights(G: torch.Tensor, rule: str, n: int, f: int = 0, m: Optional[i
     count of non-finite rows, and only an increase trips -- so workers that are genuinely
     non-finite (even half of them) are aggregated around instead of freezing the weights."""
     dim = n + 1 if rule == "centered_clip" else n
+    if pre not in PRE_IDS:
+        raise ValueError(f"unknown pre-aggregation {pre!r}; choose from {tuple(PRE_IDS)}")
+    only = rule == "nnm_only"
+    if (pre == "nnm" and rule in ("mean", "bulyan_select")) or (only and pre != "nnm"):
+        raise ValueError(f"pre={pre!r} is not defined for rule {rule!r}")
+    if only and mix_out is None:
+        raise ValueError("rule 'nnm_only' needs mix_out")
     if G.is_cuda:
         if w_out is None:
             w_out = torch.empty(dim, dtype=torch.float32, device=G.device)
         lib().robust_weights(G.contiguous(), RULE_IDS[rule], n, f, m or 0, iters, eps, tol, tau,
-                             w_out, scores, sel, guard, center_out, sel_counts)
+                             w_out, scores, sel, guard, center_out, sel_counts, PRE_IDS[pre],
+                             mix_out)
         return w_out
     if guard and center_out is not None and int(center_out.reshape(-1)[0]) < 0:
         guard = False
-    w = _robust_weights_ref(G, rule, n, f, m, iters, eps, tol, tau, scores, sel)
+    Me = None
+    if pre == "nnm":
+        M = ref.nnm_matrix(G, n, f)
+        if mix_out is not None:
+            mix_out.copy_(M.float())
+        Me = ref.nnm_extend(M, dim)
+    if only:
+        w = torch.zeros(n) if w_out is None else w_out.clone()
+    else:
+        Gr = G if Me is None else ref.nnm_gram(G[:dim, :dim], Me)
+        w = _robust_weights_ref(Gr, rule, n, f, m, iters, eps, tol, tau, scores, sel)
+    picked = w[:n] > 0                      # selections: over the (mixed) rows the rule saw
+    if Me is not None and not only:
+        w = (Me.t() @ w.double()).float()   # weights over the original rows
     nbad = int((~torch.isfinite(torch.diagonal(G)[:n])).sum())
     trip = guard and nbad > 0 and 2 * nbad >= n
     if center_out is not None and center_out.numel() >= 2:
@@ -256,10 +308,17 @@ def robust_weights(G: torch.Tensor, rule: str, n: int, f: int = 0, m: Optional[i
         w = torch.zeros_like(w)
         if rule == "centered_clip":
             w[n] = 1.0
+        picked = torch.zeros_like(picked)
         if sel is not None and rule != "bulyan_select":
             sel[:n].zero_()
+        if only:
+            mix_out.copy_(torch.eye(n))
+    if only:
+        if center_out is not None:
+            center_out.reshape(-1)[0] = -1 if trip else ref.gram_center(G[:n, :n])
+        return w if w_out is None else w_out
     if sel_counts is not None:
-        sel_counts += (w[:n] > 0).double()
+        sel_counts += picked.double()
     if center_out is not None:
         center_out.reshape(-1)[0] = -1 if trip else ref.gram_center(G[:n, :n])
     if w_out is not None:
@@ -302,25 +361,33 @@ def _robust_weights_ref(G, rule, n, f, m, iters, eps, tol, tau, scores, sel) -> 
 # --------------------------------------------------------------------------- high level
 def aggregate(X: torch.Tensor, rule: str, f: int = 0, trim: Optional[int] = None,
               m: Optional[int] = None, iters: int = 8, eps: float = 1e-6, tau: float = 10.0,
-              clip_iters: int = 3, v0: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """Full robust aggregate of a local [n, D] worker matrix -> fp32 [D] (native on GPU)."""
+              clip_iters: int = 3, v0: Optional[torch.Tensor] = None,
+              pre: str = "none") -> torch.Tensor:
+    """Full robust aggregate of a local [n, D] worker matrix -> fp32 [D] (native on GPU).
+    ``pre='nnm'``: the rule on the nearest-neighbour-mixed rows (``robust_weights``)."""
     X = _as2d(X)
     n, D = X.shape
     out = torch.empty(D, dtype=torch.float32, device=X.device)
+    if pre != "none" and rule in ("mean", "bulyan"):
+        raise ValueError(f"pre={pre!r} is not defined for rule {rule!r}")
     if rule in ("mean",):
         agg_update(X, combine="weighted", w=torch.full((n,), 1.0 / n, device=X.device), gout=out)
     elif rule in COORD_RULES:
         lo, cnt = sorted_range(rule, n, f if trim is None else trim)
-        agg_update(X, combine="sorted", lo=lo, cnt=cnt, gout=out)
+        mix = None
+        if pre != "none":
+            mix = torch.empty(n, n, dtype=torch.float32, device=X.device)
+            robust_weights(gram(X), "nnm_only", n, f, pre=pre, mix_out=mix)
+        agg_update(X, combine="sorted", lo=lo, cnt=cnt, gout=out, mix=mix)
     elif rule in ("krum", "multi_krum", "geomed"):
         G = gram(X)
-        w = robust_weights(G, rule, n, f, m, iters, eps)
+        w = robust_weights(G, rule, n, f, m, iters, eps, pre=pre)
         agg_update(X, combine="weighted", w=w, gout=out)
     elif rule == "centered_clip":
         v0 = torch.zeros(D, dtype=X.dtype, device=X.device) if v0 is None else v0.to(X.dtype)
         Y = torch.cat([X, v0[None]], 0)
         G = gram(Y)
-        c = robust_weights(G, "centered_clip", n, tau=tau, iters=clip_iters)
+        c = robust_weights(G, "centered_clip", n, f, tau=tau, iters=clip_iters, pre=pre)
         # non-finite workers carry weight 0 and are skipped by the weighted kernel
         agg_update(Y, combine="weighted", w=c, n=n + 1, gout=out)
     elif rule == "bulyan":

@@ -197,14 +197,102 @@ def bulyan(X: torch.Tensor, f: int) -> torch.Tensor:
     return trimmed_mean(X[sel.to(X.device)], f)
 
 
+def nnm_matrix(G: torch.Tensor, n: int, f: int) -> torch.Tensor:
+    """Nearest-neighbour mixing (Allouah et al. 2023) from the Gram matrix: float64 [n, n],
+    row-stochastic. Row i averages worker i with its nearest rows, k = n - f in all (itself
+    included, ties -> lower index), by d_ij = max(G_ii + G_jj - 2 G_ij, 0) (NaN -> +inf).
+    A row with a non-finite G_ii is bad: it is nobody's neighbour and keeps M_i = e_i, so the
+    rules' own handling of non-finite rows applies to it unchanged. With fewer than k good rows
+    every good row averages all of them. Only the leading n x n block of G is read."""
+    G = G[:n, :n].double()
+    d = torch.diagonal(G)
+    bad = ~torch.isfinite(d)
+    D = (d[:, None] + d[None, :] - 2.0 * G).clamp_min(0.0)
+    D = torch.where(torch.isnan(D), torch.full_like(D, float("inf")), D)
+    good = [j for j in range(n) if not bool(bad[j])]
+    take = min(max(n - f, 1), len(good))
+    M = torch.zeros(n, n, dtype=torch.float64, device=G.device)
+    for i in range(n):
+        if bool(bad[i]):
+            M[i, i] = 1.0
+            continue
+        # i itself ranks first whatever duplicates of it exist
+        order = sorted(good, key=lambda j: (-1.0 if j == i else D[i, j].item(), j))
+        M[i, order[:take]] = 1.0 / take
+    return M
+
+
+def mix_rows(M: torch.Tensor, X: torch.Tensor, dtype: torch.dtype = torch.float64
+             ) -> torch.Tensor:
+    """Y = M X, summed in ``dtype`` and returned as fp32 rows. A zero entry of M contributes
+    nothing even where X is NaN / inf (the weighted combine's convention); a non-finite x_j
+    under a non-zero M_ij propagates as in IEEE arithmetic."""
+    M = M.to(dtype)
+    Xd = X.to(dtype)
+    fin = torch.isfinite(Xd)
+    Y = M @ torch.where(fin, Xd, torch.zeros_like(Xd))
+    pos, neg = (M > 0).to(dtype), (M < 0).to(dtype)
+    xp, xn = (Xd == float("inf")).to(dtype), (Xd == float("-inf")).to(dtype)
+    pinf = (pos @ xp + neg @ xn) > 0
+    ninf = (pos @ xn + neg @ xp) > 0
+    nan = (((M != 0).to(dtype) @ torch.isnan(Xd).to(dtype)) > 0) | (pinf & ninf)
+    Y = torch.where(pinf, torch.full_like(Y, float("inf")), Y)
+    Y = torch.where(ninf, torch.full_like(Y, float("-inf")), Y)
+    return torch.where(nan, torch.full_like(Y, float("nan")), Y).float()
+
+
+def nnm_extend(M: torch.Tensor, rows: int) -> torch.Tensor:
+    """M extended by the identity to ``rows`` rows (centered clipping's previous aggregate)."""
+    n = M.shape[0]
+    if rows == n:
+        return M
+    E = torch.eye(rows, dtype=M.dtype, device=M.device)
+    E[:n, :n] = M
+    return E
+
+
+def nnm_gram(G: torch.Tensor, M: torch.Tensor) -> torch.Tensor:
+    """Gram of the mixed rows Y = M X from the Gram of X: M G M^T for a mixing matrix whose rows
+    are uniform on their support (``nnm_matrix``). Summed over each support in index order, as
+    weights.hip does: mixed rows with the same neighbours (common with NNM -- a tight cluster
+    mixes to one point) then get bit-identical Gram rows, so their scores tie exactly and the
+    rules' lower-index tie-break decides, on every device alike. A zero entry contributes
+    nothing, so a bad row's non-finite entries stay in its own row and column."""
+    G = G.double()
+    r = G.shape[0]
+    sup = [torch.nonzero(M[i]).flatten().tolist() for i in range(r)]
+    inv = [1.0 / len(s) for s in sup]
+    T = torch.zeros_like(G)          # T = G M^T
+    for j in range(r):
+        acc = torch.zeros(r, dtype=torch.float64, device=G.device)
+        for b in sup[j]:
+            acc = acc + G[:, b]
+        T[:, j] = acc * inv[j]
+    Gm = torch.zeros_like(G)         # G' = M T
+    for i in range(r):
+        acc = torch.zeros(r, dtype=torch.float64, device=G.device)
+        for a in sup[i]:
+            acc = acc + T[a, :]
+        Gm[i, :] = acc * inv[i]
+    return Gm
+
+
 # --------------------------------------------------------------------------- full rules
 
 
 def aggregate(X: torch.Tensor, rule: str, f: int = 0, trim: Optional[int] = None,
               m: Optional[int] = None, iters: int = 8, eps: float = 1e-6,
               tau: float = 10.0, clip_iters: int = 3,
-              v0: Optional[torch.Tensor] = None) -> torch.Tensor:
+              v0: Optional[torch.Tensor] = None, pre: str = "none") -> torch.Tensor:
     n = X.shape[0]
+    if pre == "nnm":
+        # the rule on the mixed rows Y = M X (the previous aggregate of centered clipping is
+        # not a worker row and stays unmixed)
+        if rule in ("mean", "bulyan"):
+            raise ValueError(f"pre='nnm' is not defined for rule {rule!r}")
+        X = mix_rows(nnm_matrix(gram(X), n, f), X)
+    elif pre != "none":
+        raise ValueError(f"unknown pre-aggregation {pre!r}")
     if rule == "mean":
         return mean(X)
     if rule == "median":

@@ -106,6 +106,10 @@ class ConsensusEngine:
         cfg.validate(self.n)
         self.topo = cfg.topology.kind
         self.rule = cfg.agg.rule
+        self.pre = cfg.agg.pre
+        # this configuration needs the Gram matrix: a Gram-space rule, or nearest-neighbour
+        # mixing (whose mixing matrix comes from G, also for the coordinate rules)
+        self.needs_gram = self.rule in GRAM_RULES or self.pre == "nnm"
         if self.topo == "allreduce" and self.rule != "mean":
             raise ValueError("the allreduce topology only implements the mean rule")
         pdtype = next(p for p in model.parameters() if p.requires_grad).dtype
@@ -154,6 +158,9 @@ class ConsensusEngine:
         self.scores = torch.zeros(self.n, dtype=torch.float64, device=dev)
         self.sel = torch.zeros(self.n + 1, dtype=torch.int32, device=dev)
         self.sel_counts = torch.zeros(self.n, dtype=torch.float64, device=dev)
+        # agg.pre=nnm: this step's mixing matrix (weights.hip), recomputed from G every step
+        self.M = (torch.eye(self.n, dtype=torch.float32, device=dev)
+                  if self.pre == "nnm" else None)
         # [centered-Gram row, non-finite rows of the previous pass] (weights.hip guard state)
         self.center = torch.zeros(2, dtype=torch.int32, device=dev)
         self.have_center = False    # self.center holds a medoid from an earlier step
@@ -220,7 +227,7 @@ class ConsensusEngine:
         # holds bucket b's local X X^T. A slot is filled as soon as that bucket's exchange has
         # landed -- polled from the gradient hooks while backward still runs -- and step() sums
         # the slots in bucket order, so the result does not depend on when each was computed.
-        self.early_gram = bool(cfg.topology.early_gram and self.rule in GRAM_RULES
+        self.early_gram = bool(cfg.topology.early_gram and self.needs_gram
                                and self.group_active
                                and self.topo in ("sharded", "allgather"))
         self.Gb = (torch.zeros(len(fl.buckets), self.rows_total, self.rows_total,
@@ -702,6 +709,8 @@ class ConsensusEngine:
             if self.group_active and self.topo == "sharded" and self.N > 1:
                 dist.all_reduce(self.G)
         rule = "bulyan_select" if self.rule == "bulyan" else self.rule
+        if self.rule not in GRAM_RULES:
+            rule = "nnm_only"    # median / trimmed mean with agg.pre=nnm: the mixing matrix only
         m = cfg.m if cfg.m is not None else self.n - cfg.f
         iters = cfg.clip_iters if rule == "centered_clip" else cfg.iters
         # one launch: weights, selection counts and -- centered Gram -- the medoid of this step's
@@ -714,7 +723,7 @@ class ConsensusEngine:
                          tol=cfg.tol, tau=cfg.tau, w_out=self.w, scores=self.scores, sel=self.sel,
                          guard=center is not None,
                          center_out=self.center if cfg.centered_gram else None,
-                         sel_counts=self.sel_counts)
+                         sel_counts=self.sel_counts, pre=self.pre, mix_out=self.M)
         if cfg.centered_gram:
             self.have_center = True
 
@@ -738,7 +747,7 @@ class ConsensusEngine:
             trim = cfg.trim if cfg.trim is not None else cfg.f
             lo, cnt = K.sorted_range(self.rule, self.n, trim)
             K.agg_update(X, combine="sorted", lo=lo, cnt=cnt, n=self.n, D=length, opt=opt,
-                         master=m, s1=s1, s2=s2, param_out=param_out, gout=gout)
+                         master=m, s1=s1, s2=s2, param_out=param_out, gout=gout, mix=self.M)
         elif self.rule == "bulyan":
             theta = self.n - 2 * cfg.f
             lo, cnt = K.sorted_range("trimmed_mean", theta, cfg.f)
@@ -757,7 +766,7 @@ class ConsensusEngine:
         if self.rule in ("median", "trimmed_mean"):
             trim = cfg.trim if cfg.trim is not None else cfg.f
             lo, cnt = K.sorted_range(self.rule, self.n, trim)
-            K.agg_update_multi(ks, combine="sorted", lo=lo, cnt=cnt, n=self.n, **st)
+            K.agg_update_multi(ks, combine="sorted", lo=lo, cnt=cnt, n=self.n, mix=self.M, **st)
         elif self.rule == "bulyan":
             theta = self.n - 2 * cfg.f
             lo, cnt = K.sorted_range("trimmed_mean", theta, cfg.f)
@@ -783,7 +792,7 @@ class ConsensusEngine:
         for b in fl.buckets:
             self._wait(b)
         cols = self._bucket_cols()
-        if self.rule in GRAM_RULES:
+        if self.needs_gram:
             self._compute_weights(cols)
         if self.record_stats:
             self._record_stats(cols)
@@ -800,7 +809,7 @@ class ConsensusEngine:
         for b in fl.buckets:
             self._wait(b)
         cols = self._bucket_cols()
-        if self.rule in GRAM_RULES:
+        if self.needs_gram:
             self._compute_weights(cols)
         if self.record_stats:
             self._record_stats(cols)
@@ -994,7 +1003,7 @@ class ConsensusEngine:
             trim = cfg.trim if cfg.trim is not None else cfg.f
             lo, cnt = K.sorted_range(self.rule, self.n, trim)
             K.agg_update(X, combine="sorted", lo=lo, cnt=cnt, n=self.n, D=length, opt=none,
-                         gout=out)
+                         gout=out, mix=self.M)
         elif self.rule == "bulyan":
             theta = self.n - 2 * cfg.f
             lo, cnt = K.sorted_range("trimmed_mean", theta, cfg.f)

@@ -43,6 +43,20 @@ T* opt_ptr(const optional<Tensor>& t, at::ScalarType st, const char* name, int64
   return reinterpret_cast<T*>(t->data_ptr());
 }
 
+// mix of the sorted combine: contiguous fp32 [n, n] on X's device (a linear pre-mix of the rows)
+const float* mix_ptr(const optional<Tensor>& mix, const Tensor& X, int64_t n, int64_t combine) {
+  if (!mix.has_value() || !mix->defined()) return nullptr;
+  TORCH_CHECK(combine == cml::CMB_SORTED, "mix is a pre-mix of the sorted combine only");
+  TORCH_CHECK(n <= 32, "the mixed sorted combine supports at most 32 rows, got ", n);
+  check_dev(*mix, "mix");
+  TORCH_CHECK(mix->get_device() == X.get_device(), "mix must be on X's device");
+  TORCH_CHECK(mix->scalar_type() == at::kFloat, "mix has dtype ", mix->scalar_type(),
+              ", expected Float");
+  TORCH_CHECK(mix->dim() == 2 && mix->size(0) == n && mix->size(1) == n && mix->is_contiguous(),
+              "mix must be a contiguous [n, n] tensor");
+  return mix->data_ptr<float>();
+}
+
 // X: [R, C] rows of workers (row stride arbitrary, unit column stride). The aggregation uses n
 // rows (rows[i] indexes X when given) and the first D columns.
 void agg_update(const Tensor& X, int64_t n, int64_t D, const optional<Tensor>& rows, int64_t combine,
@@ -51,7 +65,7 @@ void agg_update(const Tensor& X, int64_t n, int64_t D, const optional<Tensor>& r
                 const optional<Tensor>& s2, const optional<Tensor>& param_out,
                 const optional<Tensor>& gout, double lr, double momentum, double weight_decay,
                 double beta1, double beta2, double eps, double step_size, double inv_sqrt_bc2,
-                double gscale, bool nesterov, bool first) {
+                double gscale, bool nesterov, bool first, const optional<Tensor>& mix) {
   check_dev(X, "X");
   TORCH_CHECK(X.dim() == 2 && X.stride(1) == 1, "X must be 2-D with unit column stride");
   TORCH_CHECK(n >= 1 && n <= 64, "1 <= n <= 64 workers supported, got ", n);
@@ -94,8 +108,9 @@ void agg_update(const Tensor& X, int64_t n, int64_t D, const optional<Tensor>& r
   u.nesterov = nesterov ? 1 : 0;
   u.first = first ? 1 : 0;
   u.adam_l2 = adam_l2;
+  const float* mx = mix_ptr(mix, X, n, combine);
   CML_CHECK_HIP(cml::launch_agg_update(dtype_of(X), static_cast<int>(combine), static_cast<int>(opt),
-                                       s, u, D, cur_stream()));
+                                       s, u, D, cur_stream(), mx));
 }
 
 // The same rule + optimizer over several segments (the sharded engine's buckets) in one launch:
@@ -109,7 +124,7 @@ void agg_update_multi(const std::vector<Tensor>& Xs, const std::vector<int64_t>&
                       const optional<Tensor>& gout, double lr, double momentum,
                       double weight_decay, double beta1, double beta2, double eps,
                       double step_size, double inv_sqrt_bc2, double gscale, bool nesterov,
-                      bool first) {
+                      bool first, const optional<Tensor>& mix) {
   const size_t ns = Xs.size();
   TORCH_CHECK(ns >= 1 && ns <= 16 && Ds.size() == ns && offs.size() == ns && pouts.size() == ns,
               "agg_update_multi: 1..16 segments with matching Xs / Ds / offs / pouts");
@@ -165,9 +180,10 @@ void agg_update_multi(const std::vector<Tensor>& Xs, const std::vector<int64_t>&
   u.nesterov = nesterov ? 1 : 0;
   u.first = first ? 1 : 0;
   u.adam_l2 = adam_l2;
+  const float* mx = mix_ptr(mix, Xs[0], n, combine);
   CML_CHECK_HIP(cml::launch_agg_update_multi(dtype_of(Xs[0]), static_cast<int>(combine),
                                              static_cast<int>(opt), s, u, segs.data(),
-                                             static_cast<int>(ns), cur_stream()));
+                                             static_cast<int>(ns), cur_stream(), mx));
 }
 
 int64_t gram_workspace_bytes(int64_t n, int64_t D) {
@@ -248,7 +264,8 @@ void gram_center(const Tensor& G, int64_t n, Tensor& out) {
 void robust_weights(const Tensor& G, int64_t rule, int64_t n, int64_t f, int64_t m, int64_t iters,
                     double eps, double tol, double tau, Tensor& w, const optional<Tensor>& scores,
                     const optional<Tensor>& sel, bool guard, const optional<Tensor>& center_out,
-                    const optional<Tensor>& sel_counts) {
+                    const optional<Tensor>& sel_counts, int64_t pre,
+                    const optional<Tensor>& mix_out) {
   TORCH_CHECK(G.is_cuda() && G.scalar_type() == at::kDouble && G.is_contiguous(), "G: fp64 GPU");
   const int64_t dim = rule == cml::RULE_CCLIP ? n + 1 : n;
   TORCH_CHECK(G.numel() >= dim * dim, "G too small");
@@ -260,11 +277,14 @@ void robust_weights(const Tensor& G, int64_t rule, int64_t n, int64_t f, int64_t
   // a 2-element center buffer carries the guard's non-finite-row count of the previous pass
   int* nb = (co && center_out->numel() >= 2) ? co + 1 : nullptr;
   double* cnt = opt_ptr<double>(sel_counts, at::kDouble, "sel_counts", n);
+  TORCH_CHECK(pre == 0 || pre == 1, "pre: 0 (none) or 1 (nearest-neighbour mixing)");
+  float* mo = opt_ptr<float>(mix_out, at::kFloat, "mix_out", n * n);
+  if (mo) TORCH_CHECK(mix_out->get_device() == G.get_device(), "mix_out must be on G's device");
   CML_CHECK_HIP(cml::launch_robust_weights(static_cast<int>(rule), G.data_ptr<double>(),
                                            static_cast<int>(n), static_cast<int>(f),
                                            static_cast<int>(m), static_cast<int>(iters), eps, tol,
                                            tau, w.data_ptr<float>(), sc, se, cur_stream(),
-                                           guard ? 1 : 0, co, cnt, nb));
+                                           guard ? 1 : 0, co, cnt, nb, static_cast<int>(pre), mo));
 }
 
 // G = sum over b of Gb[b] (fp64 [nb, r, r] -> [r, r]) in bucket order
@@ -2604,7 +2624,14 @@ Tensor norm_bwd_seg(const Tensor& dy_in, const optional<Tensor>& dres_in, const 
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.doc() = "consensusml_amd native HIP kernels for gfx950 (MI355X)";
-  m.def("agg_update", &agg_update, "fused robust aggregation + optimizer update");
+  m.def("agg_update", &agg_update, "fused robust aggregation + optimizer update (mix: a linear "
+        "pre-mix of the rows ahead of the sorted combine)",
+        py::arg("X"), py::arg("n"), py::arg("D"), py::arg("rows"), py::arg("combine"),
+        py::arg("lo"), py::arg("cnt"), py::arg("w"), py::arg("opt"), py::arg("master"),
+        py::arg("s1"), py::arg("s2"), py::arg("param_out"), py::arg("gout"), py::arg("lr"),
+        py::arg("momentum"), py::arg("weight_decay"), py::arg("beta1"), py::arg("beta2"),
+        py::arg("eps"), py::arg("step_size"), py::arg("inv_sqrt_bc2"), py::arg("gscale"),
+        py::arg("nesterov"), py::arg("first"), py::arg("mix") = py::none());
   m.def("gram_workspace_bytes", &gram_workspace_bytes);
   m.def("gram", &gram, "G = X X^T (fp64) on MFMA; center: rows relative to that row",
         py::arg("X"), py::arg("n"), py::arg("D"), py::arg("rows"), py::arg("work"), py::arg("G"),
@@ -2615,14 +2642,20 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("G"), py::arg("rule"), py::arg("n"), py::arg("f"), py::arg("m"), py::arg("iters"),
         py::arg("eps"), py::arg("tol"), py::arg("tau"), py::arg("w"), py::arg("scores"),
         py::arg("sel"), py::arg("guard") = false, py::arg("center_out") = py::none(),
-        py::arg("sel_counts") = py::none());
+        py::arg("sel_counts") = py::none(), py::arg("pre") = 0, py::arg("mix_out") = py::none());
   m.def("gram_sum", &gram_sum, "sum of per-bucket Gram partials in bucket order");
   m.def("gram_partial", &gram_partial, "Gram stage 1 into a per-bucket workspace (block count)",
         py::arg("X"), py::arg("n"), py::arg("D"), py::arg("work"), py::arg("center") = py::none());
   m.def("gram_reduce_multi", &gram_reduce_multi,
         "reduce several buckets' Gram partials into G in one launch (bucket order)");
   m.def("agg_update_multi", &agg_update_multi,
-        "fused robust aggregation + optimizer step over several buckets in one launch");
+        "fused robust aggregation + optimizer step over several buckets in one launch",
+        py::arg("Xs"), py::arg("Ds"), py::arg("offs"), py::arg("pouts"), py::arg("n"),
+        py::arg("rows"), py::arg("combine"), py::arg("lo"), py::arg("cnt"), py::arg("w"),
+        py::arg("opt"), py::arg("master"), py::arg("s1"), py::arg("s2"), py::arg("gout"),
+        py::arg("lr"), py::arg("momentum"), py::arg("weight_decay"), py::arg("beta1"),
+        py::arg("beta2"), py::arg("eps"), py::arg("step_size"), py::arg("inv_sqrt_bc2"),
+        py::arg("gscale"), py::arg("nesterov"), py::arg("first"), py::arg("mix") = py::none());
   m.def("gossip_workspace_bytes", &gossip_workspace_bytes);
   m.def("gossip_mix", &gossip_mix, "ring gossip mixing with neighbour clipping");
   m.def("gossip_mix_k", &gossip_mix_k, "k-neighbour gossip mixing with neighbour clipping (optional "

@@ -23,6 +23,7 @@ namespace cml {
 constexpr int kBlock = 256;
 constexpr int kMaxRows = 64;
 constexpr int kMaxSegs = 16;   // segments of one multi-segment launch
+constexpr int kMaxMixRows = 32;   // rows of the mixed sorted combine (x and y live in VGPRs)
 
 // Optimizer state of VEC coordinates, loaded BEFORE the combine so those HBM reads are in flight
 // while the sort / weighted sum runs (hipcc does not hoist them above the VALU work by itself).
@@ -223,6 +224,140 @@ __device__ __forceinline__ void agg_sorted_bf16_body(const SrcArgs& s, const Upd
   }
 }
 
+// ----------------------------------------------------------------------------- mixed sorted combine
+// A linear pre-mix of the rows ahead of the sort (nearest-neighbour mixing for the coordinate
+// rules): per coordinate y_i = sum_j M_ij x_j in fp32 (an fmaf chain in j order), then the
+// sanitising, network and rank window of agg_sorted_body on y. M (fp32 [n, n]) is staged once per
+// workgroup into LDS, zero-padded to NP x NP, and read back as broadcasts (every lane the same
+// address). x and y are both live during the mix, so VEC is chosen per NP to keep 2 NP VEC fp32
+// in registers (mixed_vec below); the mixed values are fp32, so bf16 rows take the fp32 network.
+//
+// "M_ij == 0 contributes nothing even where x_j is NaN / inf": with every loaded value finite a
+// zero entry adds an exact zero, so the fast path is plain (packed) FMAs. One extra FMA per loaded
+// value (x * 0 accumulates to NaN iff some x is non-finite) detects the other case, and a wave
+// that saw a non-finite value redoes its mix with the zero entries skipped by a select.
+template <int NP, int VEC>
+__device__ __forceinline__ void mix_rows(const float (&sM)[NP * NP], const float (&x)[NP][VEC],
+                                         float (&y)[NP][VEC], int n) {
+  // M is re-read from LDS as it is used: its NP^2 values are loop invariant, and hipcc would
+  // otherwise hoist all of them into VGPRs (NP = 16: 256 registers, spilling). An offset it
+  // cannot see through (always 0) keeps the broadcast reads inside the iteration.
+  int z = 0;
+  asm volatile("" : "+v"(z));
+  float probe = 0.0f;
+#pragma unroll
+  for (int j = 0; j < NP; ++j) {
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) probe = fmaf(x[j][v], 0.0f, probe);
+  }
+  if (__builtin_amdgcn_ballot_w64(probe != probe) == 0) {   // wave-uniform
+#pragma unroll
+    for (int i = 0; i < NP; ++i) {
+      if (i < n) {   // n is a kernel argument: a scalar branch per row
+        if constexpr (VEC % 2 == 0) {
+          f32x2 acc[VEC / 2];
+#pragma unroll
+          for (int v = 0; v < VEC / 2; ++v) acc[v] = f32x2{0.0f, 0.0f};
+#pragma unroll
+          for (int j = 0; j < NP; ++j) {
+            const float mij = sM[z + i * NP + j];
+            const f32x2 mm = {mij, mij};
+#pragma unroll
+            for (int v = 0; v < VEC / 2; ++v)
+              acc[v] = __builtin_elementwise_fma(mm, f32x2{x[j][2 * v], x[j][2 * v + 1]}, acc[v]);
+          }
+#pragma unroll
+          for (int v = 0; v < VEC / 2; ++v) {
+            y[i][2 * v] = acc[v].x;
+            y[i][2 * v + 1] = acc[v].y;
+          }
+        } else {
+#pragma unroll
+          for (int v = 0; v < VEC; ++v) y[i][v] = 0.0f;
+#pragma unroll
+          for (int j = 0; j < NP; ++j) {
+            const float mij = sM[z + i * NP + j];
+#pragma unroll
+            for (int v = 0; v < VEC; ++v) y[i][v] = fmaf(mij, x[j][v], y[i][v]);
+          }
+        }
+      } else {   // padding row: replaced by +inf in the caller
+#pragma unroll
+        for (int v = 0; v < VEC; ++v) y[i][v] = 0.0f;
+      }
+    }
+  } else {
+#pragma unroll
+    for (int i = 0; i < NP; ++i) {
+      if (i < n) {
+#pragma unroll
+        for (int v = 0; v < VEC; ++v) y[i][v] = 0.0f;
+#pragma unroll
+        for (int j = 0; j < NP; ++j) {
+          const float mij = sM[z + i * NP + j];
+#pragma unroll
+          for (int v = 0; v < VEC; ++v)
+            y[i][v] = mij != 0.0f ? fmaf(mij, x[j][v], y[i][v]) : y[i][v];
+        }
+      } else {
+#pragma unroll
+        for (int v = 0; v < VEC; ++v) y[i][v] = 0.0f;
+      }
+    }
+  }
+}
+
+template <typename T, int NP, int VEC, int OPT>
+__device__ __forceinline__ void agg_mixed_body(const SrcArgs& s, const UpdArgs& u,
+    const float* __restrict__ mix, int64_t base, int64_t nvec, int blk, int nblk) {
+  __shared__ float sM[NP * NP];
+  for (int k = threadIdx.x; k < NP * NP; k += kBlock) {
+    const int i = k / NP, j = k % NP;
+    sM[k] = (i < s.n && j < s.n) ? mix[i * s.n + j] : 0.0f;
+  }
+  __syncthreads();
+  const T* X = reinterpret_cast<const T*>(s.X);
+  int64_t roff[NP];
+#pragma unroll
+  for (int i = 0; i < NP; ++i) {
+    const int r = i < s.n ? i : s.n - 1;
+    roff[i] = static_cast<int64_t>(s.rows ? s.rows[r] : r) * s.ld + base;
+  }
+  const float inf = __builtin_inff();
+  const float inv = 1.0f / static_cast<float>(s.cnt);
+  const int64_t stride = static_cast<int64_t>(nblk) * kBlock;
+  for (int64_t t = static_cast<int64_t>(blk) * kBlock + threadIdx.x; t < nvec; t += stride) {
+    const int64_t e = t * VEC;
+    float x[NP][VEC];
+#pragma unroll
+    for (int i = 0; i < NP; ++i) load_vec<T, VEC>(X + roff[i] + e, x[i]);
+    OptState<VEC> st;
+    load_state<VEC>(u, OPT, base + e, st);
+    float a[NP][VEC];
+    mix_rows<NP, VEC>(sM, x, a, s.n);
+#pragma unroll
+    for (int i = 0; i < NP; ++i) {
+      const bool pad = i >= s.n;
+#pragma unroll
+      for (int v = 0; v < VEC; ++v) a[i][v] = (pad || a[i][v] != a[i][v]) ? inf : a[i][v];
+    }
+    sort_columns<float, NP, VEC>(a);
+    float g[VEC];
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) g[v] = 0.0f;
+#pragma unroll
+    for (int i = 0; i < NP; ++i) {
+      if (i >= s.lo && i < s.lo + s.cnt) {
+#pragma unroll
+        for (int v = 0; v < VEC; ++v) g[v] += a[i][v];
+      }
+    }
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) g[v] *= inv;
+    update_and_store<VEC>(u, OPT, base + e, g, st);
+  }
+}
+
 // ----------------------------------------------------------------------------- weighted combine
 template <typename T, int VEC, int OPT>
 __device__ __forceinline__ void agg_weighted_body(const SrcArgs& s, const UpdArgs& u, int64_t base,
@@ -296,6 +431,13 @@ __global__ __launch_bounds__(kBlock) void agg_weighted_kernel(SrcArgs s, UpdArgs
   agg_weighted_body<T, VEC, OPT>(s, u, base, nvec, blockIdx.x, gridDim.x);
 }
 
+template <typename T, int NP, int VEC, int OPT>
+__global__ __launch_bounds__(kBlock) void agg_mixed_kernel(SrcArgs s, UpdArgs u,
+                                                           const float* __restrict__ mix,
+                                                           int64_t base, int64_t nvec) {
+  agg_mixed_body<T, NP, VEC, OPT>(s, u, mix, base, nvec, blockIdx.x, gridDim.x);
+}
+
 // Several segments in ONE launch (the sharded engine's buckets: per-bucket worker matrices and
 // parameter shards, one fp32 optimizer-state vector): blockIdx.y = segment. Every segment is on
 // the vector path (checked by the launcher).
@@ -332,6 +474,14 @@ template <typename T, int VEC, int OPT>
 __global__ __launch_bounds__(kBlock) void agg_weighted_multi(SrcArgs s, UpdArgs u, SegTable t) {
   seg_args(t, blockIdx.y, s, u);
   agg_weighted_body<T, VEC, OPT>(s, u, 0, t.nvec[blockIdx.y], blockIdx.x, gridDim.x);
+}
+
+template <typename T, int NP, int VEC, int OPT>
+__global__ __launch_bounds__(kBlock) void agg_mixed_multi(SrcArgs s, UpdArgs u,
+                                                          const float* __restrict__ mix,
+                                                          SegTable t) {
+  seg_args(t, blockIdx.y, s, u);
+  agg_mixed_body<T, NP, VEC, OPT>(s, u, mix, 0, t.nvec[blockIdx.y], blockIdx.x, gridDim.x);
 }
 
 // ----------------------------------------------------------------------------- dispatch
@@ -395,6 +545,55 @@ static void launch_sorted(int opt, const SrcArgs& s, const UpdArgs& u, int64_t b
   }
 }
 
+// Mixed sorted combine: elements per lane by padded row count. x and y (fp32) are live together,
+// 2 NP VEC VGPRs: 64 at NP <= 8 (NP = 4 keeps 16-B bf16 loads), 128 at NP = 16 / 32.
+static int mixed_np(int n) { return n <= 4 ? 4 : n <= 8 ? 8 : n <= 16 ? 16 : 32; }
+static int mixed_vec(int dtype, int n) {
+  const int np = mixed_np(n);
+  if (np == 4) return dtype == DT_BF16 ? 8 : 4;
+  return np <= 16 ? 4 : 2;
+}
+
+template <typename T, int NP, int VEC>
+static void launch_mixed_np(int opt, const SrcArgs& s, const UpdArgs& u, const float* mix,
+                            int64_t base, int64_t nvec, hipStream_t st) {
+  const int g = grid_for(nvec);
+  switch (opt) {
+    case OPT_NONE: agg_mixed_kernel<T, NP, VEC, OPT_NONE><<<g, kBlock, 0, st>>>(s, u, mix, base, nvec); break;
+    case OPT_SGD: agg_mixed_kernel<T, NP, VEC, OPT_SGD><<<g, kBlock, 0, st>>>(s, u, mix, base, nvec); break;
+    default: agg_mixed_kernel<T, NP, VEC, OPT_ADAM><<<g, kBlock, 0, st>>>(s, u, mix, base, nvec); break;
+  }
+}
+
+template <typename T, bool VECTOR>
+static void launch_mixed(int opt, const SrcArgs& s, const UpdArgs& u, const float* mix,
+                         int64_t base, int64_t D, hipStream_t st) {
+  // D: number of elements; VECTOR: D is a multiple of mixed_vec() and all pointers aligned.
+  constexpr bool BF = sizeof(T) == 2;
+  const int np = mixed_np(s.n);
+  if constexpr (VECTOR) {
+    if (np == 4) launch_mixed_np<T, 4, BF ? 8 : 4>(opt, s, u, mix, base, D / (BF ? 8 : 4), st);
+    else if (np == 8) launch_mixed_np<T, 8, 4>(opt, s, u, mix, base, D / 4, st);
+    else if (np == 16) launch_mixed_np<T, 16, 4>(opt, s, u, mix, base, D / 4, st);
+    else launch_mixed_np<T, 32, 2>(opt, s, u, mix, base, D / 2, st);
+  } else {
+    if (np == 4) launch_mixed_np<T, 4, 1>(opt, s, u, mix, base, D, st);
+    else if (np == 8) launch_mixed_np<T, 8, 1>(opt, s, u, mix, base, D, st);
+    else if (np == 16) launch_mixed_np<T, 16, 1>(opt, s, u, mix, base, D, st);
+    else launch_mixed_np<T, 32, 1>(opt, s, u, mix, base, D, st);
+  }
+}
+
+template <typename T, int NP, int VEC>
+static void launch_mixed_multi_np(int opt, const SrcArgs& s, const UpdArgs& u, const float* mix,
+                                  const SegTable& t, dim3 g, hipStream_t st) {
+  switch (opt) {
+    case OPT_NONE: agg_mixed_multi<T, NP, VEC, OPT_NONE><<<g, kBlock, 0, st>>>(s, u, mix, t); break;
+    case OPT_SGD: agg_mixed_multi<T, NP, VEC, OPT_SGD><<<g, kBlock, 0, st>>>(s, u, mix, t); break;
+    default: agg_mixed_multi<T, NP, VEC, OPT_ADAM><<<g, kBlock, 0, st>>>(s, u, mix, t); break;
+  }
+}
+
 template <typename T, int VEC>
 static void launch_weighted(int opt, const SrcArgs& s, const UpdArgs& u, int64_t base, int64_t nvec,
                             hipStream_t st) {
@@ -417,10 +616,12 @@ static int sorted_vec(int dtype, int n) {
 
 template <typename T>
 static hipError_t agg_update_t(int combine, int opt, const SrcArgs& s, const UpdArgs& u, int64_t D,
-                               hipStream_t st) {
+                               hipStream_t st, const float* mix = nullptr) {
   if (D <= 0) return hipSuccess;
   const int esz = sizeof(T);
-  const int vec = combine == CMB_WEIGHTED ? (esz == 2 ? 8 : 4) : sorted_vec(esz == 2 ? DT_BF16 : DT_F32, s.n);
+  const int dt = esz == 2 ? DT_BF16 : DT_F32;
+  const int vec = combine == CMB_WEIGHTED ? (esz == 2 ? 8 : 4)
+                  : mix ? mixed_vec(dt, s.n) : sorted_vec(dt, s.n);
   // The vector path needs every row start and every state pointer aligned to VEC elements.
   bool ok = (s.ld % vec) == 0 && aligned(s.X, vec * esz) && aligned(u.master, vec * 4) &&
             aligned(u.s1, vec * 4) && aligned(u.s2, vec * 4) && aligned(u.gout, vec * 4) &&
@@ -430,12 +631,15 @@ static hipError_t agg_update_t(int combine, int opt, const SrcArgs& s, const Upd
     if (combine == CMB_WEIGHTED) {
       if constexpr (sizeof(T) == 2) launch_weighted<T, 8>(opt, s, u, 0, Dv / 8, st);
       else launch_weighted<T, 4>(opt, s, u, 0, Dv / 4, st);
+    } else if (mix) {
+      launch_mixed<T, true>(opt, s, u, mix, 0, Dv, st);
     } else {
       launch_sorted<T, true>(opt, s, u, 0, Dv, st);
     }
   }
   if (D > Dv) {  // scalar tail (or fully unaligned inputs)
     if (combine == CMB_WEIGHTED) launch_weighted<T, 1>(opt, s, u, Dv, D - Dv, st);
+    else if (mix) launch_mixed<T, false>(opt, s, u, mix, Dv, D - Dv, st);
     else launch_sorted<T, false>(opt, s, u, Dv, D - Dv, st);
   }
   return hipGetLastError();
@@ -461,10 +665,12 @@ static void launch_sorted_multi_np(int opt, const SrcArgs& s, const UpdArgs& u, 
 
 template <typename T>
 static hipError_t agg_update_multi_t(int combine, int opt, const SrcArgs& s, const UpdArgs& u,
-                                     const AggSeg* segs, int nseg, hipStream_t st) {
+                                     const AggSeg* segs, int nseg, hipStream_t st,
+                                     const float* mix = nullptr) {
   const int esz = sizeof(T);
+  const int dt = esz == 2 ? DT_BF16 : DT_F32;
   const int vec = combine == CMB_WEIGHTED ? (esz == 2 ? 8 : 4)
-                                          : sorted_vec(esz == 2 ? DT_BF16 : DT_F32, s.n);
+                  : mix ? mixed_vec(dt, s.n) : sorted_vec(dt, s.n);
   bool ok = nseg >= 1 && nseg <= kMaxSegs;
   SegTable t{};
   int64_t maxv = 0;
@@ -494,7 +700,7 @@ static hipError_t agg_update_multi_t(int combine, int opt, const SrcArgs& s, con
       if (u1.s2) u1.s2 += o;
       if (u1.gout) u1.gout += o;
       u1.param_out = segs[i].param_out;
-      hipError_t e = agg_update_t<T>(combine, opt, s1, u1, segs[i].D, st);
+      hipError_t e = agg_update_t<T>(combine, opt, s1, u1, segs[i].D, st, mix);
       if (e != hipSuccess) return e;
     }
     return hipGetLastError();
@@ -510,6 +716,13 @@ static hipError_t agg_update_multi_t(int combine, int opt, const SrcArgs& s, con
       case OPT_SGD: agg_weighted_multi<T, V, OPT_SGD><<<g, kBlock, 0, st>>>(s, u, t); break;
       default: agg_weighted_multi<T, V, OPT_ADAM><<<g, kBlock, 0, st>>>(s, u, t); break;
     }
+  } else if (mix) {
+    constexpr bool BF = sizeof(T) == 2;
+    const int np = mixed_np(s.n);
+    if (np == 4) launch_mixed_multi_np<T, 4, BF ? 8 : 4>(opt, s, u, mix, t, g, st);
+    else if (np == 8) launch_mixed_multi_np<T, 8, 4>(opt, s, u, mix, t, g, st);
+    else if (np == 16) launch_mixed_multi_np<T, 16, 4>(opt, s, u, mix, t, g, st);
+    else launch_mixed_multi_np<T, 32, 2>(opt, s, u, mix, t, g, st);
   } else {
     constexpr bool BF = sizeof(T) == 2;
     const int n = s.n;
@@ -525,21 +738,24 @@ static hipError_t agg_update_multi_t(int combine, int opt, const SrcArgs& s, con
 
 hipError_t launch_agg_update_multi(int dtype, int combine, int opt, const SrcArgs& src,
                                    const UpdArgs& upd, const AggSeg* segs, int nseg,
-                                   hipStream_t stream) {
+                                   hipStream_t stream, const float* mix) {
   if (src.n < 1 || src.n > kMaxRows || nseg < 1) return hipErrorInvalidValue;
   if (combine == CMB_SORTED && (src.cnt < 1 || src.lo < 0 || src.lo + src.cnt > src.n))
     return hipErrorInvalidValue;
-  if (dtype == DT_BF16) return agg_update_multi_t<bf16>(combine, opt, src, upd, segs, nseg, stream);
-  return agg_update_multi_t<float>(combine, opt, src, upd, segs, nseg, stream);
+  if (mix && (combine != CMB_SORTED || src.n > kMaxMixRows)) return hipErrorInvalidValue;
+  if (dtype == DT_BF16)
+    return agg_update_multi_t<bf16>(combine, opt, src, upd, segs, nseg, stream, mix);
+  return agg_update_multi_t<float>(combine, opt, src, upd, segs, nseg, stream, mix);
 }
 
 hipError_t launch_agg_update(int dtype, int combine, int opt, const SrcArgs& src,
-                             const UpdArgs& upd, int64_t D, hipStream_t stream) {
+                             const UpdArgs& upd, int64_t D, hipStream_t stream, const float* mix) {
   if (src.n < 1 || src.n > kMaxRows) return hipErrorInvalidValue;
   if (combine == CMB_SORTED && (src.cnt < 1 || src.lo < 0 || src.lo + src.cnt > src.n))
     return hipErrorInvalidValue;
-  if (dtype == DT_BF16) return agg_update_t<bf16>(combine, opt, src, upd, D, stream);
-  return agg_update_t<float>(combine, opt, src, upd, D, stream);
+  if (mix && (combine != CMB_SORTED || src.n > kMaxMixRows)) return hipErrorInvalidValue;
+  if (dtype == DT_BF16) return agg_update_t<bf16>(combine, opt, src, upd, D, stream, mix);
+  return agg_update_t<float>(combine, opt, src, upd, D, stream, mix);
 }
 
 }  // namespace cml

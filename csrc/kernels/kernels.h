@@ -17,6 +17,7 @@ enum Rule : int {
   RULE_GEOMED = 3,
   RULE_CCLIP = 4,
   RULE_BULYAN_SELECT = 5,
+  RULE_NNM_ONLY = 6,   // no weights: only the nearest-neighbour mixing matrix (needs pre = 1)
 };
 
 // Worker rows of a [n, ld] matrix: row i of the aggregation is X + rows[i]*ld (rows == nullptr:
@@ -46,8 +47,12 @@ struct UpdArgs {
 
 // Aggregate n worker vectors of length D and apply the optimizer in the same pass.
 // Returns hipSuccess or the launch error.
+// mix (sorted combine only, n <= 32): device fp32 [n, n], a linear pre-mix of the rows per
+// coordinate ahead of the sort, y_i = sum_j mix[i n + j] x_j in fp32; a zero entry contributes
+// nothing even where x_j is NaN / inf.
 hipError_t launch_agg_update(int dtype, int combine, int opt, const SrcArgs& src,
-                             const UpdArgs& upd, int64_t D, hipStream_t stream);
+                             const UpdArgs& upd, int64_t D, hipStream_t stream,
+                             const float* mix = nullptr);
 // The same over up to 16 segments in ONE launch (the sharded engine's buckets): segment i reads
 // worker rows from X (row stride ld) over D elements, updates the optimizer state at element
 // offset off and writes param_out; src / upd carry the shared rule, weights and state bases
@@ -61,7 +66,7 @@ struct AggSeg {
 };
 hipError_t launch_agg_update_multi(int dtype, int combine, int opt, const SrcArgs& src,
                                    const UpdArgs& upd, const AggSeg* segs, int nseg,
-                                   hipStream_t stream);
+                                   hipStream_t stream, const float* mix = nullptr);
 
 // Gram matrix G = X X^T (fp64, [n, n], row-major) of n <= 64 worker rows. ``work`` must hold
 // gram_workspace_bytes(n, D) bytes. accumulate != 0: G += X X^T (bucket-by-bucket Gram).
@@ -86,7 +91,13 @@ hipError_t launch_robust_weights(int rule, const double* G, int n, int f, int m,
                                  double eps, double tol, double tau, float* w, double* scores,
                                  int* sel, hipStream_t stream, int guard = 0,
                                  int* center_out = nullptr, double* sel_counts = nullptr,
-                                 int* nbad_io = nullptr);
+                                 int* nbad_io = nullptr, int pre = 0, float* mix_out = nullptr);
+// pre = 1: nearest-neighbour mixing before the rule. M (row i = 1 / k on the k = n - f rows
+// nearest to row i, itself included; fp32 [n, n] into mix_out when given) is built from G, the
+// rule runs on the Gram of the mixed rows M G M^T and w leaves as M^T w (weights over the
+// original rows); scores, sel and sel_counts then refer to the mixed rows, while the guard, the
+// non-finite row count and center_out keep reading G. Every rule but RULE_MEAN and
+// RULE_BULYAN_SELECT. RULE_NNM_ONLY writes only mix_out (the identity on a tripped guard).
 // Stage 1 of launch_gram only: per-workgroup [P, P] fp32 partials into work (*nblk of them, P =
 // 16 ceil(n / 16)); launch_gram_reduce_multi then reduces nb buckets' partials into G in ONE
 // launch, bit-identical to one launch_gram per bucket into slots summed by launch_gram_sum.

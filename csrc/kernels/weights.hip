@@ -21,6 +21,13 @@
 // worker rows are non-finite, the step is distrusted: gradient weights 0 (centered clipping
 // keeps its previous aggregate), and the next center is -1 (the next Gram pass runs
 // uncentered, where the overflowing row is the non-finite one).
+//
+// Optional pre-aggregation in the same wave: nearest-neighbour mixing (NNM, Allouah et al. 2023)
+// replaces row x_i by the mean y_i of its n - f nearest rows, y = M x. Everything a Gram-space
+// rule needs of the mixed rows follows from G alone: M from the distances, the Gram of the
+// mixed rows G' = M G M^T (fp64, LDS), and sum_i w_i y_i = sum_j (M^T w)_j x_j -- so the rule
+// runs unchanged on G' and the weights leave as M^T w over the ORIGINAL rows. A row of M is
+// "1 / cnt on a set of columns": one 64-bit mask and one reciprocal per row.
 #include "common.h"
 #include "kernels.h"
 
@@ -28,6 +35,7 @@ namespace cml {
 namespace {
 
 constexpr int kMax = 65;   // n <= 64 workers (+1 row for centered clipping)
+constexpr int kMixMax = 64;   // Gram rows with mixing (centered clipping: n + 1 <= 64 as it is)
 
 __device__ __forceinline__ double wmax(double v) {
 #pragma unroll
@@ -58,6 +66,32 @@ __device__ double krum_score(const double* G, int n, int i, int k, const unsigne
     if (rank < k) s += dj;
   }
   return s;
+}
+
+// NNM neighbour set of row i (bit j = row j is averaged into y_i) over the n worker rows of the
+// nrows x nrows Gram: the `take` good rows nearest to i by (d_ij, j) order with i itself first; a
+// bad row keeps only itself (ops/reference.py nnm_matrix).
+__device__ unsigned long long nnm_mask(const double* G, int n, int nrows, int i, int take,
+                                       const bool* bad) {
+  if (bad[i]) return 1ull << i;
+  const double gii = G[i * nrows + i];
+  unsigned long long mask = 0;
+  for (int j = 0; j < n; ++j) {
+    if (bad[j]) continue;
+    double dj = fmax(gii + G[j * nrows + j] - 2.0 * G[i * nrows + j], 0.0);
+    if (dj != dj) dj = __builtin_inf();
+    if (j == i) dj = -1.0;
+    int rank = 0;
+    for (int l = 0; l < n; ++l) {
+      if (l == j || bad[l]) continue;
+      double dl = fmax(gii + G[l * nrows + l] - 2.0 * G[i * nrows + l], 0.0);
+      if (dl != dl) dl = __builtin_inf();
+      if (l == i) dl = -1.0;
+      rank += (dl < dj) || (dl == dj && l < j);
+    }
+    if (rank < take) mask |= 1ull << j;
+  }
+  return mask;
 }
 
 __device__ __forceinline__ void weights_rule(int rule, const double* __restrict__ G, int n, int f,
@@ -212,10 +246,16 @@ __global__ __launch_bounds__(64) void robust_weights_kernel(int rule, const doub
                                                            int* __restrict__ sel, int guard,
                                                            int* __restrict__ center_out,
                                                            double* __restrict__ sel_counts,
-                                                           int* __restrict__ nbad_io) {
+                                                           int* __restrict__ nbad_io, int pre,
+                                                           float* __restrict__ mix_out) {
   __shared__ bool bad[kMax];
   __shared__ double sc[kMax];
   __shared__ double a[kMax];
+  // NNM: row masks / reciprocal counts of M, T = G M^T and G' = M T (nrows <= 64 with mixing)
+  __shared__ unsigned long long mmask[kMixMax];
+  __shared__ double minv[kMixMax];
+  __shared__ double Tm[kMixMax * kMixMax];
+  __shared__ double Gm[kMixMax * kMixMax];
   const int i = threadIdx.x;
   const int nrows = rule == RULE_CCLIP ? n + 1 : n;   // Gram dimension
   // center_out holds the center THIS pass used (the engine passes one buffer): a pass that ran
@@ -233,17 +273,78 @@ __global__ __launch_bounds__(64) void robust_weights_kernel(int rule, const doub
     bad[r] = !(d == d) || d == __builtin_inf() || d == -__builtin_inf();
   }
   __syncthreads();
-  weights_rule(rule, G, n, f, m, iters, eps, tol, tau, w, scores, sel, bad, sc, a);
+  bool picked = false;   // NNM: the rule gave this (mixed) row a positive weight
+  if (pre) {
+    int good = 0;
+    for (int r = 0; r < n; ++r) good += !bad[r];
+    int take = n - f < 1 ? 1 : n - f;
+    if (take > good) take = good;
+    if (i < nrows) {
+      // (centered clipping's row n, the previous aggregate, is not a worker: identity)
+      const unsigned long long mk = i < n ? nnm_mask(G, n, nrows, i, take, bad) : 1ull << i;
+      mmask[i] = mk;
+      minv[i] = 1.0 / __popcll(mk);
+    }
+    __syncthreads();
+    if (mix_out && i < n) {
+      const float v = static_cast<float>(minv[i]);
+      for (int j = 0; j < n; ++j) mix_out[i * n + j] = ((mmask[i] >> j) & 1ull) ? v : 0.0f;
+    }
+  }
+  if (pre && rule != RULE_NNM_ONLY) {
+    if (i < nrows) {   // row i of T = G M^T: T_ij = mean of G_ib over the neighbours b of j
+      for (int j = 0; j < nrows; ++j) {
+        const unsigned long long mk = mmask[j];
+        double s = 0.0;
+        for (int b = 0; b < nrows; ++b)
+          if ((mk >> b) & 1ull) s += G[i * nrows + b];
+        Tm[i * nrows + j] = s * minv[j];
+      }
+    }
+    __syncthreads();
+    if (i < nrows) {   // row i of G' = M T
+      const unsigned long long mk = mmask[i];
+      for (int j = 0; j < nrows; ++j) {
+        double s = 0.0;
+        for (int r = 0; r < nrows; ++r)
+          if ((mk >> r) & 1ull) s += Tm[r * nrows + j];
+        Gm[i * nrows + j] = s * minv[i];
+      }
+    }
+    __syncthreads();
+    weights_rule(rule, Gm, n, f, m, iters, eps, tol, tau, w, scores, sel, bad, sc, a);
+    __syncthreads();
+    // w <- M^T w: weights over the original rows (zero weights skipped)
+    const double wi = i < nrows ? static_cast<double>(w[i]) : 0.0;
+    picked = i < n && wi > 0.0;
+    if (i < nrows) a[i] = wi;
+    __syncthreads();
+    if (i < nrows) {
+      double s = 0.0;
+      for (int r = 0; r < nrows; ++r)
+        if (a[r] != 0.0 && ((mmask[r] >> i) & 1ull)) s += a[r] * minv[r];
+      w[i] = static_cast<float>(s);
+    }
+  } else if (rule != RULE_NNM_ONLY) {
+    weights_rule(rule, G, n, f, m, iters, eps, tol, tau, w, scores, sel, bad, sc, a);
+  }
   __syncthreads();
   int nbad = 0;
   for (int r = 0; r < n; ++r) nbad += bad[r];
   const bool trip = guard && 2 * nbad >= n && nbad > 0 && (!nbad_io || nbad > nbad_prev);
   if (nbad_io && i == 0) nbad_io[0] = nbad;
-  if (trip) {
-    if (i < nrows) w[i] = (rule == RULE_CCLIP && i == n) ? 1.0f : 0.0f;
-    if (sel && rule != RULE_BULYAN_SELECT && i < n) sel[i] = 0;
+  if (rule == RULE_NNM_ONLY) {
+    // the coordinate rules' mixing matrix only: a distrusted G mixes nothing this step
+    if (trip && i < n)
+      for (int j = 0; j < n; ++j) mix_out[i * n + j] = i == j ? 1.0f : 0.0f;
+  } else {
+    if (trip) {
+      if (i < nrows) w[i] = (rule == RULE_CCLIP && i == n) ? 1.0f : 0.0f;
+      if (sel && rule != RULE_BULYAN_SELECT && i < n) sel[i] = 0;
+    }
+    if (sel_counts && i < n)
+      sel_counts[i] += (pre ? (picked && !trip) : w[i] > 0.0f) ? 1.0 : 0.0;
   }
-  if (sel_counts && i < n) sel_counts[i] += w[i] > 0.0f ? 1.0 : 0.0;
   if (center_out) {
     // medoid of the finite worker rows of G (gram_center_kernel's rule)
     double s_i = __builtin_inf();
@@ -279,12 +380,16 @@ __global__ __launch_bounds__(64) void robust_weights_kernel(int rule, const doub
 hipError_t launch_robust_weights(int rule, const double* G, int n, int f, int m, int iters,
                                  double eps, double tol, double tau, float* w, double* scores,
                                  int* sel, hipStream_t stream, int guard, int* center_out,
-                                 double* sel_counts, int* nbad_io) {
+                                 double* sel_counts, int* nbad_io, int pre, float* mix_out) {
   if (n < 1 || n > 64) return hipErrorInvalidValue;
+  if (rule < RULE_MEAN || rule > RULE_NNM_ONLY || pre < 0 || pre > 1) return hipErrorInvalidValue;
+  if (pre && (rule == RULE_MEAN || rule == RULE_BULYAN_SELECT)) return hipErrorInvalidValue;
+  if (rule == RULE_NNM_ONLY && (!pre || mix_out == nullptr)) return hipErrorInvalidValue;
   if (rule == RULE_CCLIP && n > 63) return hipErrorInvalidValue;   // n + 1 rows, one per lane
   if (rule == RULE_BULYAN_SELECT && sel == nullptr) return hipErrorInvalidValue;
   robust_weights_kernel<<<1, 64, 0, stream>>>(rule, G, n, f, m, iters, eps, tol, tau, w, scores, sel,
-                                              guard, center_out, sel_counts, nbad_io);
+                                              guard, center_out, sel_counts, nbad_io, pre,
+                                              mix_out);
   return hipGetLastError();
 }
 
