@@ -12,6 +12,9 @@ For n workers x D coordinates (bf16), times (HIP events, median of reps):
                  trimmed_mixed_sgd: the same fused updates with the nearest-neighbour pre-mix
                  y = M x per coordinate ahead of the sort (agg.pre=nnm), and their ratio to the
                  plain sorted kernels from the same process
+  --worker-momentum  times only worker_momentum (m <- beta m + g in place over [n, D], the rows
+                 replaced by bf16(m); optim.worker_momentum) and reports bytes / time with the
+                 12 B per element the kernel must move (2 + 4 read, 2 + 4 written)
 and the PyTorch equivalents (torch.median / sort / matmul / foreach) for comparison. Reports
 achieved HBM GB/s from the bytes each kernel must move. One JSON line per (n, D).
 """
@@ -53,6 +56,9 @@ def main():
     ap.add_argument("--no-torch", action="store_true")
     ap.add_argument("--mixed", action="store_true",
                     help="also time the mixed sorted kernel (agg.pre=nnm) next to the plain one")
+    ap.add_argument("--worker-momentum", action="store_true",
+                    help="time only the worker-momentum kernel (optim.worker_momentum) over "
+                         "[n, D]; use --n 1 8")
     ap.add_argument("--json-out", default=None)
     a = ap.parse_args()
     from consensusml_amd.ops import kernels as K
@@ -61,6 +67,25 @@ def main():
         for n in a.n:
             g = torch.Generator(device=dev).manual_seed(0)
             X = torch.randn(n, D, generator=g, device=dev).to(torch.bfloat16)
+            if a.worker_momentum:
+                # in place over [n, D]: bf16 row read + written, fp32 state read + written
+                state = torch.zeros(n, D, device=dev)
+                ms = timeit(lambda: K.worker_momentum(X, state, 0.9), a.reps)
+                res = {"n": n, "D": D, "dtype": "bf16", "worker_momentum_ms": round(ms, 4),
+                       "worker_momentum_bytes": 12 * n * D,
+                       "worker_momentum_GBps": round(12 * n * D / (ms * 1e-3) / 1e9, 1)}
+                if not a.no_torch:   # the reference op: three elementwise passes, 20 B / element
+                    def torch_wm():
+                        state.mul_(0.9).add_(X)
+                        X.copy_(state)
+                    res["torch_worker_momentum_ms"] = round(timeit(torch_wm, max(3, a.reps // 4)), 4)
+                line = json.dumps(res)
+                print(line, flush=True)
+                if a.json_out:
+                    with open(a.json_out, "a") as fh:
+                        fh.write(line + "\n")
+                del X, state
+                continue
             master = torch.randn(D, device=dev)
             mom = torch.zeros(D, device=dev)
             p = torch.empty(D, dtype=torch.bfloat16, device=dev)

@@ -24,9 +24,13 @@ diverged (non-finite), and for Krum / Multi-Krum how often a Byzantine worker wa
   python bench/robustness.py --task mlp --steps 200 --jsonl out.jsonl --md out.md
   python bench/robustness.py --task resnet_tiny --rules krum,median --attacks alie
   python bench/robustness.py --task mlp --pre nnm      # nearest-neighbour mixing before each rule
+  python bench/robustness.py --task mlp --worker-momentum   # the rules aggregate worker momenta
 
 ``--pre nnm`` (agg.pre) skips mean and bulyan, which have no mixed form, and leaves out the
 Byzantine selection fraction: the selections then index mixed rows, not workers.
+``--worker-momentum`` (optim.worker_momentum) moves the SGD momentum to the workers, ahead of the
+attack and the rule; it combines with ``--pre nnm``. Centered clipping's ``--tau`` then applies
+to rows about 1 / (1 - momentum) = 10x larger and is not rescaled.
 """
 from __future__ import annotations
 
@@ -71,7 +75,7 @@ def rule_f(rule: str, n: int, f: int) -> int:
 
 def make_config(task: str, rule: str, attack: str, n: int = 8, f: int = 2,
                 steps: Optional[int] = None, dtype: str = "bf16", tau: float = 1.0,
-                seed: int = 2019, pre: str = "none"):
+                seed: int = 2019, pre: str = "none", worker_momentum: bool = False):
     from consensusml_amd import TrainConfig
     t = TASKS[task]
     cfg = TrainConfig()
@@ -97,6 +101,7 @@ def make_config(task: str, rule: str, attack: str, n: int = 8, f: int = 2,
     cfg.optim.name = "sgd"
     cfg.optim.lr = t["lr"]
     cfg.optim.momentum = 0.9
+    cfg.optim.worker_momentum = worker_momentum
     cfg.fault.kind = attack
     cfg.fault.ranks = list(range(f)) if attack != "none" else []
     if attack == "sign_flip":
@@ -122,14 +127,14 @@ def fault_desc(cfg) -> str:
 def run_one(task: str, rule: str, attack: str, n: int = 8, f: int = 2,
             steps: Optional[int] = None, device: Optional[torch.device] = None,
             dtype: Optional[str] = None, tau: float = 1.0, seed: int = 2019,
-            pre: str = "none") -> Dict[str, object]:
+            pre: str = "none", worker_momentum: bool = False) -> Dict[str, object]:
     from consensusml_amd.parallel.dist import DistInfo
     from consensusml_amd.trainer.trainer import ConsensusTrainer
     if device is None:
         device = torch.device("cuda:0" if torch.cuda.is_available() else "cpu")
     if dtype is None:
         dtype = "bf16" if device.type == "cuda" else "fp32"
-    cfg = make_config(task, rule, attack, n, f, steps, dtype, tau, seed, pre)
+    cfg = make_config(task, rule, attack, n, f, steps, dtype, tau, seed, pre, worker_momentum)
     tr = ConsensusTrainer(cfg, info=DistInfo(0, 1, 0, device, "none"))
     t0 = time.perf_counter()
     res = tr.fit(cfg.steps, log_every=0)
@@ -148,6 +153,8 @@ def run_one(task: str, rule: str, attack: str, n: int = 8, f: int = 2,
            "eval_accuracy": ev["accuracy"], "diverged": not finite, "wall_s": round(wall, 2)}
     if pre != "none":
         out["pre"] = pre
+    if worker_momentum:
+        out["worker_momentum"] = True
     if rule in ("krum", "multi_krum") and pre == "none":
         tot = sum(sel)
         out["byzantine_selected_frac"] = (sum(sel[b] for b in byz) / tot) if tot else 0.0
@@ -167,6 +174,8 @@ def markdown(rows: List[Dict[str, object]]) -> str:
         params = {r["attack"]: r["attack_params"] for r in rs}
         r0 = rs[0]
         pre = f", agg.pre={r0['pre']}" if r0.get("pre") else ""
+        if r0.get("worker_momentum"):
+            pre += ", optim.worker_momentum"
         lines.append(f"### {task}: n = {r0['n']} workers, {r0.get('f', 2)} Byzantine, "
                      f"{r0['steps']} steps, {r0['dtype']} on {r0['device']}{pre}")
         lines.append("")
@@ -211,6 +220,8 @@ def main():
     ap.add_argument("--md", default=None)
     ap.add_argument("--pre", choices=("none", "nnm"), default="none",
                     help="pre-aggregation (agg.pre); nnm skips mean and bulyan")
+    ap.add_argument("--worker-momentum", action="store_true",
+                    help="optim.worker_momentum: the rules aggregate per-worker momenta")
     a = ap.parse_args()
     dev = torch.device(a.device) if a.device else None
     rows = []
@@ -219,7 +230,7 @@ def main():
             continue
         for attack in a.attacks.split(","):
             r = run_one(a.task, rule, attack, a.n, a.f, a.steps or None, dev, a.dtype, a.tau,
-                        pre=a.pre)
+                        pre=a.pre, worker_momentum=a.worker_momentum)
             rows.append(r)
             line = json.dumps(r)
             print(line, flush=True)

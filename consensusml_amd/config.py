@@ -32,7 +32,9 @@ class AggConfig:
     trim          number trimmed from each side per coordinate (trimmed mean); ``None`` -> f
     m             number of workers averaged by Multi-Krum; ``None`` -> n - f
     iters, eps    Weiszfeld iterations and distance floor (geometric median)
-    tau, clip_iters  radius / iterations of centered clipping
+    tau, clip_iters  radius / iterations of centered clipping. With ``optim.worker_momentum`` the
+                  clipped rows are momenta, about 1 / (1 - momentum) larger than gradients; tau
+                  is taken as given, never rescaled
     centered_gram Gram-space rules: the Gram of the rows relative to a medoid worker row, so
                   near-duplicate workers' distances do not cancel (ops.kernels.gram). ONE pass
                   per step, centered at the medoid picked from the previous step's Gram; the
@@ -90,6 +92,22 @@ class AggConfig:
 
 @dataclass
 class OptimConfig:
+    """Optimizer of the fused aggregate-and-update step.
+
+    worker_momentum  SGD only (Karimireddy, He, Jaggi 2021, "Learning from History"): the
+                     momentum ``momentum`` is applied per worker BEFORE the exchange instead of
+                     to the aggregate. Every local worker keeps an fp32 buffer m_i <- momentum *
+                     m_i + g_i (no dampening, torch.optim.SGD's buffer) and sends m_i rounded to
+                     the comm dtype in place of its gradient; the server applies plain SGD to
+                     rule(m_1..m_n), so there is one momentum, never two. With the mean rule the
+                     trajectory is that of server momentum; every non-linear rule sees rows whose
+                     variance is reduced over the momentum window. Order within a step: capture
+                     -> momentum -> fault injection -> exchange, so a Byzantine worker's state
+                     advances from its own honest gradient and ALIE / IPM statistics are taken
+                     over the honest workers' momenta. allgather / sharded topologies. Weight
+                     decay stays on the server, outside the momentum. The rows are about
+                     1 / (1 - momentum) larger than gradients: ``agg.tau`` is not rescaled
+    """
     name: str = "sgd"            # sgd | adam | adamw
     lr: float = 0.1
     momentum: float = 0.9
@@ -97,6 +115,18 @@ class OptimConfig:
     weight_decay: float = 0.0
     betas: tuple = (0.9, 0.999)
     eps: float = 1e-8
+    worker_momentum: bool = False
+
+    def validate(self) -> None:
+        if not self.worker_momentum:
+            return
+        if self.name != "sgd":
+            raise ValueError(f"optim.worker_momentum needs optim.name=sgd (got {self.name!r})")
+        if self.momentum == 0:
+            raise ValueError("optim.worker_momentum needs optim.momentum != 0: it moves that "
+                             "momentum to the workers")
+        if self.nesterov:
+            raise ValueError("optim.worker_momentum is not implemented with optim.nesterov")
 
 
 @dataclass
@@ -210,6 +240,10 @@ class TrainConfig:
         if self.agg.pre != "none" and self.topology.kind in ("gossip", "allreduce"):
             raise ValueError(f"agg.pre={self.agg.pre} needs the allgather or sharded topology "
                              f"(got {self.topology.kind!r}: no worker rows to mix)")
+        self.optim.validate()
+        if self.optim.worker_momentum and self.topology.kind in ("gossip", "allreduce"):
+            raise ValueError("optim.worker_momentum needs the allgather or sharded topology "
+                             f"(got {self.topology.kind!r}: no worker rows to aggregate)")
         self.fault.validate()
         return self
 

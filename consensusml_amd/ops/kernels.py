@@ -465,3 +465,20 @@ def inject_fault(g: torch.Tensor, kind: str, scale: float = 10.0, sigma: float =
         g.fill_(float("nan"))
     else:
         raise ValueError(f"fault {kind!r} needs cross-worker statistics (see parallel.faults)")
+
+
+WORKER_MOMENTUM_PASS = 256 * 4 * 8   # elements of a row one workgroup covers per pass
+                                     # (kMB * kMU * 8, worker_momentum.hip)
+
+
+def worker_momentum(rows: torch.Tensor, mom: torch.Tensor, beta: float) -> None:
+    """Worker-side momentum over an [R, L] window, in place: ``mom`` (fp32) <- beta * mom + rows,
+    ``rows`` (bf16 / fp32) <- mom rounded to the rows' dtype. Unit column stride, any row stride
+    (a bucket's column range of the flat gradient buffer and of the momentum state)."""
+    if rows.is_cuda:
+        lib().worker_momentum(rows, mom, float(beta))
+        return
+    if rows.shape != mom.shape or mom.dtype != torch.float32:
+        raise ValueError(f"worker_momentum: rows {tuple(rows.shape)} {rows.dtype} against mom "
+                         f"{tuple(mom.shape)} {mom.dtype}")
+    ref.worker_momentum(rows, mom, beta)

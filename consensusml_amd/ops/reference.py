@@ -390,5 +390,15 @@ def is_pow2(n: int) -> bool:
     return n > 0 and (n & (n - 1)) == 0
 
 
+# --------------------------------------------------------------------------- worker momentum
+
+
+def worker_momentum(rows: torch.Tensor, mom: torch.Tensor, beta: float) -> None:
+    """Worker-side momentum in place: mom <- beta * mom + rows (fp32), rows <- mom rounded to the
+    rows' dtype (``optim.worker_momentum``; the definition of csrc/kernels/worker_momentum.hip)."""
+    mom.mul_(beta).add_(rows.float())
+    rows.copy_(mom.to(rows.dtype))
+
+
 __all__ = [n for n in dir() if not n.startswith("_") and n not in ("math", "torch", "Optional",
                                                                      "Tuple", "annotations")]

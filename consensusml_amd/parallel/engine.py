@@ -45,7 +45,7 @@ from ..ops.conv import set_pending_query
 from ..perf import policy as _P
 from ..ops.native import lib
 from .dist import DistInfo
-from .faults import COLLUSION, apply_faults
+from .faults import COLLUSION, apply_faults, byzantine_rows
 from .flat import Bucket, FlatModel
 
 
@@ -130,7 +130,29 @@ class ConsensusEngine:
             self.master = fl.flat_param.float().clone()
         self.state_len = self.master.numel()
         oname = cfg.optim.name
-        self.s1 = torch.zeros_like(self.master) if (oname != "sgd" or cfg.optim.momentum) else None
+        # optim.worker_momentum: the momentum lives in one fp32 row per LOCAL worker ([V, D],
+        # flat-buffer order) and is applied to the gradient rows before fault injection and the
+        # exchange (ops.kernels.worker_momentum); the fused update then runs with momentum 0 and
+        # has no s1
+        self.worker_momentum = bool(cfg.optim.worker_momentum)
+        self.wm = (torch.zeros(self.V, fl.total, dtype=torch.float32, device=dev)
+                   if self.worker_momentum else None)
+        self.wm_restored = False    # the last load_state_dict() restored self.wm (else zeroed)
+        # The capture writes parameter elements only; the alignment padding between them keeps
+        # whatever was last sent, which for a Byzantine row is the attack's value (NaN, noise).
+        # The momentum must not fold that back into the worker's state, so those rows' padding
+        # is cleared first: padding columns per bucket (simulation only, Byzantine rows only).
+        self._pad_cols: Dict[int, torch.Tensor] = {}
+        if self.worker_momentum and cfg.fault.kind != "none":
+            pad = torch.ones(fl.total, dtype=torch.bool)
+            for i, p in enumerate(fl.params):
+                pad[fl.param_offset[i]:fl.param_offset[i] + p.numel()] = False
+            for b in fl.buckets:
+                idx = pad[b.offset:b.offset + b.length].nonzero().view(-1) + b.offset
+                if idx.numel():
+                    self._pad_cols[b.index] = idx.to(dev)
+        self.s1 = (torch.zeros_like(self.master)
+                   if (oname != "sgd" or cfg.optim.momentum) and not self.worker_momentum else None)
         self.s2 = torch.zeros_like(self.master) if oname in ("adam", "adamw") else None
         self.step_count = 0
 
@@ -283,7 +305,9 @@ class ConsensusEngine:
 
     def abort_step(self) -> None:
         """Undo zero_grad()'s per-step state after a failed forward / backward: deactivate the
-        direct-gradient destination (module-global) and drop the half-filled bucket state."""
+        direct-gradient destination (module-global) and drop the half-filled bucket state. With
+        ``optim.worker_momentum`` and overlap, the buckets that were flushed before the failure
+        have already advanced their part of the momentum state; that is not undone."""
         self._end_direct()
         for v in self._ready.values():
             v.clear()
@@ -411,6 +435,11 @@ class ConsensusEngine:
             if self._invoked:
                 self._learned = True
         self._flush_row()
+        if self.wm is not None and not self.overlap:
+            # every local row is complete (sequential workers, worker_batch(), direct gradients):
+            # one launch over [V, D], ahead of the fault injection. With overlap each bucket was
+            # done in its flush.
+            self._worker_momentum(None)
         if self.early_update:
             for b in fl.buckets:       # buckets whose gradients were never all produced
                 if b.index not in self._updated:
@@ -496,6 +525,8 @@ class ConsensusEngine:
         lst.clear()
         self._flushed.add(b.index)
         if self.overlap and b.index not in self._pending:
+            if self.wm is not None:    # this bucket's columns, before its faults and collective
+                self._worker_momentum(b)
             self._launch_bucket(b, inject=True)
             if self.early_gram:
                 if self._gram_ordered:
@@ -507,6 +538,23 @@ class ConsensusEngine:
                     self._poll_grams()
         if self.early_update and complete:
             self._early_update(b)
+
+    def _worker_momentum(self, b: Optional[Bucket]) -> None:
+        """optim.worker_momentum: m_i <- beta m_i + g_i for every local worker, the gradient rows
+        replaced by the momenta in the comm dtype; over bucket b's columns, or everything."""
+        fl = self.flat
+        bad = byzantine_rows(self.cfg.fault, self.rank, self.V, self.step_count)
+        if bad and self._pad_cols:
+            for bk in ([b] if b is not None else fl.buckets):
+                idx = self._pad_cols.get(bk.index)
+                if idx is not None:
+                    for r in bad:
+                        fl.flat_grad[r].index_fill_(0, idx, 0)
+        if b is None:
+            K.worker_momentum(fl.flat_grad, self.wm, self.cfg.optim.momentum)
+        else:
+            cols = slice(b.offset, b.offset + b.length)
+            K.worker_momentum(fl.flat_grad[:, cols], self.wm[:, cols], self.cfg.optim.momentum)
 
     def _early_update(self, b: Bucket) -> None:
         """Gossip, V == 1: this bucket's local optimizer step on the side stream."""
@@ -626,7 +674,8 @@ class ConsensusEngine:
         kind = o.name if o.name in ("sgd", "adam", "adamw") else "adamw"
         wd = o.weight_decay
         # 'adam' = torch.optim.Adam (L2 term in the gradient), 'adamw' = decoupled decay
-        return K.OptArgs(kind=kind, lr=o.lr, momentum=o.momentum if kind == "sgd" else 0.0,
+        mom = o.momentum if kind == "sgd" and not self.worker_momentum else 0.0
+        return K.OptArgs(kind=kind, lr=o.lr, momentum=mom,
                          weight_decay=wd, nesterov=o.nesterov, first=self.step_count == 0,
                          beta1=o.betas[0], beta2=o.betas[1], eps=o.eps,
                          step=self.step_count + 1, gscale=gscale)
@@ -1016,7 +1065,9 @@ class ConsensusEngine:
 
     def _record_stats(self, cols) -> None:
         """Per (parameter tensor, worker): squared gradient norm and squared distance to the
-        aggregate, from the worker rows this rank holds; shard partial sums are all-reduced."""
+        aggregate, from the worker rows this rank holds; shard partial sums are all-reduced. With
+        ``optim.worker_momentum`` the rows are the workers' momenta (what was exchanged), not
+        their gradients."""
         segs = self.flat.segments()
         n = self.n
         dev = self.device
@@ -1051,7 +1102,10 @@ class ConsensusEngine:
         per parameter tensor, one column per worker for its gradient norm and its distance to the
         robust aggregate, plus aggregate columns (aggregate norm, median worker norm, the worker
         farthest from the aggregate). Two trailing rows carry the per-worker Krum score and
-        selection count / weight. Needs a step taken with ``record_stats = True``."""
+        selection count / weight. Needs a step taken with ``record_stats = True``. With
+        ``optim.worker_momentum`` the exchanged rows are momenta, so the ``grad_norm`` and
+        ``dist_to_agg`` columns describe each worker's momentum (about 1 / (1 - momentum) the
+        gradient scale)."""
         import pandas as pd
         st = self.last_stats
         if st is None:
@@ -1103,9 +1157,18 @@ class ConsensusEngine:
             sd["s1"] = self.s1
         if self.s2 is not None:
             sd["s2"] = self.s2
+        if self.wm is not None:
+            sd["worker_momentum"] = self.wm     # [V, D] fp32: this rank's workers, full rows
+            sd["worker_momentum_layout"] = self._wm_layout()
         if self.rule == "centered_clip":
             sd["v0"] = self.gout
         return sd
+
+    def _wm_layout(self) -> torch.Tensor:
+        """Flat offset and size of every parameter: the columns of a worker-momentum row."""
+        fl = self.flat
+        return torch.tensor([[fl.param_offset[i], p.numel()] for i, p in enumerate(fl.params)],
+                            dtype=torch.int64)
 
     def load_state_dict(self, sd: dict) -> None:
         if sd["world"] != self.N or sd["topology"] != self.topo:
@@ -1115,6 +1178,19 @@ class ConsensusEngine:
             self.s1.copy_(sd["s1"])
         if self.s2 is not None and "s2" in sd:
             self.s2.copy_(sd["s2"])
+        if self.wm is not None:
+            # per-worker state: only meaningful for the same workers (a re-sharded load and a
+            # checkpoint written with server momentum carry none: start from zero)
+            # ... and for the same flat layout: another bucket_mb moves the parameters to other
+            # columns of a row of the same length
+            saved, lay = sd.get("worker_momentum"), sd.get("worker_momentum_layout")
+            self.wm_restored = (saved is not None and lay is not None
+                                and tuple(saved.shape) == tuple(self.wm.shape)
+                                and torch.equal(lay.cpu(), self._wm_layout()))
+            if self.wm_restored:
+                self.wm.copy_(saved)
+            else:
+                self.wm.zero_()
         self.step_count = int(sd["step"])
         self.sel_counts.copy_(sd["sel_counts"])
         if "gram_center" in sd:

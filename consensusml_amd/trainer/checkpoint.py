@@ -22,6 +22,9 @@ fp32 state (master, momentum / Adam moments, centered-clipping v0) from the N fi
 current rank's shard (sharded topology) or the full vector (replicated topologies) out of it in
 the CURRENT layout (bucket padding depends on the world size, so layouts differ between worlds).
 Gossip replicas are per-rank by design: rank r takes the state of saved rank r mod N.
+The worker-momentum state (``optim.worker_momentum``, one fp32 row per local worker) belongs to
+the workers that wrote it: a load at the same world size and topology restores it, a re-sharded
+load starts it from zero and reports ``worker_momentum_reset``.
 """
 from __future__ import annotations
 
@@ -212,4 +215,8 @@ def load_checkpoint(path: str, engine, gens: Optional[list] = None) -> dict:
     if same and gens and st.get("gens"):
         for g, s in zip(gens, st["gens"]):
             g.set_state(s)
-    return {"meta": meta, "extra": st.get("extra", {}), "resharded": not same}
+    # optim.worker_momentum: the per-worker state ([V, D] per rank, not a sharded flat vector, so
+    # not in STATE_KEYS) is restored only for the same workers; otherwise it restarts from zero
+    reset = getattr(engine, "wm", None) is not None and not engine.wm_restored
+    return {"meta": meta, "extra": st.get("extra", {}), "resharded": not same,
+            "worker_momentum_reset": reset}

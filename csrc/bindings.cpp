@@ -1846,6 +1846,34 @@ void fault(Tensor& g, int64_t kind, double scale, double sigma, int64_t seed) {
                                   static_cast<uint64_t>(seed), cur_stream()));
 }
 
+// rows [R, L] bf16 / fp32 and mom [R, L] fp32, unit column stride, any row stride >= L (a column
+// window of the flat gradient buffer and of the per-worker momentum state): mom <- beta mom +
+// rows, rows <- mom in the rows' dtype
+void worker_momentum(Tensor& rows, Tensor& mom, double beta, int64_t grid_cap) {
+  check_dev(rows, "rows");
+  check_dev(mom, "mom");
+  TORCH_CHECK(rows.device() == mom.device(), "worker_momentum: rows and mom are on different devices");
+  TORCH_CHECK(mom.scalar_type() == at::kFloat, "worker_momentum: mom must be fp32, got ",
+              mom.scalar_type());
+  const int dt = dtype_of(rows);
+  TORCH_CHECK(rows.dim() == 2 && mom.dim() == 2, "worker_momentum: rows and mom must be 2-D [R, L]");
+  TORCH_CHECK(rows.sizes() == mom.sizes(), "worker_momentum: rows ", rows.sizes(), " and mom ",
+              mom.sizes(), " differ in shape");
+  const int64_t R = rows.size(0), L = rows.size(1);
+  TORCH_CHECK(R <= 65535, "worker_momentum: at most 65535 rows");
+  TORCH_CHECK(grid_cap >= 0 && grid_cap <= (1 << 20), "worker_momentum: grid_cap out of range");
+  if (R == 0 || L == 0) return;
+  TORCH_CHECK((L == 1 || (rows.stride(1) == 1 && mom.stride(1) == 1)),
+              "worker_momentum: rows and mom need unit column stride");
+  TORCH_CHECK(R == 1 || (rows.stride(0) >= L && mom.stride(0) >= L),
+              "worker_momentum: row strides must be at least the row length");
+  const c10::DeviceGuard guard(rows.device());
+  CML_CHECK_HIP(cml::launch_worker_momentum(dt, rows.data_ptr(), rows.stride(0),
+                                            mom.data_ptr<float>(), mom.stride(0),
+                                            static_cast<int>(R), L, static_cast<float>(beta),
+                                            static_cast<int>(grid_cap), cur_stream()));
+}
+
 // ---------------------------------------------------------------- transformer ops
 void check_bf16c(const Tensor& t, const char* name) {
   check_dev(t, name);
@@ -2668,6 +2696,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("set_conv1x1g_mode", &cml::set_conv1x1g_mode, "select the fused 1x1 kernel family");
   m.def("set_conv1x1g_ablate", &cml::set_conv1x1g_ablate, "diagnostics: quad kernel ablation bits");
   m.def("fault", &fault, "Byzantine fault injection");
+  m.def("worker_momentum", &worker_momentum,
+        "worker-side momentum: mom <- beta mom + rows, rows <- mom, in place over an [R, L] window",
+        py::arg("rows"), py::arg("mom"), py::arg("beta"), py::arg("grid_cap") = 0);
   m.def("bn_fwd", &bn_fwd, "fused NHWC BatchNorm(+res)(+ReLU) forward");
   m.def("bn_bwd", &bn_bwd, "fused NHWC BatchNorm(+res)(+ReLU) backward");
   m.def("bn_fwd2", &bn_fwd2, "relu(BN(x1) + BN(x2)) forward (downsample-block tail)");

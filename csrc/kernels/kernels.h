@@ -239,6 +239,14 @@ hipError_t launch_pad_c4(const void* x, void* y, int64_t npix, int C, hipStream_
 hipError_t launch_fault(int dtype, void* g, int64_t D, int kind, float scale, float sigma,
                         uint64_t seed, hipStream_t stream);
 
+// Worker-side momentum (worker_momentum.hip), in place over an [R, L] window with unit column
+// stride: mom <- beta mom + rows (fp32, one fma), rows <- mom rounded to the rows' dtype (bf16 RNE
+// or fp32). Row strides ldr, ldm >= L in elements; 16-B aligned bases and row strides take 16-B
+// vector accesses, anything else the scalar variant. grid_cap: most workgroups of the launch over
+// all rows (they stride over their row when it needs more); <= 0 = the default, 8192.
+hipError_t launch_worker_momentum(int dtype, void* rows, int64_t ldr, float* mom, int64_t ldm,
+                                  int R, int64_t L, float beta, int grid_cap, hipStream_t stream);
+
 // ---- transformer ops (transformer.hip); bf16 activations, fp32 statistics.
 // Cross-entropy over contiguous bf16 logits [R, V] (16-B aligned base): forward writes the
 // per-row logsumexp and loss (0 for ignored rows); backward writes
