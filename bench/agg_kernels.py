@@ -6,12 +6,14 @@ For n workers x D coordinates (bf16), times (HIP events, median of reps):
   weights        Krum / Weiszfeld weights on G (one wave)
   median_sgd     coordinate median fused with SGD-momentum (master, momentum, bf16 params)
   trimmed_sgd    trimmed mean (trim f) fused with SGD-momentum
+  meamed_sgd / phocas_sgd  the n - f values nearest to the median / to the trimmed mean per
+                 coordinate (f at least 1), fused with SGD-momentum, and their ratio to median_sgd
   krum_sgd       weighted combine (one-hot Krum weights: 1 row read) fused with SGD-momentum
   mean_sgd       weighted combine of all n rows fused with SGD-momentum
   --mixed adds   nnm_matrix (the mixing matrix from G, one wave) and median_mixed_sgd /
                  trimmed_mixed_sgd: the same fused updates with the nearest-neighbour pre-mix
                  y = M x per coordinate ahead of the sort (agg.pre=nnm), and their ratio to the
-                 plain sorted kernels from the same process
+                 plain sorted kernels from the same process; meamed_mixed_sgd / phocas_mixed_sgd likewise
   --worker-momentum  times only worker_momentum (m <- beta m + g in place over [n, D], the rows
                  replaced by bf16(m); optim.worker_momentum) and reports bytes / time with the
                  12 B per element the kernel must move (2 + 4 read, 2 + 4 written)
@@ -106,6 +108,13 @@ def main():
             lo2, cnt2 = K.sorted_range("trimmed_mean", n, f if 2 * f < n else 0)
             res["trimmed_sgd_ms"] = timeit(lambda: K.agg_update(
                 X, combine="sorted", lo=lo2, cnt=cnt2, opt=opt, master=master, s1=mom, param_out=p), a.reps)
+            fn = max(1, f)   # the nearest-to-centre rules at f = 0 are the mean
+            near = {r: K.near_range(r, n, fn) for r in ("meamed", "phocas")} if 2 * fn < n else {}
+            for r, (lo3, cnt3, keep3) in near.items():
+                res[f"{r}_sgd_ms"] = timeit(lambda: K.agg_update(
+                    X, combine="sorted", lo=lo3, cnt=cnt3, keep=keep3, opt=opt, master=master,
+                    s1=mom, param_out=p), a.reps)
+                res["near_f"] = fn
             if a.mixed:
                 K.gram(X, out=G)
                 fm = max(0, (n - 1) // 3)
@@ -119,6 +128,10 @@ def main():
                 res["trimmed_mixed_sgd_ms"] = timeit(lambda: K.agg_update(
                     X, combine="sorted", lo=lo2, cnt=cnt2, opt=opt, master=master, s1=mom,
                     param_out=p, mix=M), a.reps)
+                for r, (lo3, cnt3, keep3) in near.items():
+                    res[f"{r}_mixed_sgd_ms"] = timeit(lambda: K.agg_update(
+                        X, combine="sorted", lo=lo3, cnt=cnt3, keep=keep3, opt=opt, master=master,
+                        s1=mom, param_out=p, mix=M), a.reps)
             K.robust_weights(G, "krum", n, f=f, w_out=w)
             res["krum_sgd_ms"] = timeit(lambda: K.agg_update(
                 X, combine="weighted", w=w, opt=opt, master=master, s1=mom, param_out=p), a.reps)
@@ -134,6 +147,12 @@ def main():
             res["trimmed_sgd_GBps"] = gbs(n * D * 2 + state, res["trimmed_sgd_ms"])
             res["krum_sgd_GBps"] = gbs(D * 2 + state, res["krum_sgd_ms"])
             res["mean_sgd_GBps"] = gbs(n * D * 2 + state, res["mean_sgd_ms"])
+            for r in near:
+                res[f"{r}_sgd_GBps"] = gbs(n * D * 2 + state, res[f"{r}_sgd_ms"])
+                res[f"{r}_over_median"] = round(res[f"{r}_sgd_ms"] / res["median_sgd_ms"], 3)
+                if a.mixed:
+                    res[f"{r}_mixed_over_median_mixed"] = round(
+                        res[f"{r}_mixed_sgd_ms"] / res["median_mixed_sgd_ms"], 3)
             if a.mixed:
                 for k in ("median", "trimmed"):
                     res[f"{k}_mixed_sgd_GBps"] = gbs(n * D * 2 + state, res[f"{k}_mixed_sgd_ms"])

@@ -10,7 +10,8 @@ f = 2 of them Byzantine from step 0, on two learnable synthetic tasks:
   resnet_tiny  ResNet (width 8, one block per stage) on 32x32 images: one smooth template per
                class plus pixel noise 6x its scale (models.build_task extra synthetic=templates)
 
-Rules:   mean, median, trimmed_mean (trim f), krum (f), multi_krum (m = n - f), geomed,
+Rules:   mean, median, trimmed_mean (trim f), meamed / phocas (the n - f values nearest to the
+         median / to the trimmed mean, per coordinate), krum (f), multi_krum (m = n - f), geomed,
          bulyan (f = (n - 3) // 4 = 1: the rule needs n >= 4f + 3, so at n = 8 it is configured
          for one fault while two attack -- reported as such), centered_clip (tau, 3 iterations)
 Attacks: none, sign_flip (g <- -10 g), gaussian (g <- N(0, sigma^2)), scaled (g <- 100 g),
@@ -49,6 +50,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 RULES = ("mean", "median", "trimmed_mean", "krum", "multi_krum", "geomed", "bulyan",
          "centered_clip")
+NEAR_RULES = ("meamed", "phocas")   # nearest-to-centre coordinate rules (keep n - f per coordinate)
+ALL_RULES = RULES[:3] + NEAR_RULES + RULES[3:]
 ATTACKS = ("none", "sign_flip", "gaussian", "scaled", "alie", "ipm")
 
 TASKS = {
@@ -170,7 +173,7 @@ def markdown(rows: List[Dict[str, object]]) -> str:
     for task in sorted({r["task"] for r in rows}):
         rs = [r for r in rows if r["task"] == task]
         attacks = [a for a in ATTACKS if any(r["attack"] == a for r in rs)]
-        rules = [u for u in RULES if any(r["rule"] == u for r in rs)]
+        rules = [u for u in ALL_RULES if any(r["rule"] == u for r in rs)]
         params = {r["attack"]: r["attack_params"] for r in rs}
         r0 = rs[0]
         pre = f", agg.pre={r0['pre']}" if r0.get("pre") else ""
@@ -208,7 +211,7 @@ def markdown(rows: List[Dict[str, object]]) -> str:
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--task", choices=sorted(TASKS), default="mlp")
-    ap.add_argument("--rules", default=",".join(RULES))
+    ap.add_argument("--rules", default=",".join(ALL_RULES))
     ap.add_argument("--attacks", default=",".join(ATTACKS))
     ap.add_argument("--n", type=int, default=8)
     ap.add_argument("--f", type=int, default=2)

@@ -16,7 +16,9 @@ from typing import Any, Dict, List, Optional
 
 import yaml
 
-RULES = ("mean", "median", "trimmed_mean", "krum", "multi_krum", "geomed", "bulyan", "centered_clip")
+RULES = ("mean", "median", "trimmed_mean", "meamed", "phocas", "krum", "multi_krum", "geomed", "bulyan",
+         "centered_clip")
+COORD_RULES = ("median", "trimmed_mean", "meamed", "phocas")
 TOPOLOGIES = ("allreduce", "allgather", "sharded", "gossip")
 GOSSIP_GRAPHS = ("ring", "exp", "exp_all")
 PRE = ("none", "nnm")
@@ -28,8 +30,11 @@ class AggConfig:
     """Robust aggregation rule and its parameters.
 
     rule          one of RULES
-    f             number of Byzantine workers tolerated (Krum / Multi-Krum / Bulyan)
-    trim          number trimmed from each side per coordinate (trimmed mean); ``None`` -> f
+    f             number of Byzantine workers tolerated (Krum / Multi-Krum / Bulyan); meamed and
+                  phocas average the n - f values nearest to their centre per coordinate (the
+                  median / the trimmed mean)
+    trim          number trimmed from each side per coordinate (trimmed mean, and the centre of
+                  phocas); ``None`` -> f
     m             number of workers averaged by Multi-Krum; ``None`` -> n - f
     iters, eps    Weiszfeld iterations and distance floor (geometric median)
     tau, clip_iters  radius / iterations of centered clipping. With ``optim.worker_momentum`` the
@@ -71,7 +76,7 @@ class AggConfig:
                 raise ValueError(f"agg.pre=nnm is not implemented for rule {self.rule!r}")
             if n <= 2 * self.f:
                 raise ValueError(f"agg.pre=nnm needs n > 2f (n={n}, f={self.f})")
-            if self.rule in ("median", "trimmed_mean") and n > 32:
+            if self.rule in COORD_RULES and n > 32:
                 raise ValueError(f"agg.pre=nnm with {self.rule} supports at most 32 workers "
                                  f"(n={n})")
         # the HIP kernels keep one worker row per lane of a 64-wide wave; centered clipping adds
@@ -79,6 +84,8 @@ class AggConfig:
         limit = 63 if self.rule == "centered_clip" else 64
         if n > limit:
             raise ValueError(f"{self.rule} supports at most {limit} workers (n={n})")
+        if self.rule in ("meamed", "phocas") and n <= 2 * self.f:
+            raise ValueError(f"{self.rule} needs n > 2f (n={n}, f={self.f})")
         if self.rule in ("krum", "multi_krum") and n > 1 and n <= 2 * self.f:
             # Krum's guarantee needs n >= 2f+3; smaller n runs (nearest-neighbour scoring) but
             # f < n/2 is the hard floor.
@@ -86,8 +93,8 @@ class AggConfig:
         if self.rule == "bulyan" and n > 1 and n < 4 * self.f + 3:
             raise ValueError(f"bulyan needs n >= 4f+3 (n={n}, f={self.f})")
         b = self.trim if self.trim is not None else self.f
-        if self.rule == "trimmed_mean" and 2 * b >= n:
-            raise ValueError(f"trimmed_mean needs n > 2*trim (n={n}, trim={b})")
+        if self.rule in ("trimmed_mean", "phocas") and 2 * b >= n:
+            raise ValueError(f"{self.rule} needs n > 2*trim (n={n}, trim={b})")
 
 
 @dataclass

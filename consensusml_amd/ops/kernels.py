@@ -18,7 +18,7 @@ from .native import lib
 
 RULE_IDS = {"mean": 0, "krum": 1, "multi_krum": 2, "geomed": 3, "centered_clip": 4,
             "bulyan_select": 5, "nnm_only": 6}
-COORD_RULES = ("median", "trimmed_mean")
+COORD_RULES = ("median", "trimmed_mean", "meamed", "phocas")
 PRE_IDS = {"none": 0, "nnm": 1}
 GRAM_RULES = ("krum", "multi_krum", "geomed", "centered_clip")
 GOSSIP_MAX_NBRS = 8   # neighbour buffers one gossip_mix_k launch reads (kMaxNbrs, gossip_fault.hip)
@@ -35,6 +35,22 @@ def sorted_range(rule: str, n: int, trim: int = 0) -> Tuple[int, int]:
     if rule == "mean":
         return 0, n
     raise ValueError(rule)
+
+
+def near_range(rule: str, n: int, f: int, trim: Optional[int] = None) -> Tuple[int, int, int]:
+    """(lo, cnt, keep) of a coordinate rule: the centre is the mean of sorted ranks [lo, lo+cnt)
+    and the rule averages the ``keep`` values nearest to it (``reference.mean_around``).
+    keep == 0: the plain window rules (median, trimmed_mean), whose result is the centre."""
+    if rule in ("meamed", "phocas"):
+        if 2 * f >= n:
+            raise ValueError(f"{rule} needs n > 2f (n={n}, f={f})")
+        if rule == "meamed":
+            return (*sorted_range("median", n), n - f)
+        b = f if trim is None else trim
+        if 2 * b >= n:
+            raise ValueError(f"phocas needs n > 2*trim (n={n}, trim={b})")
+        return b, n - 2 * b, n - f
+    return (*sorted_range(rule, n, f if trim is None else trim), 0)
 
 
 @dataclass
@@ -70,7 +86,7 @@ def agg_update(X: torch.Tensor, *, combine: str, lo: int = 0, cnt: int = 1,
                master: Optional[torch.Tensor] = None, s1: Optional[torch.Tensor] = None,
                s2: Optional[torch.Tensor] = None, param_out: Optional[torch.Tensor] = None,
                gout: Optional[torch.Tensor] = None,
-               mix: Optional[torch.Tensor] = None) -> None:
+               mix: Optional[torch.Tensor] = None, keep: Optional[int] = None) -> None:
     """Aggregate worker rows and apply the optimizer in one pass (in place on the state).
 
     combine='sorted'   mean of sorted ranks [lo, lo+cnt) per coordinate
@@ -78,19 +94,23 @@ def agg_update(X: torch.Tensor, *, combine: str, lo: int = 0, cnt: int = 1,
     mix                sorted combine only: fp32 [n, n] on X's device, a linear pre-mix of the
                        rows per coordinate, y_i = sum_j mix[i, j] x_j in fp32, before the sort
                        (n <= 32). A zero entry contributes nothing even where x_j is NaN / inf.
+    keep               sorted combine only: [lo, lo+cnt) is the centre's window and the result is
+                       the mean of the ``keep`` sorted values nearest to the centre
+                       (``reference.mean_around``; n / 2 <= keep <= n). None / 0: the plain window.
     """
     X = _as2d(X)
     n = n if n is not None else (rows.numel() if rows is not None else X.shape[0])
     D = D if D is not None else X.shape[1]
     opt = opt or OptArgs(kind="none")
     _check_mix(mix, combine, n)
+    keep = _check_keep(keep, combine, n)
     if X.is_cuda:
         bc1 = 1.0 - opt.beta1 ** opt.step
         bc2 = 1.0 - opt.beta2 ** opt.step
         lib().agg_update(X, n, D, rows, 0 if combine == "sorted" else 1, lo, cnt, w, opt.opt_id(),
                          master, s1, s2, param_out, gout, opt.lr, opt.momentum, opt.weight_decay,
                          opt.beta1, opt.beta2, opt.eps, opt.lr / bc1, 1.0 / math.sqrt(bc2),
-                         opt.gscale, opt.nesterov, opt.first, mix)
+                         opt.gscale, opt.nesterov, opt.first, mix, keep)
         return
     # ---- CPU reference path
     Xr = X[rows.long()] if rows is not None else X[:n]
@@ -98,8 +118,11 @@ def agg_update(X: torch.Tensor, *, combine: str, lo: int = 0, cnt: int = 1,
     if combine == "sorted":
         if mix is not None:
             Xr = ref.mix_rows(mix[:n, :n].float().cpu(), Xr, torch.float32)
-        S, _ = torch.sort(ref._sanitize(Xr), dim=0)
-        g = S[lo:lo + cnt].mean(0)
+        if keep:
+            g = ref.mean_around(Xr, lo, cnt, keep)
+        else:
+            S, _ = torch.sort(ref._sanitize(Xr), dim=0)
+            g = S[lo:lo + cnt].mean(0)
     else:
         ww = torch.ones(n) if w is None else w[:n].float().cpu()
         nz = (ww != 0).nonzero().flatten()
@@ -124,6 +147,16 @@ def agg_update(X: torch.Tensor, *, combine: str, lo: int = 0, cnt: int = 1,
         s2[:D].copy_(v)
     if param_out is not None:
         param_out[:D].copy_(master[:D].to(param_out.dtype))
+
+
+def _check_keep(keep: Optional[int], combine: str, n: int) -> int:
+    if not keep:
+        return 0
+    if combine != "sorted":
+        raise ValueError("keep is a form of the sorted combine only")
+    if keep < 0 or keep > n or 2 * keep < n:
+        raise ValueError(f"keep must be 0 or in [n / 2, n] (keep={keep}, n={n})")
+    return int(keep)
 
 
 def _check_mix(mix: Optional[torch.Tensor], combine: str, n: int) -> None:
@@ -159,12 +192,13 @@ def agg_update_multi(segs, *, combine: str, lo: int = 0, cnt: int = 1,
                      n: int, opt: Optional[OptArgs] = None, master: Optional[torch.Tensor] = None,
                      s1: Optional[torch.Tensor] = None, s2: Optional[torch.Tensor] = None,
                      gout: Optional[torch.Tensor] = None,
-                     mix: Optional[torch.Tensor] = None) -> None:
+                     mix: Optional[torch.Tensor] = None, keep: Optional[int] = None) -> None:
     """``agg_update`` over several segments in ONE launch on GPU (the sharded engine's buckets).
     ``segs``: (X [rows, >= D], D, off, param_out) -- worker rows, element count, offset into the
     shared master / s1 / s2 / gout vectors, and the segment's parameters."""
     opt = opt or OptArgs(kind="none")
     _check_mix(mix, combine, n)
+    keep = _check_keep(keep, combine, n)
     if segs and segs[0][0].is_cuda and len(segs) <= 16:
         bc1 = 1.0 - opt.beta1 ** opt.step
         bc2 = 1.0 - opt.beta2 ** opt.step
@@ -173,13 +207,13 @@ def agg_update_multi(segs, *, combine: str, lo: int = 0, cnt: int = 1,
                                rows, 0 if combine == "sorted" else 1, lo, cnt, w, opt.opt_id(),
                                master, s1, s2, gout, opt.lr, opt.momentum, opt.weight_decay,
                                opt.beta1, opt.beta2, opt.eps, opt.lr / bc1, 1.0 / math.sqrt(bc2),
-                               opt.gscale, opt.nesterov, opt.first, mix)
+                               opt.gscale, opt.nesterov, opt.first, mix, keep)
         return
     sl = lambda t, o, d: None if t is None else t[o:o + d]   # noqa: E731
     for X, D, off, pout in segs:
         agg_update(X, combine=combine, lo=lo, cnt=cnt, w=w, rows=rows, n=n, D=D, opt=opt,
                    master=sl(master, off, D), s1=sl(s1, off, D), s2=sl(s2, off, D),
-                   param_out=pout, gout=sl(gout, off, D), mix=mix)
+                   param_out=pout, gout=sl(gout, off, D), mix=mix, keep=keep)
 
 
 def gram(X: torch.Tensor, rows: Optional[torch.Tensor] = None, n: Optional[int] = None,
@@ -373,12 +407,12 @@ def aggregate(X: torch.Tensor, rule: str, f: int = 0, trim: Optional[int] = None
     if rule in ("mean",):
         agg_update(X, combine="weighted", w=torch.full((n,), 1.0 / n, device=X.device), gout=out)
     elif rule in COORD_RULES:
-        lo, cnt = sorted_range(rule, n, f if trim is None else trim)
+        lo, cnt, keep = near_range(rule, n, f, trim)
         mix = None
         if pre != "none":
             mix = torch.empty(n, n, dtype=torch.float32, device=X.device)
             robust_weights(gram(X), "nnm_only", n, f, pre=pre, mix_out=mix)
-        agg_update(X, combine="sorted", lo=lo, cnt=cnt, gout=out, mix=mix)
+        agg_update(X, combine="sorted", lo=lo, cnt=cnt, gout=out, mix=mix, keep=keep)
     elif rule in ("krum", "multi_krum", "geomed"):
         G = gram(X)
         w = robust_weights(G, rule, n, f, m, iters, eps, pre=pre)

@@ -48,6 +48,60 @@ def trimmed_mean(X: torch.Tensor, b: int) -> torch.Tensor:
     return S[b:n - b].mean(0)
 
 
+def median_window(n: int) -> Tuple[int, int]:
+    """Sorted-rank window [lo, lo+cnt) of the median of n values."""
+    return ((n - 1) // 2, 1) if n % 2 else (n // 2 - 1, 2)
+
+
+def mean_around(X: torch.Tensor, lo: int, cnt: int, keep: int) -> torch.Tensor:
+    """Mean of the ``keep`` values nearest to a robust centre, per coordinate (MeaMed / Phocas).
+
+    The n values are sanitised (NaN -> +inf) and sorted, s_0 <= ... <= s_{n-1}. The centre c is
+    the mean of ranks [lo, lo+cnt); the result is the mean of ranks [j, j+keep) with
+    j = #{i in [0, n-keep) : (s_{i+keep} - c) < (c - s_i)}, strictly: the keep values nearest to c,
+    ties to the lower rank (the left side does not decrease with i and the right side does not
+    increase, so the true predicates are a prefix). All in fp32: c is the rank-order sum times
+    the fp32 1/cnt, the result the rank-order sum of the window times the fp32 1/keep.
+    s_{i+keep} = +inf makes its predicate false and s_i = -inf makes it true, so with a finite
+    centre and at most n-keep non-finite values no non-finite value reaches the result.
+    keep == n is the plain mean."""
+    S, _ = torch.sort(_sanitize(X), dim=0)
+    n = S.shape[0]
+    if not (0 <= lo and cnt >= 1 and lo + cnt <= n and 1 <= keep <= n):
+        raise ValueError(f"mean_around: window ({lo}, {cnt}) / keep {keep} out of range for n={n}")
+    one = torch.tensor(1.0, dtype=torch.float32)
+    c = torch.zeros_like(S[0])
+    for i in range(lo, lo + cnt):
+        c = c + S[i]
+    c = c * (one / cnt)
+    j = torch.zeros(S.shape[1:], dtype=torch.long, device=S.device)
+    for i in range(n - keep):
+        j = j + ((S[i + keep] - c) < (c - S[i])).long()
+    out = torch.zeros_like(S[0])
+    for i in range(n):
+        inside = (j <= i) & (i < j + keep)
+        out = torch.where(inside, out + S[i], out)
+    return out * (one / keep)
+
+
+def meamed(X: torch.Tensor, f: int) -> torch.Tensor:
+    """Mean around median (Xie, Koyejo, Gupta 2018): the n - f values nearest to the median."""
+    n = X.shape[0]
+    if 2 * f >= n:
+        raise ValueError(f"meamed needs n > 2f (n={n}, f={f})")
+    lo, cnt = median_window(n)
+    return mean_around(X, lo, cnt, n - f)
+
+
+def phocas(X: torch.Tensor, f: int, trim: Optional[int] = None) -> torch.Tensor:
+    """Phocas (Xie, Koyejo, Gupta 2018): the n - f values nearest to the trimmed mean."""
+    n = X.shape[0]
+    b = f if trim is None else trim
+    if 2 * f >= n or 2 * b >= n:
+        raise ValueError(f"phocas needs n > 2f and n > 2 trim (n={n}, f={f}, trim={b})")
+    return mean_around(X, b, n - 2 * b, n - f)
+
+
 def vote(X: torch.Tensor, thresh: float = 0.0) -> torch.Tensor:
     """Coordinate-wise count of workers with |x| > thresh (ConsensusML's selection consensus:
     count == n is the n-way intersection of `model_walkthrough.ipynb:1939`)."""
@@ -299,6 +353,10 @@ def aggregate(X: torch.Tensor, rule: str, f: int = 0, trim: Optional[int] = None
         return coord_median(X)
     if rule == "trimmed_mean":
         return trimmed_mean(X, f if trim is None else trim)
+    if rule == "meamed":
+        return meamed(X, f)
+    if rule == "phocas":
+        return phocas(X, f, trim)
     if rule == "krum":
         w = krum_weights(gram(X), f, 1)
         return (w.float() @ _zero_bad(X)).float()

@@ -759,7 +759,7 @@ class ConsensusEngine:
                 dist.all_reduce(self.G)
         rule = "bulyan_select" if self.rule == "bulyan" else self.rule
         if self.rule not in GRAM_RULES:
-            rule = "nnm_only"    # median / trimmed mean with agg.pre=nnm: the mixing matrix only
+            rule = "nnm_only"    # a coordinate rule with agg.pre=nnm: the mixing matrix only
         m = cfg.m if cfg.m is not None else self.n - cfg.f
         iters = cfg.clip_iters if rule == "centered_clip" else cfg.iters
         # one launch: weights, selection counts and -- centered Gram -- the medoid of this step's
@@ -792,11 +792,10 @@ class ConsensusEngine:
                           gout: Optional[torch.Tensor]) -> None:
         cfg = self.cfg.agg
         m, s1, s2 = self._state(state_off, length)
-        if self.rule in ("median", "trimmed_mean"):
-            trim = cfg.trim if cfg.trim is not None else cfg.f
-            lo, cnt = K.sorted_range(self.rule, self.n, trim)
+        if self.rule in K.COORD_RULES:
+            lo, cnt, keep = K.near_range(self.rule, self.n, cfg.f, cfg.trim)
             K.agg_update(X, combine="sorted", lo=lo, cnt=cnt, n=self.n, D=length, opt=opt,
-                         master=m, s1=s1, s2=s2, param_out=param_out, gout=gout, mix=self.M)
+                         master=m, s1=s1, s2=s2, param_out=param_out, gout=gout, mix=self.M, keep=keep)
         elif self.rule == "bulyan":
             theta = self.n - 2 * cfg.f
             lo, cnt = K.sorted_range("trimmed_mean", theta, cfg.f)
@@ -812,10 +811,10 @@ class ConsensusEngine:
         cfg = self.cfg.agg
         ks = [(X, length, soff, pout) for X, length, pout, soff in segs]
         st = dict(master=self.master, s1=self.s1, s2=self.s2, opt=opt)
-        if self.rule in ("median", "trimmed_mean"):
-            trim = cfg.trim if cfg.trim is not None else cfg.f
-            lo, cnt = K.sorted_range(self.rule, self.n, trim)
-            K.agg_update_multi(ks, combine="sorted", lo=lo, cnt=cnt, n=self.n, mix=self.M, **st)
+        if self.rule in K.COORD_RULES:
+            lo, cnt, keep = K.near_range(self.rule, self.n, cfg.f, cfg.trim)
+            K.agg_update_multi(ks, combine="sorted", lo=lo, cnt=cnt, n=self.n, mix=self.M, keep=keep,
+                               **st)
         elif self.rule == "bulyan":
             theta = self.n - 2 * cfg.f
             lo, cnt = K.sorted_range("trimmed_mean", theta, cfg.f)
@@ -1048,11 +1047,10 @@ class ConsensusEngine:
         cfg = self.cfg.agg
         out = torch.empty(length, dtype=torch.float32, device=X.device)
         none = K.OptArgs(kind="none")
-        if self.rule in ("median", "trimmed_mean"):
-            trim = cfg.trim if cfg.trim is not None else cfg.f
-            lo, cnt = K.sorted_range(self.rule, self.n, trim)
+        if self.rule in K.COORD_RULES:
+            lo, cnt, keep = K.near_range(self.rule, self.n, cfg.f, cfg.trim)
             K.agg_update(X, combine="sorted", lo=lo, cnt=cnt, n=self.n, D=length, opt=none,
-                         gout=out, mix=self.M)
+                         gout=out, mix=self.M, keep=keep)
         elif self.rule == "bulyan":
             theta = self.n - 2 * cfg.f
             lo, cnt = K.sorted_range("trimmed_mean", theta, cfg.f)

@@ -57,6 +57,16 @@ const float* mix_ptr(const optional<Tensor>& mix, const Tensor& X, int64_t n, in
   return mix->data_ptr<float>();
 }
 
+// keep of the sorted combine: 0 (the plain rank window), or the count of sorted values nearest to
+// the centre that are averaged (MeaMed / Phocas), at least half of the rows
+int check_keep(int64_t keep, int64_t n, int64_t combine) {
+  if (keep == 0) return 0;
+  TORCH_CHECK(combine == cml::CMB_SORTED, "keep is a form of the sorted combine only");
+  TORCH_CHECK(keep > 0 && keep <= n, "keep must be in [0, n], got keep=", keep, " n=", n);
+  TORCH_CHECK(2 * keep >= n, "keep must be at least n / 2, got keep=", keep, " n=", n);
+  return static_cast<int>(keep);
+}
+
 // X: [R, C] rows of workers (row stride arbitrary, unit column stride). The aggregation uses n
 // rows (rows[i] indexes X when given) and the first D columns.
 void agg_update(const Tensor& X, int64_t n, int64_t D, const optional<Tensor>& rows, int64_t combine,
@@ -65,7 +75,8 @@ void agg_update(const Tensor& X, int64_t n, int64_t D, const optional<Tensor>& r
                 const optional<Tensor>& s2, const optional<Tensor>& param_out,
                 const optional<Tensor>& gout, double lr, double momentum, double weight_decay,
                 double beta1, double beta2, double eps, double step_size, double inv_sqrt_bc2,
-                double gscale, bool nesterov, bool first, const optional<Tensor>& mix) {
+                double gscale, bool nesterov, bool first, const optional<Tensor>& mix,
+                int64_t keep) {
   check_dev(X, "X");
   TORCH_CHECK(X.dim() == 2 && X.stride(1) == 1, "X must be 2-D with unit column stride");
   TORCH_CHECK(n >= 1 && n <= 64, "1 <= n <= 64 workers supported, got ", n);
@@ -83,6 +94,7 @@ void agg_update(const Tensor& X, int64_t n, int64_t D, const optional<Tensor>& r
   s.w = opt_ptr<const float>(w, at::kFloat, "w", n);
   s.lo = static_cast<int>(lo);
   s.cnt = static_cast<int>(cnt);
+  s.keep = check_keep(keep, n, combine);
   cml::UpdArgs u{};
   u.master = opt_ptr<float>(master, at::kFloat, "master", D);
   u.s1 = opt_ptr<float>(s1, at::kFloat, "s1", D);
@@ -124,7 +136,7 @@ void agg_update_multi(const std::vector<Tensor>& Xs, const std::vector<int64_t>&
                       const optional<Tensor>& gout, double lr, double momentum,
                       double weight_decay, double beta1, double beta2, double eps,
                       double step_size, double inv_sqrt_bc2, double gscale, bool nesterov,
-                      bool first, const optional<Tensor>& mix) {
+                      bool first, const optional<Tensor>& mix, int64_t keep) {
   const size_t ns = Xs.size();
   TORCH_CHECK(ns >= 1 && ns <= 16 && Ds.size() == ns && offs.size() == ns && pouts.size() == ns,
               "agg_update_multi: 1..16 segments with matching Xs / Ds / offs / pouts");
@@ -158,6 +170,7 @@ void agg_update_multi(const std::vector<Tensor>& Xs, const std::vector<int64_t>&
   s.w = opt_ptr<const float>(w, at::kFloat, "w", n);
   s.lo = static_cast<int>(lo);
   s.cnt = static_cast<int>(cnt);
+  s.keep = check_keep(keep, n, combine);
   cml::UpdArgs u{};
   u.master = opt_ptr<float>(master, at::kFloat, "master", need);
   u.s1 = opt_ptr<float>(s1, at::kFloat, "s1", need);
@@ -2659,7 +2672,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("s1"), py::arg("s2"), py::arg("param_out"), py::arg("gout"), py::arg("lr"),
         py::arg("momentum"), py::arg("weight_decay"), py::arg("beta1"), py::arg("beta2"),
         py::arg("eps"), py::arg("step_size"), py::arg("inv_sqrt_bc2"), py::arg("gscale"),
-        py::arg("nesterov"), py::arg("first"), py::arg("mix") = py::none());
+        py::arg("nesterov"), py::arg("first"), py::arg("mix") = py::none(),
+        py::arg("keep") = 0);
   m.def("gram_workspace_bytes", &gram_workspace_bytes);
   m.def("gram", &gram, "G = X X^T (fp64) on MFMA; center: rows relative to that row",
         py::arg("X"), py::arg("n"), py::arg("D"), py::arg("rows"), py::arg("work"), py::arg("G"),
@@ -2683,7 +2697,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("opt"), py::arg("master"), py::arg("s1"), py::arg("s2"), py::arg("gout"),
         py::arg("lr"), py::arg("momentum"), py::arg("weight_decay"), py::arg("beta1"),
         py::arg("beta2"), py::arg("eps"), py::arg("step_size"), py::arg("inv_sqrt_bc2"),
-        py::arg("gscale"), py::arg("nesterov"), py::arg("first"), py::arg("mix") = py::none());
+        py::arg("gscale"), py::arg("nesterov"), py::arg("first"), py::arg("mix") = py::none(),
+        py::arg("keep") = 0);
   m.def("gossip_workspace_bytes", &gossip_workspace_bytes);
   m.def("gossip_mix", &gossip_mix, "ring gossip mixing with neighbour clipping");
   m.def("gossip_mix_k", &gossip_mix_k, "k-neighbour gossip mixing with neighbour clipping (optional "

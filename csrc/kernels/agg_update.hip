@@ -9,6 +9,14 @@
 // and then SGD(momentum, nesterov, wd) or Adam/AdamW on the fp32 master, rewriting the bf16
 // parameters in the same pass. The aggregated gradient never round-trips through HBM.
 //
+// The SORTED combine has a second form, NEAREST (SrcArgs::keep > 0; MeaMed / Phocas): the mean of
+// the keep sorted values nearest to a centre c = mean of ranks [lo, lo+cnt). Those values are a
+// contiguous rank window whose position varies per coordinate (near_combine below). bf16 rows
+// take the fp32 network there, as the mixed combine does: the predicate needs floats. The other
+// form, the packed u16 sort and a decode of all NP keys after it, was not built or measured; by
+// instruction count it would save about a tenth of the vector ALU work at NP = 16 and a quarter
+// at NP = 32.
+//
 // Memory-bound streaming kernel: 16 B per lane per worker row (8 bf16 / 4 f32), grid-stride,
 // <= 2048 workgroups of 256 threads. Row addresses are hoisted out of the loop; padded rows load
 // a clamped (valid) row and are replaced by +inf with a select, so no per-row branch sits
@@ -107,10 +115,83 @@ __device__ __forceinline__ void update_and_store(const UpdArgs& u, int opt, int6
   }
 }
 
+// ----------------------------------------------------------------------------- nearest to centre
+// a: NP sorted values per coordinate (+inf padding on top). k = keep, f = n - k (launchers ensure
+// 1 <= f <= k, so f <= NP / 2). Every window [j, j+k), j <= f, holds the core ranks [f, k); of each
+// pair (s_j, s_{j+k}), j < f, it holds s_{j+k} where (s_{j+k} - c) < (c - s_j) and s_j otherwise
+// (the true predicates are a prefix: the left side does not decrease with j, the right side does
+// not increase, in fp32 as in exact arithmetic). The pair distance k is a runtime value and the
+// register array takes static indices only, so the upper partners come from a copy shifted down
+// by k in log2(NP) conditional static shifts, one scalar branch per bit of k, high bit first;
+// only ranks [0, NP/2) of the result are needed, so stage b moves NP/2 + b - 1 rows at most. The
+// shift is in place after a copy of the low NP/2 rows: 1.5 NP VEC live values at the peak.
+template <int B, int NP, int VEC>
+__device__ __forceinline__ void shift_down(float (&a)[NP][VEC], int k) {
+  if constexpr (B >= 1) {
+    if (k & B) {   // wave-uniform
+#pragma unroll
+      for (int i = 0; i < NP; ++i) {
+        if (i + B < NP && i < NP / 2 + B - 1) {
+#pragma unroll
+          for (int v = 0; v < VEC; ++v) a[i][v] = a[i + B][v];
+        }
+      }
+    }
+    shift_down<B / 2, NP, VEC>(a, k);
+  }
+}
+
+template <int NP, int VEC>
+__device__ __forceinline__ void near_combine(float (&a)[NP][VEC], const SrcArgs& s, float inv,
+                                             float (&g)[VEC]) {
+  constexpr int H = NP / 2;
+  const int k = s.keep, f = s.n - k;
+  float c[VEC];
+#pragma unroll
+  for (int v = 0; v < VEC; ++v) c[v] = 0.0f;
+#pragma unroll
+  for (int i = 0; i < NP; ++i) {
+    if (i >= s.lo && i < s.lo + s.cnt) {
+#pragma unroll
+      for (int v = 0; v < VEC; ++v) c[v] += a[i][v];
+    }
+  }
+#pragma unroll
+  for (int v = 0; v < VEC; ++v) {
+    c[v] *= inv;
+    g[v] = 0.0f;
+  }
+#pragma unroll
+  for (int i = 0; i < NP; ++i) {
+    if (i >= f && i < k) {
+#pragma unroll
+      for (int v = 0; v < VEC; ++v) g[v] += a[i][v];
+    }
+  }
+  float low[H][VEC];
+#pragma unroll
+  for (int j = 0; j < H; ++j) {
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) low[j][v] = a[j][v];
+  }
+  shift_down<H, NP, VEC>(a, k);   // a[j] = s_{j+k} for j < f
+#pragma unroll
+  for (int j = 0; j < H; ++j) {
+    if (j < f) {
+#pragma unroll
+      for (int v = 0; v < VEC; ++v)
+        g[v] += (a[j][v] - c[v]) < (c[v] - low[j][v]) ? a[j][v] : low[j][v];
+    }
+  }
+  const float invk = 1.0f / static_cast<float>(k);
+#pragma unroll
+  for (int v = 0; v < VEC; ++v) g[v] *= invk;
+}
+
 // ----------------------------------------------------------------------------- sorted combine
 // fp32 rows (and the bf16 scalar tail): sort fp32 values. The rank window [lo, lo+cnt) is
 // wave-uniform (kernel arguments), so the per-rank test is a scalar branch, not a VALU select.
-template <typename T, int NP, int VEC, int OPT>
+template <typename T, int NP, int VEC, int OPT, bool NEAR = false>
 __device__ __forceinline__ void agg_sorted_body(const SrcArgs& s, const UpdArgs& u, int64_t base,
     int64_t nvec, int blk, int nblk) {
   const T* X = reinterpret_cast<const T*>(s.X);
@@ -138,17 +219,21 @@ __device__ __forceinline__ void agg_sorted_body(const SrcArgs& s, const UpdArgs&
     }
     sort_columns<float, NP, VEC>(a);
     float g[VEC];
+    if constexpr (NEAR) {
+      near_combine<NP, VEC>(a, s, inv, g);
+    } else {
 #pragma unroll
-    for (int v = 0; v < VEC; ++v) g[v] = 0.0f;
+      for (int v = 0; v < VEC; ++v) g[v] = 0.0f;
 #pragma unroll
-    for (int i = 0; i < NP; ++i) {
-      if (i >= s.lo && i < s.lo + s.cnt) {
+      for (int i = 0; i < NP; ++i) {
+        if (i >= s.lo && i < s.lo + s.cnt) {
 #pragma unroll
-        for (int v = 0; v < VEC; ++v) g[v] += a[i][v];
+          for (int v = 0; v < VEC; ++v) g[v] += a[i][v];
+        }
       }
-    }
 #pragma unroll
-    for (int v = 0; v < VEC; ++v) g[v] *= inv;
+      for (int v = 0; v < VEC; ++v) g[v] *= inv;
+    }
     update_and_store<VEC>(u, OPT, base + e, g, st);
   }
 }
@@ -307,7 +392,7 @@ __device__ __forceinline__ void mix_rows(const float (&sM)[NP * NP], const float
   }
 }
 
-template <typename T, int NP, int VEC, int OPT>
+template <typename T, int NP, int VEC, int OPT, bool NEAR = false>
 __device__ __forceinline__ void agg_mixed_body(const SrcArgs& s, const UpdArgs& u,
     const float* __restrict__ mix, int64_t base, int64_t nvec, int blk, int nblk) {
   __shared__ float sM[NP * NP];
@@ -343,17 +428,21 @@ __device__ __forceinline__ void agg_mixed_body(const SrcArgs& s, const UpdArgs& 
     }
     sort_columns<float, NP, VEC>(a);
     float g[VEC];
+    if constexpr (NEAR) {
+      near_combine<NP, VEC>(a, s, inv, g);
+    } else {
 #pragma unroll
-    for (int v = 0; v < VEC; ++v) g[v] = 0.0f;
+      for (int v = 0; v < VEC; ++v) g[v] = 0.0f;
 #pragma unroll
-    for (int i = 0; i < NP; ++i) {
-      if (i >= s.lo && i < s.lo + s.cnt) {
+      for (int i = 0; i < NP; ++i) {
+        if (i >= s.lo && i < s.lo + s.cnt) {
 #pragma unroll
-        for (int v = 0; v < VEC; ++v) g[v] += a[i][v];
+          for (int v = 0; v < VEC; ++v) g[v] += a[i][v];
+        }
       }
-    }
 #pragma unroll
-    for (int v = 0; v < VEC; ++v) g[v] *= inv;
+      for (int v = 0; v < VEC; ++v) g[v] *= inv;
+    }
     update_and_store<VEC>(u, OPT, base + e, g, st);
   }
 }
@@ -438,6 +527,20 @@ __global__ __launch_bounds__(kBlock) void agg_mixed_kernel(SrcArgs s, UpdArgs u,
   agg_mixed_body<T, NP, VEC, OPT>(s, u, mix, base, nvec, blockIdx.x, gridDim.x);
 }
 
+// The nearest-to-centre forms (keep > 0) are kernels of their own, so the plain instantiations
+// above keep their code.
+template <typename T, int NP, int VEC, int OPT>
+__global__ __launch_bounds__(kBlock) void agg_near_kernel(SrcArgs s, UpdArgs u, int64_t base,
+                                                          int64_t nvec) {
+  agg_sorted_body<T, NP, VEC, OPT, true>(s, u, base, nvec, blockIdx.x, gridDim.x);
+}
+template <typename T, int NP, int VEC, int OPT>
+__global__ __launch_bounds__(kBlock) void agg_near_mixed_kernel(SrcArgs s, UpdArgs u,
+                                                                const float* __restrict__ mix,
+                                                                int64_t base, int64_t nvec) {
+  agg_mixed_body<T, NP, VEC, OPT, true>(s, u, mix, base, nvec, blockIdx.x, gridDim.x);
+}
+
 // Several segments in ONE launch (the sharded engine's buckets: per-bucket worker matrices and
 // parameter shards, one fp32 optimizer-state vector): blockIdx.y = segment. Every segment is on
 // the vector path (checked by the launcher).
@@ -484,6 +587,19 @@ __global__ __launch_bounds__(kBlock) void agg_mixed_multi(SrcArgs s, UpdArgs u,
   agg_mixed_body<T, NP, VEC, OPT>(s, u, mix, 0, t.nvec[blockIdx.y], blockIdx.x, gridDim.x);
 }
 
+template <typename T, int NP, int VEC, int OPT>
+__global__ __launch_bounds__(kBlock) void agg_near_multi(SrcArgs s, UpdArgs u, SegTable t) {
+  seg_args(t, blockIdx.y, s, u);
+  agg_sorted_body<T, NP, VEC, OPT, true>(s, u, 0, t.nvec[blockIdx.y], blockIdx.x, gridDim.x);
+}
+template <typename T, int NP, int VEC, int OPT>
+__global__ __launch_bounds__(kBlock) void agg_near_mixed_multi(SrcArgs s, UpdArgs u,
+                                                               const float* __restrict__ mix,
+                                                               SegTable t) {
+  seg_args(t, blockIdx.y, s, u);
+  agg_mixed_body<T, NP, VEC, OPT, true>(s, u, mix, 0, t.nvec[blockIdx.y], blockIdx.x, gridDim.x);
+}
+
 // ----------------------------------------------------------------------------- dispatch
 // CML_AGG_GRID_CAP: the most workgroups of an update launch (default 0 = no cap: one vector per
 // thread, the form that streams fastest on MI355X -- tools/diag/hbm_copy.py: a one-pass copy
@@ -501,11 +617,17 @@ static inline int grid_for(int64_t nvec) {
   return static_cast<int>(b);
 }
 
-template <typename T, int NP, int VEC>
+template <typename T, int NP, int VEC, bool NEAR = false>
 static void launch_sorted_np(int opt, const SrcArgs& s, const UpdArgs& u, int64_t base,
                              int64_t nvec, hipStream_t st) {
   const int g = grid_for(nvec);
-  if constexpr (sizeof(T) == 2 && VEC >= 2) {   // packed-key path
+  if constexpr (NEAR) {   // fp32 network for both row types
+    switch (opt) {
+      case OPT_NONE: agg_near_kernel<T, NP, VEC, OPT_NONE><<<g, kBlock, 0, st>>>(s, u, base, nvec); break;
+      case OPT_SGD: agg_near_kernel<T, NP, VEC, OPT_SGD><<<g, kBlock, 0, st>>>(s, u, base, nvec); break;
+      default: agg_near_kernel<T, NP, VEC, OPT_ADAM><<<g, kBlock, 0, st>>>(s, u, base, nvec); break;
+    }
+  } else if constexpr (sizeof(T) == 2 && VEC >= 2) {   // packed-key path
     switch (opt) {
       case OPT_NONE: agg_sorted_bf16_kernel<NP, VEC, OPT_NONE><<<g, kBlock, 0, st>>>(s, u, base, nvec); break;
       case OPT_SGD: agg_sorted_bf16_kernel<NP, VEC, OPT_SGD><<<g, kBlock, 0, st>>>(s, u, base, nvec); break;
@@ -545,6 +667,40 @@ static void launch_sorted(int opt, const SrcArgs& s, const UpdArgs& u, int64_t b
   }
 }
 
+// Nearest-to-centre combine: fp32 values for both row types plus the copy of the low half
+// (1.5 NP VEC live fp32). bf16 rows keep 16 B loads up to NP = 4 only: at NP = 8, 8 elements per
+// lane take 172-206 VGPRs (2 waves per SIMD) and ran 1.13-1.21x the plain median kernel, 4
+// elements per lane 86-121 VGPRs (4-5 waves) and 0.98-1.02x. At NP = 16 / 32, 2 elements per lane
+// ran 9-12 % / 25-26 % faster than 4 (bf16 rows; fp32 rows take the same widths, not timed).
+// All in profiles/meamed/README.md.
+static int near_vec(int dtype, int n) {
+  if (n > 8) return 2;
+  return (dtype == DT_BF16 && n <= 4) ? 8 : 4;
+}
+
+template <typename T, bool VECTOR>
+static void launch_near(int opt, const SrcArgs& s, const UpdArgs& u, int64_t base, int64_t D,
+                        hipStream_t st) {
+  // D: number of elements; VECTOR: D is a multiple of near_vec() and all pointers aligned.
+  const int n = s.n;
+  constexpr int V8 = sizeof(T) == 2 ? 8 : 4;
+  if constexpr (VECTOR) {
+    if (n <= 2) launch_sorted_np<T, 2, V8, true>(opt, s, u, base, D / V8, st);
+    else if (n <= 4) launch_sorted_np<T, 4, V8, true>(opt, s, u, base, D / V8, st);
+    else if (n <= 8) launch_sorted_np<T, 8, 4, true>(opt, s, u, base, D / 4, st);
+    else if (n <= 16) launch_sorted_np<T, 16, 2, true>(opt, s, u, base, D / 2, st);
+    else if (n <= 32) launch_sorted_np<T, 32, 2, true>(opt, s, u, base, D / 2, st);
+    else launch_sorted_np<T, 64, 2, true>(opt, s, u, base, D / 2, st);
+  } else {
+    if (n <= 2) launch_sorted_np<T, 2, 1, true>(opt, s, u, base, D, st);
+    else if (n <= 4) launch_sorted_np<T, 4, 1, true>(opt, s, u, base, D, st);
+    else if (n <= 8) launch_sorted_np<T, 8, 1, true>(opt, s, u, base, D, st);
+    else if (n <= 16) launch_sorted_np<T, 16, 1, true>(opt, s, u, base, D, st);
+    else if (n <= 32) launch_sorted_np<T, 32, 1, true>(opt, s, u, base, D, st);
+    else launch_sorted_np<T, 64, 1, true>(opt, s, u, base, D, st);
+  }
+}
+
 // Mixed sorted combine: elements per lane by padded row count. x and y (fp32) are live together,
 // 2 NP VEC VGPRs: 64 at NP <= 8 (NP = 4 keeps 16-B bf16 loads), 128 at NP = 16 / 32.
 static int mixed_np(int n) { return n <= 4 ? 4 : n <= 8 ? 8 : n <= 16 ? 16 : 32; }
@@ -558,6 +714,14 @@ template <typename T, int NP, int VEC>
 static void launch_mixed_np(int opt, const SrcArgs& s, const UpdArgs& u, const float* mix,
                             int64_t base, int64_t nvec, hipStream_t st) {
   const int g = grid_for(nvec);
+  if (s.keep > 0) {
+    switch (opt) {
+      case OPT_NONE: agg_near_mixed_kernel<T, NP, VEC, OPT_NONE><<<g, kBlock, 0, st>>>(s, u, mix, base, nvec); break;
+      case OPT_SGD: agg_near_mixed_kernel<T, NP, VEC, OPT_SGD><<<g, kBlock, 0, st>>>(s, u, mix, base, nvec); break;
+      default: agg_near_mixed_kernel<T, NP, VEC, OPT_ADAM><<<g, kBlock, 0, st>>>(s, u, mix, base, nvec); break;
+    }
+    return;
+  }
   switch (opt) {
     case OPT_NONE: agg_mixed_kernel<T, NP, VEC, OPT_NONE><<<g, kBlock, 0, st>>>(s, u, mix, base, nvec); break;
     case OPT_SGD: agg_mixed_kernel<T, NP, VEC, OPT_SGD><<<g, kBlock, 0, st>>>(s, u, mix, base, nvec); break;
@@ -587,6 +751,14 @@ static void launch_mixed(int opt, const SrcArgs& s, const UpdArgs& u, const floa
 template <typename T, int NP, int VEC>
 static void launch_mixed_multi_np(int opt, const SrcArgs& s, const UpdArgs& u, const float* mix,
                                   const SegTable& t, dim3 g, hipStream_t st) {
+  if (s.keep > 0) {
+    switch (opt) {
+      case OPT_NONE: agg_near_mixed_multi<T, NP, VEC, OPT_NONE><<<g, kBlock, 0, st>>>(s, u, mix, t); break;
+      case OPT_SGD: agg_near_mixed_multi<T, NP, VEC, OPT_SGD><<<g, kBlock, 0, st>>>(s, u, mix, t); break;
+      default: agg_near_mixed_multi<T, NP, VEC, OPT_ADAM><<<g, kBlock, 0, st>>>(s, u, mix, t); break;
+    }
+    return;
+  }
   switch (opt) {
     case OPT_NONE: agg_mixed_multi<T, NP, VEC, OPT_NONE><<<g, kBlock, 0, st>>>(s, u, mix, t); break;
     case OPT_SGD: agg_mixed_multi<T, NP, VEC, OPT_SGD><<<g, kBlock, 0, st>>>(s, u, mix, t); break;
@@ -621,7 +793,8 @@ static hipError_t agg_update_t(int combine, int opt, const SrcArgs& s, const Upd
   const int esz = sizeof(T);
   const int dt = esz == 2 ? DT_BF16 : DT_F32;
   const int vec = combine == CMB_WEIGHTED ? (esz == 2 ? 8 : 4)
-                  : mix ? mixed_vec(dt, s.n) : sorted_vec(dt, s.n);
+                  : mix ? mixed_vec(dt, s.n)
+                  : s.keep > 0 ? near_vec(dt, s.n) : sorted_vec(dt, s.n);
   // The vector path needs every row start and every state pointer aligned to VEC elements.
   bool ok = (s.ld % vec) == 0 && aligned(s.X, vec * esz) && aligned(u.master, vec * 4) &&
             aligned(u.s1, vec * 4) && aligned(u.s2, vec * 4) && aligned(u.gout, vec * 4) &&
@@ -633,6 +806,8 @@ static hipError_t agg_update_t(int combine, int opt, const SrcArgs& s, const Upd
       else launch_weighted<T, 4>(opt, s, u, 0, Dv / 4, st);
     } else if (mix) {
       launch_mixed<T, true>(opt, s, u, mix, 0, Dv, st);
+    } else if (s.keep > 0) {
+      launch_near<T, true>(opt, s, u, 0, Dv, st);
     } else {
       launch_sorted<T, true>(opt, s, u, 0, Dv, st);
     }
@@ -640,15 +815,22 @@ static hipError_t agg_update_t(int combine, int opt, const SrcArgs& s, const Upd
   if (D > Dv) {  // scalar tail (or fully unaligned inputs)
     if (combine == CMB_WEIGHTED) launch_weighted<T, 1>(opt, s, u, Dv, D - Dv, st);
     else if (mix) launch_mixed<T, false>(opt, s, u, mix, Dv, D - Dv, st);
+    else if (s.keep > 0) launch_near<T, false>(opt, s, u, Dv, D - Dv, st);
     else launch_sorted<T, false>(opt, s, u, Dv, D - Dv, st);
   }
   return hipGetLastError();
 }
 
-template <typename T, int NP, int VEC>
+template <typename T, int NP, int VEC, bool NEAR = false>
 static void launch_sorted_multi_np(int opt, const SrcArgs& s, const UpdArgs& u, const SegTable& t,
                                    dim3 g, hipStream_t st) {
-  if constexpr (sizeof(T) == 2 && VEC >= 2) {
+  if constexpr (NEAR) {
+    switch (opt) {
+      case OPT_NONE: agg_near_multi<T, NP, VEC, OPT_NONE><<<g, kBlock, 0, st>>>(s, u, t); break;
+      case OPT_SGD: agg_near_multi<T, NP, VEC, OPT_SGD><<<g, kBlock, 0, st>>>(s, u, t); break;
+      default: agg_near_multi<T, NP, VEC, OPT_ADAM><<<g, kBlock, 0, st>>>(s, u, t); break;
+    }
+  } else if constexpr (sizeof(T) == 2 && VEC >= 2) {
     switch (opt) {
       case OPT_NONE: agg_sorted_bf16_multi<NP, VEC, OPT_NONE><<<g, kBlock, 0, st>>>(s, u, t); break;
       case OPT_SGD: agg_sorted_bf16_multi<NP, VEC, OPT_SGD><<<g, kBlock, 0, st>>>(s, u, t); break;
@@ -670,7 +852,8 @@ static hipError_t agg_update_multi_t(int combine, int opt, const SrcArgs& s, con
   const int esz = sizeof(T);
   const int dt = esz == 2 ? DT_BF16 : DT_F32;
   const int vec = combine == CMB_WEIGHTED ? (esz == 2 ? 8 : 4)
-                  : mix ? mixed_vec(dt, s.n) : sorted_vec(dt, s.n);
+                  : mix ? mixed_vec(dt, s.n)
+                  : s.keep > 0 ? near_vec(dt, s.n) : sorted_vec(dt, s.n);
   bool ok = nseg >= 1 && nseg <= kMaxSegs;
   SegTable t{};
   int64_t maxv = 0;
@@ -723,6 +906,15 @@ static hipError_t agg_update_multi_t(int combine, int opt, const SrcArgs& s, con
     else if (np == 8) launch_mixed_multi_np<T, 8, 4>(opt, s, u, mix, t, g, st);
     else if (np == 16) launch_mixed_multi_np<T, 16, 4>(opt, s, u, mix, t, g, st);
     else launch_mixed_multi_np<T, 32, 2>(opt, s, u, mix, t, g, st);
+  } else if (s.keep > 0) {
+    constexpr int V8 = sizeof(T) == 2 ? 8 : 4;
+    const int n = s.n;
+    if (n <= 2) launch_sorted_multi_np<T, 2, V8, true>(opt, s, u, t, g, st);
+    else if (n <= 4) launch_sorted_multi_np<T, 4, V8, true>(opt, s, u, t, g, st);
+    else if (n <= 8) launch_sorted_multi_np<T, 8, 4, true>(opt, s, u, t, g, st);
+    else if (n <= 16) launch_sorted_multi_np<T, 16, 2, true>(opt, s, u, t, g, st);
+    else if (n <= 32) launch_sorted_multi_np<T, 32, 2, true>(opt, s, u, t, g, st);
+    else launch_sorted_multi_np<T, 64, 2, true>(opt, s, u, t, g, st);
   } else {
     constexpr bool BF = sizeof(T) == 2;
     const int n = s.n;
@@ -736,6 +928,19 @@ static hipError_t agg_update_multi_t(int combine, int opt, const SrcArgs& s, con
   return hipGetLastError();
 }
 
+// keep: 0, or a sorted combine keeping at least half of the rows (near_combine's window needs
+// f = n - keep <= keep). keep == n is the plain mean of all n rows: the fixed window [0, n).
+static bool near_args(int combine, SrcArgs& s) {
+  if (s.keep == 0) return true;
+  if (combine != CMB_SORTED || s.keep < 0 || s.keep > s.n || 2 * s.keep < s.n) return false;
+  if (s.keep == s.n) {
+    s.lo = 0;
+    s.cnt = s.n;
+    s.keep = 0;
+  }
+  return true;
+}
+
 hipError_t launch_agg_update_multi(int dtype, int combine, int opt, const SrcArgs& src,
                                    const UpdArgs& upd, const AggSeg* segs, int nseg,
                                    hipStream_t stream, const float* mix) {
@@ -743,9 +948,11 @@ hipError_t launch_agg_update_multi(int dtype, int combine, int opt, const SrcArg
   if (combine == CMB_SORTED && (src.cnt < 1 || src.lo < 0 || src.lo + src.cnt > src.n))
     return hipErrorInvalidValue;
   if (mix && (combine != CMB_SORTED || src.n > kMaxMixRows)) return hipErrorInvalidValue;
+  SrcArgs s = src;
+  if (!near_args(combine, s)) return hipErrorInvalidValue;
   if (dtype == DT_BF16)
-    return agg_update_multi_t<bf16>(combine, opt, src, upd, segs, nseg, stream, mix);
-  return agg_update_multi_t<float>(combine, opt, src, upd, segs, nseg, stream, mix);
+    return agg_update_multi_t<bf16>(combine, opt, s, upd, segs, nseg, stream, mix);
+  return agg_update_multi_t<float>(combine, opt, s, upd, segs, nseg, stream, mix);
 }
 
 hipError_t launch_agg_update(int dtype, int combine, int opt, const SrcArgs& src,
@@ -754,8 +961,10 @@ hipError_t launch_agg_update(int dtype, int combine, int opt, const SrcArgs& src
   if (combine == CMB_SORTED && (src.cnt < 1 || src.lo < 0 || src.lo + src.cnt > src.n))
     return hipErrorInvalidValue;
   if (mix && (combine != CMB_SORTED || src.n > kMaxMixRows)) return hipErrorInvalidValue;
-  if (dtype == DT_BF16) return agg_update_t<bf16>(combine, opt, src, upd, D, stream, mix);
-  return agg_update_t<float>(combine, opt, src, upd, D, stream, mix);
+  SrcArgs s = src;
+  if (!near_args(combine, s)) return hipErrorInvalidValue;
+  if (dtype == DT_BF16) return agg_update_t<bf16>(combine, opt, s, upd, D, stream, mix);
+  return agg_update_t<float>(combine, opt, s, upd, D, stream, mix);
 }
 
 }  // namespace cml

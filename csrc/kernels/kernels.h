@@ -23,10 +23,15 @@ enum Rule : int {
 // Worker rows of a [n, ld] matrix: row i of the aggregation is X + rows[i]*ld (rows == nullptr:
 // identity). Sorted combine averages sorted ranks [lo, lo+cnt); weighted combine computes
 // sum_i w[i] x_i (w == nullptr: all ones), skipping zero-weight rows.
+// keep > 0 (sorted combine, n <= 2 keep <= 2 n): the centre c is the mean of ranks [lo, lo+cnt) and
+// the result is the mean of the keep sorted values nearest to c (ties to the lower rank) -- a
+// contiguous rank window [j, j+keep), j = #{i < n-keep : (s[i+keep] - c) < (c - s[i])} in fp32
+// (MeaMed: the median window as centre; Phocas: the trimmed window). keep == 0: the plain window.
 struct SrcArgs {
   const void* X;
   int64_t ld;
   int n;
+  int keep;          // (sits in the padding after n: the layout of the other fields is unchanged)
   const int* rows;
   const float* w;
   int lo, cnt;

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Per-kernel VGPR / AGPR / spill / occupancy / LDS table of HIP sources (gfx950), from the
+"""Per-kernel VGPR / AGPR / spill / scratch (bytes per lane) / occupancy / LDS table of HIP sources (gfx950), from the
 compiler's kernel-resource-usage remarks:  python tools/kernel_resources.py csrc/kernels/gram.hip"""
 import os
 import re
@@ -34,5 +34,6 @@ if __name__ == "__main__":
         for r in table(src):
             g = r.get
             print(f"{g('VGPRs', '?'):>4} vgpr {g('AGPRs', '?'):>4} agpr  spill {g('VGPRs Spill', '?'):>4}"
+                  f"  scratch {g('ScratchSize [bytes/lane]', '?'):>4}"
                   f"  occ {g('Occupancy [waves/SIMD]', '?'):>2}  lds {g('LDS Size [bytes/block]', '?'):>6}"
                   f"  {r['name']}")
