@@ -105,12 +105,8 @@ def agg_update(X: torch.Tensor, *, combine: str, lo: int = 0, cnt: int = 1,
     _check_mix(mix, combine, n)
     keep = _check_keep(keep, combine, n)
     if X.is_cuda:
-        bc1 = 1.0 - opt.beta1 ** opt.step
-        bc2 = 1.0 - opt.beta2 ** opt.step
-        lib().agg_update(X, n, D, rows, 0 if combine == "sorted" else 1, lo, cnt, w, opt.opt_id(),
-                         master, s1, s2, param_out, gout, opt.lr, opt.momentum, opt.weight_decay,
-                         opt.beta1, opt.beta2, opt.eps, opt.lr / bc1, 1.0 / math.sqrt(bc2),
-                         opt.gscale, opt.nesterov, opt.first, mix, keep)
+        head, tail = _binding_args(rows, combine, lo, cnt, w, opt, master, s1, s2, gout, mix, keep)
+        lib().agg_update(X, n, D, *head, param_out, *tail)
         return
     # ---- CPU reference path
     Xr = X[rows.long()] if rows is not None else X[:n]
@@ -147,6 +143,17 @@ def agg_update(X: torch.Tensor, *, combine: str, lo: int = 0, cnt: int = 1,
         s2[:D].copy_(v)
     if param_out is not None:
         param_out[:D].copy_(master[:D].to(param_out.dtype))
+
+
+def _binding_args(rows, combine, lo, cnt, w, opt, master, s1, s2, gout, mix, keep):
+    """What ``lib().agg_update`` and ``lib().agg_update_multi`` both take: the arguments from
+    ``rows`` to ``s2`` and, after the single form's ``param_out``, those from ``gout`` on."""
+    bc1 = 1.0 - opt.beta1 ** opt.step
+    bc2 = 1.0 - opt.beta2 ** opt.step
+    head = (rows, 0 if combine == "sorted" else 1, lo, cnt, w, opt.opt_id(), master, s1, s2)
+    tail = (gout, opt.lr, opt.momentum, opt.weight_decay, opt.beta1, opt.beta2, opt.eps,
+            opt.lr / bc1, 1.0 / math.sqrt(bc2), opt.gscale, opt.nesterov, opt.first, mix, keep)
+    return head, tail
 
 
 def _check_keep(keep: Optional[int], combine: str, n: int) -> int:
@@ -200,14 +207,10 @@ def agg_update_multi(segs, *, combine: str, lo: int = 0, cnt: int = 1,
     _check_mix(mix, combine, n)
     keep = _check_keep(keep, combine, n)
     if segs and segs[0][0].is_cuda and len(segs) <= 16:
-        bc1 = 1.0 - opt.beta1 ** opt.step
-        bc2 = 1.0 - opt.beta2 ** opt.step
+        head, tail = _binding_args(rows, combine, lo, cnt, w, opt, master, s1, s2, gout, mix, keep)
         lib().agg_update_multi([_as2d(x) for x, _, _, _ in segs], [int(d) for _, d, _, _ in segs],
                                [int(o) for _, _, o, _ in segs], [p for _, _, _, p in segs], n,
-                               rows, 0 if combine == "sorted" else 1, lo, cnt, w, opt.opt_id(),
-                               master, s1, s2, gout, opt.lr, opt.momentum, opt.weight_decay,
-                               opt.beta1, opt.beta2, opt.eps, opt.lr / bc1, 1.0 / math.sqrt(bc2),
-                               opt.gscale, opt.nesterov, opt.first, mix, keep)
+                               *head, *tail)
         return
     sl = lambda t, o, d: None if t is None else t[o:o + d]   # noqa: E731
     for X, D, off, pout in segs:

@@ -67,6 +67,52 @@ int check_keep(int64_t keep, int64_t n, int64_t combine) {
   return static_cast<int>(keep);
 }
 
+// The rule's part of SrcArgs, shared by every segment; the caller adds X and ld.
+cml::SrcArgs rule_args(int64_t n, const optional<Tensor>& rows, int64_t combine, int64_t lo,
+                       int64_t cnt, const optional<Tensor>& w, int64_t keep) {
+  cml::SrcArgs s{};
+  s.n = static_cast<int>(n);
+  s.rows = opt_ptr<const int>(rows, at::kInt, "rows", n);
+  s.w = opt_ptr<const float>(w, at::kFloat, "w", n);
+  s.lo = static_cast<int>(lo);
+  s.cnt = static_cast<int>(cnt);
+  s.keep = check_keep(keep, n, combine);
+  return s;
+}
+
+// UpdArgs of optimizer opt (OPT_*; adam_l2: Adam's L2 term) over state vectors of at least
+// `need` elements; the caller adds param_out.
+cml::UpdArgs upd_args(int64_t opt, int adam_l2, int64_t need, const optional<Tensor>& master,
+                      const optional<Tensor>& s1, const optional<Tensor>& s2,
+                      const optional<Tensor>& gout, bool param_f32, double lr, double momentum,
+                      double weight_decay, double beta1, double beta2, double eps,
+                      double step_size, double inv_sqrt_bc2, double gscale, bool nesterov,
+                      bool first) {
+  cml::UpdArgs u{};
+  u.master = opt_ptr<float>(master, at::kFloat, "master", need);
+  u.s1 = opt_ptr<float>(s1, at::kFloat, "s1", need);
+  u.s2 = opt_ptr<float>(s2, at::kFloat, "s2", need);
+  u.gout = opt_ptr<float>(gout, at::kFloat, "gout", need);
+  u.param_f32 = param_f32 ? 1 : 0;
+  if (opt != cml::OPT_NONE) TORCH_CHECK(u.master, "optimizer update needs master weights");
+  if (opt == cml::OPT_SGD && momentum != 0.0) TORCH_CHECK(u.s1, "SGD momentum needs s1");
+  if (opt == cml::OPT_ADAM) TORCH_CHECK(u.s1 && u.s2, "Adam needs s1 and s2");
+  if (opt == cml::OPT_NONE) TORCH_CHECK(u.gout, "OPT_NONE needs gout");
+  u.lr = static_cast<float>(lr);
+  u.momentum = static_cast<float>(momentum);
+  u.weight_decay = static_cast<float>(weight_decay);
+  u.beta1 = static_cast<float>(beta1);
+  u.beta2 = static_cast<float>(beta2);
+  u.eps = static_cast<float>(eps);
+  u.step_size = static_cast<float>(step_size);
+  u.inv_sqrt_bc2 = static_cast<float>(inv_sqrt_bc2);
+  u.gscale = static_cast<float>(gscale);
+  u.nesterov = nesterov ? 1 : 0;
+  u.first = first ? 1 : 0;
+  u.adam_l2 = adam_l2;
+  return u;
+}
+
 // X: [R, C] rows of workers (row stride arbitrary, unit column stride). The aggregation uses n
 // rows (rows[i] indexes X when given) and the first D columns.
 void agg_update(const Tensor& X, int64_t n, int64_t D, const optional<Tensor>& rows, int64_t combine,
@@ -85,41 +131,16 @@ void agg_update(const Tensor& X, int64_t n, int64_t D, const optional<Tensor>& r
   if (adam_l2) opt = cml::OPT_ADAM;
   TORCH_CHECK(D >= 0 && D <= X.size(1), "D out of range");
   const c10::DeviceGuard guard(X.device());
-  cml::SrcArgs s{};
+  cml::SrcArgs s = rule_args(n, rows, combine, lo, cnt, w, keep);
   s.X = X.data_ptr();
   s.ld = X.stride(0);
-  s.n = static_cast<int>(n);
-  s.rows = opt_ptr<const int>(rows, at::kInt, "rows", n);
   if (!s.rows) TORCH_CHECK(X.size(0) >= n, "X has fewer rows than n");
-  s.w = opt_ptr<const float>(w, at::kFloat, "w", n);
-  s.lo = static_cast<int>(lo);
-  s.cnt = static_cast<int>(cnt);
-  s.keep = check_keep(keep, n, combine);
-  cml::UpdArgs u{};
-  u.master = opt_ptr<float>(master, at::kFloat, "master", D);
-  u.s1 = opt_ptr<float>(s1, at::kFloat, "s1", D);
-  u.s2 = opt_ptr<float>(s2, at::kFloat, "s2", D);
   const bool pf32 = param_out.has_value() && param_out->defined() &&
                     param_out->scalar_type() == at::kFloat;
+  cml::UpdArgs u = upd_args(opt, adam_l2, D, master, s1, s2, gout, pf32, lr, momentum,
+                            weight_decay, beta1, beta2, eps, step_size, inv_sqrt_bc2, gscale,
+                            nesterov, first);
   u.param_out = opt_ptr<void>(param_out, pf32 ? at::kFloat : at::kBFloat16, "param_out", D);
-  u.param_f32 = pf32 ? 1 : 0;
-  u.gout = opt_ptr<float>(gout, at::kFloat, "gout", D);
-  if (opt != cml::OPT_NONE) TORCH_CHECK(u.master, "optimizer update needs master weights");
-  if (opt == cml::OPT_SGD && momentum != 0.0) TORCH_CHECK(u.s1, "SGD momentum needs s1");
-  if (opt == cml::OPT_ADAM) TORCH_CHECK(u.s1 && u.s2, "Adam needs s1 and s2");
-  if (opt == cml::OPT_NONE) TORCH_CHECK(u.gout, "OPT_NONE needs gout");
-  u.lr = static_cast<float>(lr);
-  u.momentum = static_cast<float>(momentum);
-  u.weight_decay = static_cast<float>(weight_decay);
-  u.beta1 = static_cast<float>(beta1);
-  u.beta2 = static_cast<float>(beta2);
-  u.eps = static_cast<float>(eps);
-  u.step_size = static_cast<float>(step_size);
-  u.inv_sqrt_bc2 = static_cast<float>(inv_sqrt_bc2);
-  u.gscale = static_cast<float>(gscale);
-  u.nesterov = nesterov ? 1 : 0;
-  u.first = first ? 1 : 0;
-  u.adam_l2 = adam_l2;
   const float* mx = mix_ptr(mix, X, n, combine);
   CML_CHECK_HIP(cml::launch_agg_update(dtype_of(X), static_cast<int>(combine), static_cast<int>(opt),
                                        s, u, D, cur_stream(), mx));
@@ -164,35 +185,10 @@ void agg_update_multi(const std::vector<Tensor>& Xs, const std::vector<int64_t>&
     need = std::max(need, offs[i] + Ds[i]);
   }
   const c10::DeviceGuard guard(Xs[0].device());
-  cml::SrcArgs s{};
-  s.n = static_cast<int>(n);
-  s.rows = opt_ptr<const int>(rows, at::kInt, "rows", n);
-  s.w = opt_ptr<const float>(w, at::kFloat, "w", n);
-  s.lo = static_cast<int>(lo);
-  s.cnt = static_cast<int>(cnt);
-  s.keep = check_keep(keep, n, combine);
-  cml::UpdArgs u{};
-  u.master = opt_ptr<float>(master, at::kFloat, "master", need);
-  u.s1 = opt_ptr<float>(s1, at::kFloat, "s1", need);
-  u.s2 = opt_ptr<float>(s2, at::kFloat, "s2", need);
-  u.gout = opt_ptr<float>(gout, at::kFloat, "gout", need);
-  u.param_f32 = pf32 ? 1 : 0;
-  if (opt != cml::OPT_NONE) TORCH_CHECK(u.master, "optimizer update needs master weights");
-  if (opt == cml::OPT_SGD && momentum != 0.0) TORCH_CHECK(u.s1, "SGD momentum needs s1");
-  if (opt == cml::OPT_ADAM) TORCH_CHECK(u.s1 && u.s2, "Adam needs s1 and s2");
-  if (opt == cml::OPT_NONE) TORCH_CHECK(u.gout, "OPT_NONE needs gout");
-  u.lr = static_cast<float>(lr);
-  u.momentum = static_cast<float>(momentum);
-  u.weight_decay = static_cast<float>(weight_decay);
-  u.beta1 = static_cast<float>(beta1);
-  u.beta2 = static_cast<float>(beta2);
-  u.eps = static_cast<float>(eps);
-  u.step_size = static_cast<float>(step_size);
-  u.inv_sqrt_bc2 = static_cast<float>(inv_sqrt_bc2);
-  u.gscale = static_cast<float>(gscale);
-  u.nesterov = nesterov ? 1 : 0;
-  u.first = first ? 1 : 0;
-  u.adam_l2 = adam_l2;
+  const cml::SrcArgs s = rule_args(n, rows, combine, lo, cnt, w, keep);
+  const cml::UpdArgs u = upd_args(opt, adam_l2, need, master, s1, s2, gout, pf32, lr, momentum,
+                                  weight_decay, beta1, beta2, eps, step_size, inv_sqrt_bc2,
+                                  gscale, nesterov, first);
   const float* mx = mix_ptr(mix, Xs[0], n, combine);
   CML_CHECK_HIP(cml::launch_agg_update_multi(dtype_of(Xs[0]), static_cast<int>(combine),
                                              static_cast<int>(opt), s, u, segs.data(),

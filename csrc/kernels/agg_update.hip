@@ -17,11 +17,18 @@
 // instruction count it would save about a tenth of the vector ALU work at NP = 16 and a quarter
 // at NP = 32.
 //
-// Memory-bound streaming kernel: 16 B per lane per worker row (8 bf16 / 4 f32), grid-stride,
-// <= 2048 workgroups of 256 threads. Row addresses are hoisted out of the loop; padded rows load
-// a clamped (valid) row and are replaced by +inf with a select, so no per-row branch sits
-// between the loads (hipcc would otherwise wait vmcnt(0) per row).
+// Memory-bound streaming kernel: up to 16 B per lane per worker row (Form::vec below), workgroups
+// of 256 threads. A single-segment launch has no grid cap by default, one vector per thread
+// (CML_AGG_GRID_CAP, grid_for below); a multi-segment launch strides at most 2048 / nseg
+// workgroups over each segment. Row addresses are hoisted out of the loop; padded rows load a
+// clamped (valid) row and are replaced by +inf with a select, so no per-row branch sits between
+// the loads (hipcc would otherwise wait vmcnt(0) per row).
+//
+// Every kernel is one (Form, NP, VEC, OPT) instance of agg_kernel / agg_multi; Form is the only
+// table of padded row counts and elements per lane, read by the launch ladder and by the
+// run-time alignment checks alike (dispatch, at the end of the file).
 #include <cstdlib>
+#include <type_traits>
 
 #include "common.h"
 #include "kernels.h"
@@ -32,6 +39,48 @@ constexpr int kBlock = 256;
 constexpr int kMaxRows = 64;
 constexpr int kMaxSegs = 16;   // segments of one multi-segment launch
 constexpr int kMaxMixRows = 32;   // rows of the mixed sorted combine (x and y live in VGPRs)
+
+// ----------------------------------------------------------------------------- dispatch space
+// One kernel form: the row type, the sorted combine's variants (NEAR: SrcArgs::keep > 0, MIX: a
+// pre-mix matrix) or the weighted combine. np(n) is the padded row count of the sorting network
+// (0: no network) and vec(NP, vector) the elements per lane; both are evaluated at compile time
+// by the launch ladder and at run time by the alignment checks.
+template <typename T_, bool NEAR, bool MIX, bool WEIGHTED = false>
+struct Form {
+  using T = T_;
+  static constexpr bool near = NEAR, mix = MIX, weighted = WEIGHTED;
+  static constexpr bool bf = sizeof(T) == 2;
+
+  // The mixed forms start at 4 rows (n <= 4 pads to 4, not 2) and end at kMaxMixRows.
+  static constexpr int np(int n) {
+    if (WEIGHTED) return 0;
+    int p = MIX ? 4 : 2;
+    while (p < n && p < (MIX ? kMaxMixRows : kMaxRows)) p *= 2;
+    return p;
+  }
+
+  static constexpr int vec(int NP, bool vector) {
+    if (!vector) return 1;   // scalar tail, or unaligned inputs
+    const int full = bf ? 8 : 4;   // 16 B per lane per row
+    if (WEIGHTED) return full;
+    // Mixed: x and y (fp32) are live together, 2 NP VEC VGPRs: 64 at NP <= 8 (NP = 4 keeps 16-B
+    // bf16 loads), 128 at NP = 16 / 32. The nearest-mixed form takes the same widths.
+    if (MIX) return NP <= 4 ? full : NP <= 16 ? 4 : 2;
+    // Nearest to centre: fp32 values for both row types plus the copy of the low half (1.5 NP VEC
+    // live fp32). bf16 rows keep 16 B loads up to NP = 4 only: at NP = 8, 8 elements per lane take
+    // 172-206 VGPRs (2 waves per SIMD) and ran 1.13-1.21x the plain median kernel, 4 elements per
+    // lane 86-121 VGPRs (4-5 waves) and 0.98-1.02x. At NP = 16 / 32, 2 elements per lane ran
+    // 9-12 % / 25-26 % faster than 4 (bf16 rows; fp32 rows take the same widths, not timed).
+    // All in profiles/meamed/README.md.
+    if (NEAR) return NP <= 4 ? full : NP <= 8 ? 4 : 2;
+    // Plain: bf16 keys take half a VGPR per value, so bf16 keeps 16 B loads up to NP = 32;
+    // NP = 64 drops to 2 elements per lane.
+    return NP <= 32 ? full : 2;
+  }
+
+  // bf16 rows of the plain form sort packed u16 keys, two coordinates per word
+  static constexpr bool packed(int VEC) { return bf && !NEAR && !MIX && !WEIGHTED && VEC >= 2; }
+};
 
 // Optimizer state of VEC coordinates, loaded BEFORE the combine so those HBM reads are in flight
 // while the sort / weighted sum runs (hipcc does not hoist them above the VALU work by itself).
@@ -188,12 +237,114 @@ __device__ __forceinline__ void near_combine(float (&a)[NP][VEC], const SrcArgs&
   for (int v = 0; v < VEC; ++v) g[v] *= invk;
 }
 
+// ----------------------------------------------------------------------------- mixed sorted combine
+// A linear pre-mix of the rows ahead of the sort (nearest-neighbour mixing for the coordinate
+// rules): per coordinate y_i = sum_j M_ij x_j in fp32 (an fmaf chain in j order), then the
+// sanitising, network and rank window of agg_sorted_body on y. M (fp32 [n, n]) is staged once per
+// workgroup into LDS, zero-padded to NP x NP, and read back as broadcasts (every lane the same
+// address). x and y are both live during the mix, so VEC is chosen per NP to keep 2 NP VEC fp32
+// in registers (Form::vec); the mixed values are fp32, so bf16 rows take the fp32 network.
+//
+// "M_ij == 0 contributes nothing even where x_j is NaN / inf": with every loaded value finite a
+// zero entry adds an exact zero, so the fast path is plain (packed) FMAs. One extra FMA per loaded
+// value (x * 0 accumulates to NaN iff some x is non-finite) detects the other case, and a wave
+// that saw a non-finite value redoes its mix with the zero entries skipped by a select.
+template <int NP, int VEC>
+__device__ __forceinline__ void mix_rows(const float (&sM)[NP * NP], const float (&x)[NP][VEC],
+                                         float (&y)[NP][VEC], int n) {
+  // M is re-read from LDS as it is used: its NP^2 values are loop invariant, and hipcc would
+  // otherwise hoist all of them into VGPRs (NP = 16: 256 registers, spilling). An offset it
+  // cannot see through (always 0) keeps the broadcast reads inside the iteration.
+  int z = 0;
+  asm volatile("" : "+v"(z));
+  float probe = 0.0f;
+#pragma unroll
+  for (int j = 0; j < NP; ++j) {
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) probe = fmaf(x[j][v], 0.0f, probe);
+  }
+  if (__builtin_amdgcn_ballot_w64(probe != probe) == 0) {   // wave-uniform
+#pragma unroll
+    for (int i = 0; i < NP; ++i) {
+      if (i < n) {   // n is a kernel argument: a scalar branch per row
+        if constexpr (VEC % 2 == 0) {
+          f32x2 acc[VEC / 2];
+#pragma unroll
+          for (int v = 0; v < VEC / 2; ++v) acc[v] = f32x2{0.0f, 0.0f};
+#pragma unroll
+          for (int j = 0; j < NP; ++j) {
+            const float mij = sM[z + i * NP + j];
+            const f32x2 mm = {mij, mij};
+#pragma unroll
+            for (int v = 0; v < VEC / 2; ++v)
+              acc[v] = __builtin_elementwise_fma(mm, f32x2{x[j][2 * v], x[j][2 * v + 1]}, acc[v]);
+          }
+#pragma unroll
+          for (int v = 0; v < VEC / 2; ++v) {
+            y[i][2 * v] = acc[v].x;
+            y[i][2 * v + 1] = acc[v].y;
+          }
+        } else {
+#pragma unroll
+          for (int v = 0; v < VEC; ++v) y[i][v] = 0.0f;
+#pragma unroll
+          for (int j = 0; j < NP; ++j) {
+            const float mij = sM[z + i * NP + j];
+#pragma unroll
+            for (int v = 0; v < VEC; ++v) y[i][v] = fmaf(mij, x[j][v], y[i][v]);
+          }
+        }
+      } else {   // padding row: replaced by +inf in the caller
+#pragma unroll
+        for (int v = 0; v < VEC; ++v) y[i][v] = 0.0f;
+      }
+    }
+  } else {
+#pragma unroll
+    for (int i = 0; i < NP; ++i) {
+      if (i < n) {
+#pragma unroll
+        for (int v = 0; v < VEC; ++v) y[i][v] = 0.0f;
+#pragma unroll
+        for (int j = 0; j < NP; ++j) {
+          const float mij = sM[z + i * NP + j];
+#pragma unroll
+          for (int v = 0; v < VEC; ++v)
+            y[i][v] = mij != 0.0f ? fmaf(mij, x[j][v], y[i][v]) : y[i][v];
+        }
+      } else {
+#pragma unroll
+        for (int v = 0; v < VEC; ++v) y[i][v] = 0.0f;
+      }
+    }
+  }
+}
+
 // ----------------------------------------------------------------------------- sorted combine
-// fp32 rows (and the bf16 scalar tail): sort fp32 values. The rank window [lo, lo+cnt) is
-// wave-uniform (kernel arguments), so the per-rank test is a scalar branch, not a VALU select.
-template <typename T, int NP, int VEC, int OPT, bool NEAR = false>
+// fp32 rows, the bf16 scalar tail, and bf16 rows of the NEAR and MIX forms: sort fp32 values. The
+// rank window [lo, lo+cnt) is wave-uniform (kernel arguments), so the per-rank test is a scalar
+// branch, not a VALU select. MIX: the rows are mixed (mix_rows) between the loads and the
+// sanitising pass.
+//
+// The row offsets, the sanitising pass and the window mean are written out here (and the first
+// and the last again in the packed-key body and in near_combine's centre) rather than factored
+// into __forceinline__ helpers: a helper is simplified on its own before it is inlined, and each
+// of the three then moves registers or code in kernels that must not move -- the sanitising pass
+// over the whole array turns its selects into branches (fp32, NP = 8, 4 per lane, SGD: 3800 ->
+// 7312 bytes, 108 -> 112 VGPRs), the window mean moves 68 -> 65 VGPRs at fp32 NP = 4 and as
+// near_combine's centre 152 -> 162 at NP = 32, the row offsets move code size alone
+// (profiles/agg_dispatch/README.md).
+template <typename T, int NP, int VEC, int OPT, bool MIX, bool NEAR>
 __device__ __forceinline__ void agg_sorted_body(const SrcArgs& s, const UpdArgs& u, int64_t base,
-    int64_t nvec, int blk, int nblk) {
+    int64_t nvec, int blk, int nblk, const float* __restrict__ mix = nullptr) {
+  __shared__ float sM[MIX ? NP * NP : 1];
+  if constexpr (MIX) {
+    for (int k = threadIdx.x; k < NP * NP; k += kBlock) {
+      const int i = k / NP, j = k % NP;
+      sM[k] = (i < s.n && j < s.n) ? mix[i * s.n + j] : 0.0f;
+    }
+    __syncthreads();
+  }
   const T* X = reinterpret_cast<const T*>(s.X);
   int64_t roff[NP];
 #pragma unroll
@@ -207,10 +358,18 @@ __device__ __forceinline__ void agg_sorted_body(const SrcArgs& s, const UpdArgs&
   for (int64_t t = static_cast<int64_t>(blk) * kBlock + threadIdx.x; t < nvec; t += stride) {
     const int64_t e = t * VEC;
     float a[NP][VEC];
-#pragma unroll
-    for (int i = 0; i < NP; ++i) load_vec<T, VEC>(X + roff[i] + e, a[i]);
     OptState<VEC> st;
-    load_state<VEC>(u, OPT, base + e, st);
+    if constexpr (MIX) {
+      float x[NP][VEC];
+#pragma unroll
+      for (int i = 0; i < NP; ++i) load_vec<T, VEC>(X + roff[i] + e, x[i]);
+      load_state<VEC>(u, OPT, base + e, st);
+      mix_rows<NP, VEC>(sM, x, a, s.n);
+    } else {
+#pragma unroll
+      for (int i = 0; i < NP; ++i) load_vec<T, VEC>(X + roff[i] + e, a[i]);
+      load_state<VEC>(u, OPT, base + e, st);
+    }
 #pragma unroll
     for (int i = 0; i < NP; ++i) {
       const bool pad = i >= s.n;
@@ -309,144 +468,6 @@ __device__ __forceinline__ void agg_sorted_bf16_body(const SrcArgs& s, const Upd
   }
 }
 
-// ----------------------------------------------------------------------------- mixed sorted combine
-// A linear pre-mix of the rows ahead of the sort (nearest-neighbour mixing for the coordinate
-// rules): per coordinate y_i = sum_j M_ij x_j in fp32 (an fmaf chain in j order), then the
-// sanitising, network and rank window of agg_sorted_body on y. M (fp32 [n, n]) is staged once per
-// workgroup into LDS, zero-padded to NP x NP, and read back as broadcasts (every lane the same
-// address). x and y are both live during the mix, so VEC is chosen per NP to keep 2 NP VEC fp32
-// in registers (mixed_vec below); the mixed values are fp32, so bf16 rows take the fp32 network.
-//
-// "M_ij == 0 contributes nothing even where x_j is NaN / inf": with every loaded value finite a
-// zero entry adds an exact zero, so the fast path is plain (packed) FMAs. One extra FMA per loaded
-// value (x * 0 accumulates to NaN iff some x is non-finite) detects the other case, and a wave
-// that saw a non-finite value redoes its mix with the zero entries skipped by a select.
-template <int NP, int VEC>
-__device__ __forceinline__ void mix_rows(const float (&sM)[NP * NP], const float (&x)[NP][VEC],
-                                         float (&y)[NP][VEC], int n) {
-  // M is re-read from LDS as it is used: its NP^2 values are loop invariant, and hipcc would
-  // otherwise hoist all of them into VGPRs (NP = 16: 256 registers, spilling). An offset it
-  // cannot see through (always 0) keeps the broadcast reads inside the iteration.
-  int z = 0;
-  asm volatile("" : "+v"(z));
-  float probe = 0.0f;
-#pragma unroll
-  for (int j = 0; j < NP; ++j) {
-#pragma unroll
-    for (int v = 0; v < VEC; ++v) probe = fmaf(x[j][v], 0.0f, probe);
-  }
-  if (__builtin_amdgcn_ballot_w64(probe != probe) == 0) {   // wave-uniform
-#pragma unroll
-    for (int i = 0; i < NP; ++i) {
-      if (i < n) {   // n is a kernel argument: a scalar branch per row
-        if constexpr (VEC % 2 == 0) {
-          f32x2 acc[VEC / 2];
-#pragma unroll
-          for (int v = 0; v < VEC / 2; ++v) acc[v] = f32x2{0.0f, 0.0f};
-#pragma unroll
-          for (int j = 0; j < NP; ++j) {
-            const float mij = sM[z + i * NP + j];
-            const f32x2 mm = {mij, mij};
-#pragma unroll
-            for (int v = 0; v < VEC / 2; ++v)
-              acc[v] = __builtin_elementwise_fma(mm, f32x2{x[j][2 * v], x[j][2 * v + 1]}, acc[v]);
-          }
-#pragma unroll
-          for (int v = 0; v < VEC / 2; ++v) {
-            y[i][2 * v] = acc[v].x;
-            y[i][2 * v + 1] = acc[v].y;
-          }
-        } else {
-#pragma unroll
-          for (int v = 0; v < VEC; ++v) y[i][v] = 0.0f;
-#pragma unroll
-          for (int j = 0; j < NP; ++j) {
-            const float mij = sM[z + i * NP + j];
-#pragma unroll
-            for (int v = 0; v < VEC; ++v) y[i][v] = fmaf(mij, x[j][v], y[i][v]);
-          }
-        }
-      } else {   // padding row: replaced by +inf in the caller
-#pragma unroll
-        for (int v = 0; v < VEC; ++v) y[i][v] = 0.0f;
-      }
-    }
-  } else {
-#pragma unroll
-    for (int i = 0; i < NP; ++i) {
-      if (i < n) {
-#pragma unroll
-        for (int v = 0; v < VEC; ++v) y[i][v] = 0.0f;
-#pragma unroll
-        for (int j = 0; j < NP; ++j) {
-          const float mij = sM[z + i * NP + j];
-#pragma unroll
-          for (int v = 0; v < VEC; ++v)
-            y[i][v] = mij != 0.0f ? fmaf(mij, x[j][v], y[i][v]) : y[i][v];
-        }
-      } else {
-#pragma unroll
-        for (int v = 0; v < VEC; ++v) y[i][v] = 0.0f;
-      }
-    }
-  }
-}
-
-template <typename T, int NP, int VEC, int OPT, bool NEAR = false>
-__device__ __forceinline__ void agg_mixed_body(const SrcArgs& s, const UpdArgs& u,
-    const float* __restrict__ mix, int64_t base, int64_t nvec, int blk, int nblk) {
-  __shared__ float sM[NP * NP];
-  for (int k = threadIdx.x; k < NP * NP; k += kBlock) {
-    const int i = k / NP, j = k % NP;
-    sM[k] = (i < s.n && j < s.n) ? mix[i * s.n + j] : 0.0f;
-  }
-  __syncthreads();
-  const T* X = reinterpret_cast<const T*>(s.X);
-  int64_t roff[NP];
-#pragma unroll
-  for (int i = 0; i < NP; ++i) {
-    const int r = i < s.n ? i : s.n - 1;
-    roff[i] = static_cast<int64_t>(s.rows ? s.rows[r] : r) * s.ld + base;
-  }
-  const float inf = __builtin_inff();
-  const float inv = 1.0f / static_cast<float>(s.cnt);
-  const int64_t stride = static_cast<int64_t>(nblk) * kBlock;
-  for (int64_t t = static_cast<int64_t>(blk) * kBlock + threadIdx.x; t < nvec; t += stride) {
-    const int64_t e = t * VEC;
-    float x[NP][VEC];
-#pragma unroll
-    for (int i = 0; i < NP; ++i) load_vec<T, VEC>(X + roff[i] + e, x[i]);
-    OptState<VEC> st;
-    load_state<VEC>(u, OPT, base + e, st);
-    float a[NP][VEC];
-    mix_rows<NP, VEC>(sM, x, a, s.n);
-#pragma unroll
-    for (int i = 0; i < NP; ++i) {
-      const bool pad = i >= s.n;
-#pragma unroll
-      for (int v = 0; v < VEC; ++v) a[i][v] = (pad || a[i][v] != a[i][v]) ? inf : a[i][v];
-    }
-    sort_columns<float, NP, VEC>(a);
-    float g[VEC];
-    if constexpr (NEAR) {
-      near_combine<NP, VEC>(a, s, inv, g);
-    } else {
-#pragma unroll
-      for (int v = 0; v < VEC; ++v) g[v] = 0.0f;
-#pragma unroll
-      for (int i = 0; i < NP; ++i) {
-        if (i >= s.lo && i < s.lo + s.cnt) {
-#pragma unroll
-          for (int v = 0; v < VEC; ++v) g[v] += a[i][v];
-        }
-      }
-#pragma unroll
-      for (int v = 0; v < VEC; ++v) g[v] *= inv;
-    }
-    update_and_store<VEC>(u, OPT, base + e, g, st);
-  }
-}
-
 // ----------------------------------------------------------------------------- weighted combine
 template <typename T, int VEC, int OPT>
 __device__ __forceinline__ void agg_weighted_body(const SrcArgs& s, const UpdArgs& u, int64_t base,
@@ -501,44 +522,22 @@ __device__ __forceinline__ void agg_weighted_body(const SrcArgs& s, const UpdArg
   }
 }
 
-
 // ----------------------------------------------------------------------------- kernels
+// A mixed form's kernels take the matrix as one more argument after u: Mix = {MixPtr}; the other
+// forms' kernels take none: Mix = {}. Both kernels pick the body of form F themselves: one more
+// __forceinline__ layer between kernel and body moves code in the largest scalar-tail kernels
+// (NP = 64, no optimizer: up to 252 bytes and one VGPR).
+using MixPtr = const float* __restrict__;
+
 // Single segment (one bucket / one vector): grid-stride over nvec vectors.
-template <typename T, int NP, int VEC, int OPT>
-__global__ __launch_bounds__(kBlock) void agg_sorted_kernel(SrcArgs s, UpdArgs u, int64_t base,
-                                                            int64_t nvec) {
-  agg_sorted_body<T, NP, VEC, OPT>(s, u, base, nvec, blockIdx.x, gridDim.x);
-}
-template <int NP, int VEC, int OPT>
-__global__ __launch_bounds__(kBlock) void agg_sorted_bf16_kernel(SrcArgs s, UpdArgs u,
-                                                                 int64_t base, int64_t nvec) {
-  agg_sorted_bf16_body<NP, VEC, OPT>(s, u, base, nvec, blockIdx.x, gridDim.x);
-}
-template <typename T, int VEC, int OPT>
-__global__ __launch_bounds__(kBlock) void agg_weighted_kernel(SrcArgs s, UpdArgs u, int64_t base,
-                                                              int64_t nvec) {
-  agg_weighted_body<T, VEC, OPT>(s, u, base, nvec, blockIdx.x, gridDim.x);
-}
-
-template <typename T, int NP, int VEC, int OPT>
-__global__ __launch_bounds__(kBlock) void agg_mixed_kernel(SrcArgs s, UpdArgs u,
-                                                           const float* __restrict__ mix,
-                                                           int64_t base, int64_t nvec) {
-  agg_mixed_body<T, NP, VEC, OPT>(s, u, mix, base, nvec, blockIdx.x, gridDim.x);
-}
-
-// The nearest-to-centre forms (keep > 0) are kernels of their own, so the plain instantiations
-// above keep their code.
-template <typename T, int NP, int VEC, int OPT>
-__global__ __launch_bounds__(kBlock) void agg_near_kernel(SrcArgs s, UpdArgs u, int64_t base,
-                                                          int64_t nvec) {
-  agg_sorted_body<T, NP, VEC, OPT, true>(s, u, base, nvec, blockIdx.x, gridDim.x);
-}
-template <typename T, int NP, int VEC, int OPT>
-__global__ __launch_bounds__(kBlock) void agg_near_mixed_kernel(SrcArgs s, UpdArgs u,
-                                                                const float* __restrict__ mix,
-                                                                int64_t base, int64_t nvec) {
-  agg_mixed_body<T, NP, VEC, OPT, true>(s, u, mix, base, nvec, blockIdx.x, gridDim.x);
+template <class F, int NP, int VEC, int OPT, class... Mix>
+__global__ __launch_bounds__(kBlock) void agg_kernel(SrcArgs s, UpdArgs u, Mix... mix, int64_t base,
+                                                     int64_t nvec) {
+  using T = typename F::T;
+  const int blk = blockIdx.x, nblk = gridDim.x;
+  if constexpr (F::weighted) agg_weighted_body<T, VEC, OPT>(s, u, base, nvec, blk, nblk);
+  else if constexpr (F::packed(VEC)) agg_sorted_bf16_body<NP, VEC, OPT>(s, u, base, nvec, blk, nblk);
+  else agg_sorted_body<T, NP, VEC, OPT, F::mix, F::near>(s, u, base, nvec, blk, nblk, mix...);
 }
 
 // Several segments in ONE launch (the sharded engine's buckets: per-bucket worker matrices and
@@ -552,7 +551,10 @@ struct SegTable {
   void* pout[kMaxSegs];
 };
 
-__device__ __forceinline__ void seg_args(const SegTable& t, int sg, SrcArgs& s, UpdArgs& u) {
+// The shared rule and state bases (s, u) become those of segment sg: in the multi kernel, and on
+// the host for the per-segment fallback.
+__host__ __device__ __forceinline__ void seg_args(const SegTable& t, int sg, SrcArgs& s,
+                                                  UpdArgs& u) {
   s.X = t.X[sg];
   s.ld = t.ld[sg];
   const int64_t o = t.off[sg];
@@ -563,44 +565,66 @@ __device__ __forceinline__ void seg_args(const SegTable& t, int sg, SrcArgs& s, 
   u.param_out = t.pout[sg];
 }
 
-template <typename T, int NP, int VEC, int OPT>
-__global__ __launch_bounds__(kBlock) void agg_sorted_multi(SrcArgs s, UpdArgs u, SegTable t) {
+template <class F, int NP, int VEC, int OPT, class... Mix>
+__global__ __launch_bounds__(kBlock) void agg_multi(SrcArgs s, UpdArgs u, Mix... mix, SegTable t) {
   seg_args(t, blockIdx.y, s, u);
-  agg_sorted_body<T, NP, VEC, OPT>(s, u, 0, t.nvec[blockIdx.y], blockIdx.x, gridDim.x);
-}
-template <int NP, int VEC, int OPT>
-__global__ __launch_bounds__(kBlock) void agg_sorted_bf16_multi(SrcArgs s, UpdArgs u, SegTable t) {
-  seg_args(t, blockIdx.y, s, u);
-  agg_sorted_bf16_body<NP, VEC, OPT>(s, u, 0, t.nvec[blockIdx.y], blockIdx.x, gridDim.x);
-}
-template <typename T, int VEC, int OPT>
-__global__ __launch_bounds__(kBlock) void agg_weighted_multi(SrcArgs s, UpdArgs u, SegTable t) {
-  seg_args(t, blockIdx.y, s, u);
-  agg_weighted_body<T, VEC, OPT>(s, u, 0, t.nvec[blockIdx.y], blockIdx.x, gridDim.x);
-}
-
-template <typename T, int NP, int VEC, int OPT>
-__global__ __launch_bounds__(kBlock) void agg_mixed_multi(SrcArgs s, UpdArgs u,
-                                                          const float* __restrict__ mix,
-                                                          SegTable t) {
-  seg_args(t, blockIdx.y, s, u);
-  agg_mixed_body<T, NP, VEC, OPT>(s, u, mix, 0, t.nvec[blockIdx.y], blockIdx.x, gridDim.x);
-}
-
-template <typename T, int NP, int VEC, int OPT>
-__global__ __launch_bounds__(kBlock) void agg_near_multi(SrcArgs s, UpdArgs u, SegTable t) {
-  seg_args(t, blockIdx.y, s, u);
-  agg_sorted_body<T, NP, VEC, OPT, true>(s, u, 0, t.nvec[blockIdx.y], blockIdx.x, gridDim.x);
-}
-template <typename T, int NP, int VEC, int OPT>
-__global__ __launch_bounds__(kBlock) void agg_near_mixed_multi(SrcArgs s, UpdArgs u,
-                                                               const float* __restrict__ mix,
-                                                               SegTable t) {
-  seg_args(t, blockIdx.y, s, u);
-  agg_mixed_body<T, NP, VEC, OPT, true>(s, u, mix, 0, t.nvec[blockIdx.y], blockIdx.x, gridDim.x);
+  using T = typename F::T;
+  const int64_t nvec = t.nvec[blockIdx.y];
+  const int blk = blockIdx.x, nblk = gridDim.x;
+  if constexpr (F::weighted) agg_weighted_body<T, VEC, OPT>(s, u, 0, nvec, blk, nblk);
+  else if constexpr (F::packed(VEC)) agg_sorted_bf16_body<NP, VEC, OPT>(s, u, 0, nvec, blk, nblk);
+  else agg_sorted_body<T, NP, VEC, OPT, F::mix, F::near>(s, u, 0, nvec, blk, nblk, mix...);
 }
 
 // ----------------------------------------------------------------------------- dispatch
+// Run-time values to compile-time ones: each calls fn with a std::integral_constant (with_form:
+// with a Form). These are the only ladder over n and the only switch over opt in the file.
+template <int V> using IC = std::integral_constant<int, V>;
+
+template <class Fn>
+static void with_np(int n, Fn&& fn) {   // the least power of two >= n; Form::np maps it further
+  if (n <= 2) fn(IC<2>{});
+  else if (n <= 4) fn(IC<4>{});
+  else if (n <= 8) fn(IC<8>{});
+  else if (n <= 16) fn(IC<16>{});
+  else if (n <= 32) fn(IC<32>{});
+  else fn(IC<64>{});
+}
+
+template <class Fn>
+static void with_opt(int opt, Fn&& fn) {
+  switch (opt) {
+    case OPT_NONE: fn(IC<OPT_NONE>{}); break;
+    case OPT_SGD: fn(IC<OPT_SGD>{}); break;
+    default: fn(IC<OPT_ADAM>{}); break;
+  }
+}
+
+template <class Fn>
+static void with_form(int dtype, int combine, bool mix, bool near, Fn&& fn) {
+  auto rows = [&](auto t) {
+    using T = decltype(t);
+    if (combine == CMB_WEIGHTED) fn(Form<T, false, false, true>{});
+    else if (mix && near) fn(Form<T, true, true>{});
+    else if (mix) fn(Form<T, false, true>{});
+    else if (near) fn(Form<T, true, false>{});
+    else fn(Form<T, false, false>{});
+  };
+  if (dtype == DT_BF16) rows(bf16{});
+  else rows(float{});
+}
+
+// fn(IC<NP>, IC<VEC>, IC<OPT>) of form F for n rows on the vector or the scalar path.
+template <class F, bool VECTOR, class Fn>
+static void with_kernel(int n, int opt, Fn&& fn) {
+  with_np(n, [&](auto np) {
+    with_opt(opt, [&](auto o) {
+      constexpr int NP = F::np(decltype(np)::value);
+      fn(IC<NP>{}, IC<F::vec(NP, VECTOR)>{}, o);
+    });
+  });
+}
+
 // CML_AGG_GRID_CAP: the most workgroups of an update launch (default 0 = no cap: one vector per
 // thread, the form that streams fastest on MI355X -- tools/diag/hbm_copy.py: a one-pass copy
 // 6.0-6.6 TB/s vs 4.7-5.7 for grid-stride loops; the fused rule + SGD update 8.6-12.7 % faster
@@ -617,273 +641,75 @@ static inline int grid_for(int64_t nvec) {
   return static_cast<int>(b);
 }
 
-template <typename T, int NP, int VEC, bool NEAR = false>
-static void launch_sorted_np(int opt, const SrcArgs& s, const UpdArgs& u, int64_t base,
-                             int64_t nvec, hipStream_t st) {
-  const int g = grid_for(nvec);
-  if constexpr (NEAR) {   // fp32 network for both row types
-    switch (opt) {
-      case OPT_NONE: agg_near_kernel<T, NP, VEC, OPT_NONE><<<g, kBlock, 0, st>>>(s, u, base, nvec); break;
-      case OPT_SGD: agg_near_kernel<T, NP, VEC, OPT_SGD><<<g, kBlock, 0, st>>>(s, u, base, nvec); break;
-      default: agg_near_kernel<T, NP, VEC, OPT_ADAM><<<g, kBlock, 0, st>>>(s, u, base, nvec); break;
-    }
-  } else if constexpr (sizeof(T) == 2 && VEC >= 2) {   // packed-key path
-    switch (opt) {
-      case OPT_NONE: agg_sorted_bf16_kernel<NP, VEC, OPT_NONE><<<g, kBlock, 0, st>>>(s, u, base, nvec); break;
-      case OPT_SGD: agg_sorted_bf16_kernel<NP, VEC, OPT_SGD><<<g, kBlock, 0, st>>>(s, u, base, nvec); break;
-      default: agg_sorted_bf16_kernel<NP, VEC, OPT_ADAM><<<g, kBlock, 0, st>>>(s, u, base, nvec); break;
-    }
-  } else {
-    switch (opt) {
-      case OPT_NONE: agg_sorted_kernel<T, NP, VEC, OPT_NONE><<<g, kBlock, 0, st>>>(s, u, base, nvec); break;
-      case OPT_SGD: agg_sorted_kernel<T, NP, VEC, OPT_SGD><<<g, kBlock, 0, st>>>(s, u, base, nvec); break;
-      default: agg_sorted_kernel<T, NP, VEC, OPT_ADAM><<<g, kBlock, 0, st>>>(s, u, base, nvec); break;
-    }
-  }
-}
-
-// Vector width per padded row count (sorted_vec below must agree): bf16 keys take half a VGPR
-// per value, so bf16 keeps 16 B loads up to NP = 32; NP = 64 drops to 2 elements per lane.
-template <typename T, bool VECTOR>
-static void launch_sorted(int opt, const SrcArgs& s, const UpdArgs& u, int64_t base, int64_t D,
-                          hipStream_t st) {
-  // D: number of elements; VECTOR: D is a multiple of sorted_vec() and all pointers aligned.
-  const int n = s.n;
-  constexpr bool BF = sizeof(T) == 2;
-  if constexpr (VECTOR) {
-    if (n <= 2) launch_sorted_np<T, 2, BF ? 8 : 4>(opt, s, u, base, D / (BF ? 8 : 4), st);
-    else if (n <= 4) launch_sorted_np<T, 4, BF ? 8 : 4>(opt, s, u, base, D / (BF ? 8 : 4), st);
-    else if (n <= 8) launch_sorted_np<T, 8, BF ? 8 : 4>(opt, s, u, base, D / (BF ? 8 : 4), st);
-    else if (n <= 16) launch_sorted_np<T, 16, BF ? 8 : 4>(opt, s, u, base, D / (BF ? 8 : 4), st);
-    else if (n <= 32) launch_sorted_np<T, 32, BF ? 8 : 4>(opt, s, u, base, D / (BF ? 8 : 4), st);
-    else launch_sorted_np<T, 64, 2>(opt, s, u, base, D / 2, st);
-  } else {
-    if (n <= 2) launch_sorted_np<T, 2, 1>(opt, s, u, base, D, st);
-    else if (n <= 4) launch_sorted_np<T, 4, 1>(opt, s, u, base, D, st);
-    else if (n <= 8) launch_sorted_np<T, 8, 1>(opt, s, u, base, D, st);
-    else if (n <= 16) launch_sorted_np<T, 16, 1>(opt, s, u, base, D, st);
-    else if (n <= 32) launch_sorted_np<T, 32, 1>(opt, s, u, base, D, st);
-    else launch_sorted_np<T, 64, 1>(opt, s, u, base, D, st);
-  }
-}
-
-// Nearest-to-centre combine: fp32 values for both row types plus the copy of the low half
-// (1.5 NP VEC live fp32). bf16 rows keep 16 B loads up to NP = 4 only: at NP = 8, 8 elements per
-// lane take 172-206 VGPRs (2 waves per SIMD) and ran 1.13-1.21x the plain median kernel, 4
-// elements per lane 86-121 VGPRs (4-5 waves) and 0.98-1.02x. At NP = 16 / 32, 2 elements per lane
-// ran 9-12 % / 25-26 % faster than 4 (bf16 rows; fp32 rows take the same widths, not timed).
-// All in profiles/meamed/README.md.
-static int near_vec(int dtype, int n) {
-  if (n > 8) return 2;
-  return (dtype == DT_BF16 && n <= 4) ? 8 : 4;
-}
-
-template <typename T, bool VECTOR>
-static void launch_near(int opt, const SrcArgs& s, const UpdArgs& u, int64_t base, int64_t D,
-                        hipStream_t st) {
-  // D: number of elements; VECTOR: D is a multiple of near_vec() and all pointers aligned.
-  const int n = s.n;
-  constexpr int V8 = sizeof(T) == 2 ? 8 : 4;
-  if constexpr (VECTOR) {
-    if (n <= 2) launch_sorted_np<T, 2, V8, true>(opt, s, u, base, D / V8, st);
-    else if (n <= 4) launch_sorted_np<T, 4, V8, true>(opt, s, u, base, D / V8, st);
-    else if (n <= 8) launch_sorted_np<T, 8, 4, true>(opt, s, u, base, D / 4, st);
-    else if (n <= 16) launch_sorted_np<T, 16, 2, true>(opt, s, u, base, D / 2, st);
-    else if (n <= 32) launch_sorted_np<T, 32, 2, true>(opt, s, u, base, D / 2, st);
-    else launch_sorted_np<T, 64, 2, true>(opt, s, u, base, D / 2, st);
-  } else {
-    if (n <= 2) launch_sorted_np<T, 2, 1, true>(opt, s, u, base, D, st);
-    else if (n <= 4) launch_sorted_np<T, 4, 1, true>(opt, s, u, base, D, st);
-    else if (n <= 8) launch_sorted_np<T, 8, 1, true>(opt, s, u, base, D, st);
-    else if (n <= 16) launch_sorted_np<T, 16, 1, true>(opt, s, u, base, D, st);
-    else if (n <= 32) launch_sorted_np<T, 32, 1, true>(opt, s, u, base, D, st);
-    else launch_sorted_np<T, 64, 1, true>(opt, s, u, base, D, st);
-  }
-}
-
-// Mixed sorted combine: elements per lane by padded row count. x and y (fp32) are live together,
-// 2 NP VEC VGPRs: 64 at NP <= 8 (NP = 4 keeps 16-B bf16 loads), 128 at NP = 16 / 32.
-static int mixed_np(int n) { return n <= 4 ? 4 : n <= 8 ? 8 : n <= 16 ? 16 : 32; }
-static int mixed_vec(int dtype, int n) {
-  const int np = mixed_np(n);
-  if (np == 4) return dtype == DT_BF16 ? 8 : 4;
-  return np <= 16 ? 4 : 2;
-}
-
-template <typename T, int NP, int VEC>
-static void launch_mixed_np(int opt, const SrcArgs& s, const UpdArgs& u, const float* mix,
-                            int64_t base, int64_t nvec, hipStream_t st) {
-  const int g = grid_for(nvec);
-  if (s.keep > 0) {
-    switch (opt) {
-      case OPT_NONE: agg_near_mixed_kernel<T, NP, VEC, OPT_NONE><<<g, kBlock, 0, st>>>(s, u, mix, base, nvec); break;
-      case OPT_SGD: agg_near_mixed_kernel<T, NP, VEC, OPT_SGD><<<g, kBlock, 0, st>>>(s, u, mix, base, nvec); break;
-      default: agg_near_mixed_kernel<T, NP, VEC, OPT_ADAM><<<g, kBlock, 0, st>>>(s, u, mix, base, nvec); break;
-    }
-    return;
-  }
-  switch (opt) {
-    case OPT_NONE: agg_mixed_kernel<T, NP, VEC, OPT_NONE><<<g, kBlock, 0, st>>>(s, u, mix, base, nvec); break;
-    case OPT_SGD: agg_mixed_kernel<T, NP, VEC, OPT_SGD><<<g, kBlock, 0, st>>>(s, u, mix, base, nvec); break;
-    default: agg_mixed_kernel<T, NP, VEC, OPT_ADAM><<<g, kBlock, 0, st>>>(s, u, mix, base, nvec); break;
-  }
-}
-
-template <typename T, bool VECTOR>
-static void launch_mixed(int opt, const SrcArgs& s, const UpdArgs& u, const float* mix,
-                         int64_t base, int64_t D, hipStream_t st) {
-  // D: number of elements; VECTOR: D is a multiple of mixed_vec() and all pointers aligned.
-  constexpr bool BF = sizeof(T) == 2;
-  const int np = mixed_np(s.n);
-  if constexpr (VECTOR) {
-    if (np == 4) launch_mixed_np<T, 4, BF ? 8 : 4>(opt, s, u, mix, base, D / (BF ? 8 : 4), st);
-    else if (np == 8) launch_mixed_np<T, 8, 4>(opt, s, u, mix, base, D / 4, st);
-    else if (np == 16) launch_mixed_np<T, 16, 4>(opt, s, u, mix, base, D / 4, st);
-    else launch_mixed_np<T, 32, 2>(opt, s, u, mix, base, D / 2, st);
-  } else {
-    if (np == 4) launch_mixed_np<T, 4, 1>(opt, s, u, mix, base, D, st);
-    else if (np == 8) launch_mixed_np<T, 8, 1>(opt, s, u, mix, base, D, st);
-    else if (np == 16) launch_mixed_np<T, 16, 1>(opt, s, u, mix, base, D, st);
-    else launch_mixed_np<T, 32, 1>(opt, s, u, mix, base, D, st);
-  }
-}
-
-template <typename T, int NP, int VEC>
-static void launch_mixed_multi_np(int opt, const SrcArgs& s, const UpdArgs& u, const float* mix,
-                                  const SegTable& t, dim3 g, hipStream_t st) {
-  if (s.keep > 0) {
-    switch (opt) {
-      case OPT_NONE: agg_near_mixed_multi<T, NP, VEC, OPT_NONE><<<g, kBlock, 0, st>>>(s, u, mix, t); break;
-      case OPT_SGD: agg_near_mixed_multi<T, NP, VEC, OPT_SGD><<<g, kBlock, 0, st>>>(s, u, mix, t); break;
-      default: agg_near_mixed_multi<T, NP, VEC, OPT_ADAM><<<g, kBlock, 0, st>>>(s, u, mix, t); break;
-    }
-    return;
-  }
-  switch (opt) {
-    case OPT_NONE: agg_mixed_multi<T, NP, VEC, OPT_NONE><<<g, kBlock, 0, st>>>(s, u, mix, t); break;
-    case OPT_SGD: agg_mixed_multi<T, NP, VEC, OPT_SGD><<<g, kBlock, 0, st>>>(s, u, mix, t); break;
-    default: agg_mixed_multi<T, NP, VEC, OPT_ADAM><<<g, kBlock, 0, st>>>(s, u, mix, t); break;
-  }
-}
-
-template <typename T, int VEC>
-static void launch_weighted(int opt, const SrcArgs& s, const UpdArgs& u, int64_t base, int64_t nvec,
-                            hipStream_t st) {
-  const int g = grid_for(nvec);
-  switch (opt) {
-    case OPT_NONE: agg_weighted_kernel<T, VEC, OPT_NONE><<<g, kBlock, 0, st>>>(s, u, base, nvec); break;
-    case OPT_SGD: agg_weighted_kernel<T, VEC, OPT_SGD><<<g, kBlock, 0, st>>>(s, u, base, nvec); break;
-    default: agg_weighted_kernel<T, VEC, OPT_ADAM><<<g, kBlock, 0, st>>>(s, u, base, nvec); break;
-  }
+// D elements from element base on; VECTOR: D is a multiple of F::vec and all pointers aligned.
+template <class F, bool VECTOR>
+static void launch(int opt, const SrcArgs& s, const UpdArgs& u, const float* mix, int64_t base,
+                   int64_t D, hipStream_t st) {
+  with_kernel<F, VECTOR>(s.n, opt, [&](auto np, auto vec, auto o) {
+    constexpr int NP = decltype(np)::value, VEC = decltype(vec)::value, OPT = decltype(o)::value;
+    const int64_t nvec = D / VEC;
+    const int g = grid_for(nvec);
+    if constexpr (F::mix) agg_kernel<F, NP, VEC, OPT, MixPtr><<<g, kBlock, 0, st>>>(s, u, mix, base, nvec);
+    else agg_kernel<F, NP, VEC, OPT><<<g, kBlock, 0, st>>>(s, u, base, nvec);
+  });
 }
 
 static inline bool aligned(const void* p, int bytes) {
   return p == nullptr || (reinterpret_cast<uintptr_t>(p) % bytes) == 0;
 }
 
-static int sorted_vec(int dtype, int n) {
-  if (n > 32) return 2;
-  return dtype == DT_BF16 ? 8 : 4;
+// The vector path needs every state pointer aligned to vec elements (and every row start, which
+// the callers check with the row pointer and stride of each segment).
+static bool state_aligned(const UpdArgs& u, const void* param_out, int vec) {
+  return aligned(u.master, vec * 4) && aligned(u.s1, vec * 4) && aligned(u.s2, vec * 4) &&
+         aligned(u.gout, vec * 4) && aligned(param_out, vec * (u.param_f32 ? 4 : 2));
 }
 
-template <typename T>
-static hipError_t agg_update_t(int combine, int opt, const SrcArgs& s, const UpdArgs& u, int64_t D,
-                               hipStream_t st, const float* mix = nullptr) {
+template <class F>
+static hipError_t agg_update_f(int opt, const SrcArgs& s, const UpdArgs& u, int64_t D,
+                               hipStream_t st, const float* mix) {
   if (D <= 0) return hipSuccess;
-  const int esz = sizeof(T);
-  const int dt = esz == 2 ? DT_BF16 : DT_F32;
-  const int vec = combine == CMB_WEIGHTED ? (esz == 2 ? 8 : 4)
-                  : mix ? mixed_vec(dt, s.n)
-                  : s.keep > 0 ? near_vec(dt, s.n) : sorted_vec(dt, s.n);
-  // The vector path needs every row start and every state pointer aligned to VEC elements.
-  bool ok = (s.ld % vec) == 0 && aligned(s.X, vec * esz) && aligned(u.master, vec * 4) &&
-            aligned(u.s1, vec * 4) && aligned(u.s2, vec * 4) && aligned(u.gout, vec * 4) &&
-            aligned(u.param_out, vec * (u.param_f32 ? 4 : 2));
-  int64_t Dv = ok ? (D / vec) * vec : 0;
-  if (Dv > 0) {
-    if (combine == CMB_WEIGHTED) {
-      if constexpr (sizeof(T) == 2) launch_weighted<T, 8>(opt, s, u, 0, Dv / 8, st);
-      else launch_weighted<T, 4>(opt, s, u, 0, Dv / 4, st);
-    } else if (mix) {
-      launch_mixed<T, true>(opt, s, u, mix, 0, Dv, st);
-    } else if (s.keep > 0) {
-      launch_near<T, true>(opt, s, u, 0, Dv, st);
-    } else {
-      launch_sorted<T, true>(opt, s, u, 0, Dv, st);
-    }
-  }
-  if (D > Dv) {  // scalar tail (or fully unaligned inputs)
-    if (combine == CMB_WEIGHTED) launch_weighted<T, 1>(opt, s, u, Dv, D - Dv, st);
-    else if (mix) launch_mixed<T, false>(opt, s, u, mix, Dv, D - Dv, st);
-    else if (s.keep > 0) launch_near<T, false>(opt, s, u, Dv, D - Dv, st);
-    else launch_sorted<T, false>(opt, s, u, Dv, D - Dv, st);
-  }
+  constexpr int esz = sizeof(typename F::T);
+  const int vec = F::vec(F::np(s.n), true);
+  const bool ok = (s.ld % vec) == 0 && aligned(s.X, vec * esz) && state_aligned(u, u.param_out, vec);
+  const int64_t Dv = ok ? (D / vec) * vec : 0;
+  if (Dv > 0) launch<F, true>(opt, s, u, mix, 0, Dv, st);
+  if (D > Dv) launch<F, false>(opt, s, u, mix, Dv, D - Dv, st);   // scalar tail (or unaligned inputs)
   return hipGetLastError();
 }
 
-template <typename T, int NP, int VEC, bool NEAR = false>
-static void launch_sorted_multi_np(int opt, const SrcArgs& s, const UpdArgs& u, const SegTable& t,
-                                   dim3 g, hipStream_t st) {
-  if constexpr (NEAR) {
-    switch (opt) {
-      case OPT_NONE: agg_near_multi<T, NP, VEC, OPT_NONE><<<g, kBlock, 0, st>>>(s, u, t); break;
-      case OPT_SGD: agg_near_multi<T, NP, VEC, OPT_SGD><<<g, kBlock, 0, st>>>(s, u, t); break;
-      default: agg_near_multi<T, NP, VEC, OPT_ADAM><<<g, kBlock, 0, st>>>(s, u, t); break;
-    }
-  } else if constexpr (sizeof(T) == 2 && VEC >= 2) {
-    switch (opt) {
-      case OPT_NONE: agg_sorted_bf16_multi<NP, VEC, OPT_NONE><<<g, kBlock, 0, st>>>(s, u, t); break;
-      case OPT_SGD: agg_sorted_bf16_multi<NP, VEC, OPT_SGD><<<g, kBlock, 0, st>>>(s, u, t); break;
-      default: agg_sorted_bf16_multi<NP, VEC, OPT_ADAM><<<g, kBlock, 0, st>>>(s, u, t); break;
-    }
-  } else {
-    switch (opt) {
-      case OPT_NONE: agg_sorted_multi<T, NP, VEC, OPT_NONE><<<g, kBlock, 0, st>>>(s, u, t); break;
-      case OPT_SGD: agg_sorted_multi<T, NP, VEC, OPT_SGD><<<g, kBlock, 0, st>>>(s, u, t); break;
-      default: agg_sorted_multi<T, NP, VEC, OPT_ADAM><<<g, kBlock, 0, st>>>(s, u, t); break;
-    }
-  }
+static void set_seg(SegTable& t, int i, const AggSeg& g, int vec) {
+  t.X[i] = g.X;
+  t.ld[i] = g.ld;
+  t.nvec[i] = g.D / vec;
+  t.off[i] = g.off;
+  t.pout[i] = g.param_out;
 }
 
-template <typename T>
-static hipError_t agg_update_multi_t(int combine, int opt, const SrcArgs& s, const UpdArgs& u,
+template <class F>
+static hipError_t agg_update_multi_f(int opt, const SrcArgs& s, const UpdArgs& u,
                                      const AggSeg* segs, int nseg, hipStream_t st,
-                                     const float* mix = nullptr) {
-  const int esz = sizeof(T);
-  const int dt = esz == 2 ? DT_BF16 : DT_F32;
-  const int vec = combine == CMB_WEIGHTED ? (esz == 2 ? 8 : 4)
-                  : mix ? mixed_vec(dt, s.n)
-                  : s.keep > 0 ? near_vec(dt, s.n) : sorted_vec(dt, s.n);
-  bool ok = nseg >= 1 && nseg <= kMaxSegs;
+                                     const float* mix) {
+  constexpr int esz = sizeof(typename F::T);
+  const int vec = F::vec(F::np(s.n), true);
+  bool ok = nseg <= kMaxSegs;
   SegTable t{};
   int64_t maxv = 0;
   for (int i = 0; ok && i < nseg; ++i) {
     const AggSeg& g = segs[i];
-    const int64_t o = g.off;
     ok = g.D > 0 && g.D % vec == 0 && (g.ld % vec) == 0 && aligned(g.X, vec * esz) &&
-         o % vec == 0 && aligned(u.master, vec * 4) && aligned(u.s1, vec * 4) &&
-         aligned(u.s2, vec * 4) && aligned(u.gout, vec * 4) &&
-         aligned(g.param_out, vec * (u.param_f32 ? 4 : 2));
-    t.X[i] = g.X;
-    t.ld[i] = g.ld;
-    t.nvec[i] = g.D / vec;
-    t.off[i] = o;
-    t.pout[i] = g.param_out;
+         g.off % vec == 0 && state_aligned(u, g.param_out, vec);
+    set_seg(t, i, g, vec);
     maxv = t.nvec[i] > maxv ? t.nvec[i] : maxv;
   }
   if (!ok) {   // per-segment launches (unaligned / ragged segments)
     for (int i = 0; i < nseg; ++i) {
+      SegTable one;
+      set_seg(one, 0, segs[i], vec);
       SrcArgs s1 = s;
-      s1.X = segs[i].X;
-      s1.ld = segs[i].ld;
       UpdArgs u1 = u;
-      const int64_t o = segs[i].off;
-      if (u1.master) u1.master += o;
-      if (u1.s1) u1.s1 += o;
-      if (u1.s2) u1.s2 += o;
-      if (u1.gout) u1.gout += o;
-      u1.param_out = segs[i].param_out;
-      hipError_t e = agg_update_t<T>(combine, opt, s1, u1, segs[i].D, st, mix);
+      seg_args(one, 0, s1, u1);
+      hipError_t e = agg_update_f<F>(opt, s1, u1, segs[i].D, st, mix);
       if (e != hipSuccess) return e;
     }
     return hipGetLastError();
@@ -892,45 +718,21 @@ static hipError_t agg_update_multi_t(int combine, int opt, const SrcArgs& s, con
   const int cap = 2048 / nseg;
   if (gx > cap) gx = cap < 1 ? 1 : cap;
   const dim3 g(static_cast<unsigned>(gx), static_cast<unsigned>(nseg));
-  if (combine == CMB_WEIGHTED) {
-    constexpr int V = sizeof(T) == 2 ? 8 : 4;
-    switch (opt) {
-      case OPT_NONE: agg_weighted_multi<T, V, OPT_NONE><<<g, kBlock, 0, st>>>(s, u, t); break;
-      case OPT_SGD: agg_weighted_multi<T, V, OPT_SGD><<<g, kBlock, 0, st>>>(s, u, t); break;
-      default: agg_weighted_multi<T, V, OPT_ADAM><<<g, kBlock, 0, st>>>(s, u, t); break;
-    }
-  } else if (mix) {
-    constexpr bool BF = sizeof(T) == 2;
-    const int np = mixed_np(s.n);
-    if (np == 4) launch_mixed_multi_np<T, 4, BF ? 8 : 4>(opt, s, u, mix, t, g, st);
-    else if (np == 8) launch_mixed_multi_np<T, 8, 4>(opt, s, u, mix, t, g, st);
-    else if (np == 16) launch_mixed_multi_np<T, 16, 4>(opt, s, u, mix, t, g, st);
-    else launch_mixed_multi_np<T, 32, 2>(opt, s, u, mix, t, g, st);
-  } else if (s.keep > 0) {
-    constexpr int V8 = sizeof(T) == 2 ? 8 : 4;
-    const int n = s.n;
-    if (n <= 2) launch_sorted_multi_np<T, 2, V8, true>(opt, s, u, t, g, st);
-    else if (n <= 4) launch_sorted_multi_np<T, 4, V8, true>(opt, s, u, t, g, st);
-    else if (n <= 8) launch_sorted_multi_np<T, 8, 4, true>(opt, s, u, t, g, st);
-    else if (n <= 16) launch_sorted_multi_np<T, 16, 2, true>(opt, s, u, t, g, st);
-    else if (n <= 32) launch_sorted_multi_np<T, 32, 2, true>(opt, s, u, t, g, st);
-    else launch_sorted_multi_np<T, 64, 2, true>(opt, s, u, t, g, st);
-  } else {
-    constexpr bool BF = sizeof(T) == 2;
-    const int n = s.n;
-    if (n <= 2) launch_sorted_multi_np<T, 2, BF ? 8 : 4>(opt, s, u, t, g, st);
-    else if (n <= 4) launch_sorted_multi_np<T, 4, BF ? 8 : 4>(opt, s, u, t, g, st);
-    else if (n <= 8) launch_sorted_multi_np<T, 8, BF ? 8 : 4>(opt, s, u, t, g, st);
-    else if (n <= 16) launch_sorted_multi_np<T, 16, BF ? 8 : 4>(opt, s, u, t, g, st);
-    else if (n <= 32) launch_sorted_multi_np<T, 32, BF ? 8 : 4>(opt, s, u, t, g, st);
-    else launch_sorted_multi_np<T, 64, 2>(opt, s, u, t, g, st);
-  }
+  with_kernel<F, true>(s.n, opt, [&](auto np, auto v, auto o) {
+    constexpr int NP = decltype(np)::value, VEC = decltype(v)::value, OPT = decltype(o)::value;
+    if constexpr (F::mix) agg_multi<F, NP, VEC, OPT, MixPtr><<<g, kBlock, 0, st>>>(s, u, mix, t);
+    else agg_multi<F, NP, VEC, OPT><<<g, kBlock, 0, st>>>(s, u, t);
+  });
   return hipGetLastError();
 }
 
-// keep: 0, or a sorted combine keeping at least half of the rows (near_combine's window needs
-// f = n - keep <= keep). keep == n is the plain mean of all n rows: the fixed window [0, n).
-static bool near_args(int combine, SrcArgs& s) {
+// The n, window, mix and keep checks of both entry points. keep: 0, or a sorted combine keeping at
+// least half of the rows (near_combine's window needs f = n - keep <= keep). keep == n is the
+// plain mean of all n rows: the fixed window [0, n).
+static bool check_rule(int combine, SrcArgs& s, const float* mix) {
+  if (s.n < 1 || s.n > kMaxRows) return false;
+  if (combine == CMB_SORTED && (s.cnt < 1 || s.lo < 0 || s.lo + s.cnt > s.n)) return false;
+  if (mix && (combine != CMB_SORTED || s.n > kMaxMixRows)) return false;
   if (s.keep == 0) return true;
   if (combine != CMB_SORTED || s.keep < 0 || s.keep > s.n || 2 * s.keep < s.n) return false;
   if (s.keep == s.n) {
@@ -944,27 +746,24 @@ static bool near_args(int combine, SrcArgs& s) {
 hipError_t launch_agg_update_multi(int dtype, int combine, int opt, const SrcArgs& src,
                                    const UpdArgs& upd, const AggSeg* segs, int nseg,
                                    hipStream_t stream, const float* mix) {
-  if (src.n < 1 || src.n > kMaxRows || nseg < 1) return hipErrorInvalidValue;
-  if (combine == CMB_SORTED && (src.cnt < 1 || src.lo < 0 || src.lo + src.cnt > src.n))
-    return hipErrorInvalidValue;
-  if (mix && (combine != CMB_SORTED || src.n > kMaxMixRows)) return hipErrorInvalidValue;
   SrcArgs s = src;
-  if (!near_args(combine, s)) return hipErrorInvalidValue;
-  if (dtype == DT_BF16)
-    return agg_update_multi_t<bf16>(combine, opt, s, upd, segs, nseg, stream, mix);
-  return agg_update_multi_t<float>(combine, opt, s, upd, segs, nseg, stream, mix);
+  if (!check_rule(combine, s, mix) || nseg < 1) return hipErrorInvalidValue;
+  hipError_t e = hipSuccess;
+  with_form(dtype, combine, mix != nullptr, s.keep > 0, [&](auto f) {
+    e = agg_update_multi_f<decltype(f)>(opt, s, upd, segs, nseg, stream, mix);
+  });
+  return e;
 }
 
 hipError_t launch_agg_update(int dtype, int combine, int opt, const SrcArgs& src,
                              const UpdArgs& upd, int64_t D, hipStream_t stream, const float* mix) {
-  if (src.n < 1 || src.n > kMaxRows) return hipErrorInvalidValue;
-  if (combine == CMB_SORTED && (src.cnt < 1 || src.lo < 0 || src.lo + src.cnt > src.n))
-    return hipErrorInvalidValue;
-  if (mix && (combine != CMB_SORTED || src.n > kMaxMixRows)) return hipErrorInvalidValue;
   SrcArgs s = src;
-  if (!near_args(combine, s)) return hipErrorInvalidValue;
-  if (dtype == DT_BF16) return agg_update_t<bf16>(combine, opt, s, upd, D, stream, mix);
-  return agg_update_t<float>(combine, opt, s, upd, D, stream, mix);
+  if (!check_rule(combine, s, mix)) return hipErrorInvalidValue;
+  hipError_t e = hipSuccess;
+  with_form(dtype, combine, mix != nullptr, s.keep > 0, [&](auto f) {
+    e = agg_update_f<decltype(f)>(opt, s, upd, D, stream, mix);
+  });
+  return e;
 }
 
 }  // namespace cml

@@ -328,7 +328,7 @@ def run_near_multi(dev, dt, n, f, centre, Ds, optname, seed, mix=None):
 
 
 def _near_vec(dt, n):
-    """Elements per lane of the nearest-to-centre kernels (near_vec, agg_update.hip)."""
+    """Elements per lane of the nearest-to-centre kernels (Form::vec, agg_update.hip)."""
     if n > 8:
         return 2
     return 8 if (dt == "bf16" and n <= 4) else 4
@@ -348,7 +348,7 @@ def test_near_multi(cuda, dt, n, f):
 @pytest.mark.parametrize("dt", ["bf16", "f32"])
 def test_near_mixed_multi(cuda, dt, n):
     f = (n - 1) // 3
-    vec = 8 if (dt == "bf16" and n <= 4) else (4 if n <= 16 else 2)    # mixed_vec
+    vec = 8 if (dt == "bf16" and n <= 4) else (4 if n <= 16 else 2)    # Form::vec, MIX
     run_near_multi(cuda, dt, n, f, "median", (4096, vec, 808, 520), "adamw", 5900 + n, mix="dense")
     run_near_multi(cuda, dt, n, f, "trimmed", (4096, 2051, 808, 520), "sgd_nesterov", 5910 + n,
                    mix="dense")
