@@ -11,6 +11,7 @@ from __future__ import annotations
 import argparse
 import dataclasses
 import json
+import math
 from dataclasses import dataclass, field
 from typing import Any, Dict, List, Optional
 
@@ -114,6 +115,19 @@ class OptimConfig:
                      over the honest workers' momenta. allgather / sharded topologies. Weight
                      decay stays on the server, outside the momentum. The rows are about
                      1 / (1 - momentum) larger than gradients: ``agg.tau`` is not rescaled
+    clip_norm        global-norm clipping of the AGGREGATE (0 = off: the fused step as it is).
+                     With clip_norm = c > 0 every step scales the aggregated gradient g -- the
+                     mean over workers or the rule's output, over all parameters of the model
+                     (all buckets; sharded topology: all ranks, one fp64 all-reduce) -- by
+                     min(1, c / (||g||_2 + 1e-6)) before weight decay, momentum and Adam see it:
+                     the arithmetic of ``torch.nn.utils.clip_grad_norm_``. The norm stays on
+                     the device (``engine.grad_stats``). A non-finite norm gives coefficient 0:
+                     the step applies a ZERO gradient (weight decay and the moments' decay still
+                     act) and counts the event in ``engine.grad_stats[2]``; no state is poisoned.
+                     Gossip: every rank clips its own local gradient. centered_clip: v0 is the
+                     unclipped aggregate. With ``worker_momentum`` the clipped quantity is the
+                     aggregate of the momenta (about 1 / (1 - momentum) the gradient scale);
+                     nothing is rescaled
     """
     name: str = "sgd"            # sgd | adam | adamw
     lr: float = 0.1
@@ -123,8 +137,12 @@ class OptimConfig:
     betas: tuple = (0.9, 0.999)
     eps: float = 1e-8
     worker_momentum: bool = False
+    clip_norm: float = 0.0
 
     def validate(self) -> None:
+        c = self.clip_norm
+        if isinstance(c, bool) or not isinstance(c, (int, float)) or not math.isfinite(c) or c < 0:
+            raise ValueError(f"optim.clip_norm must be a finite number >= 0 (got {c!r})")
         if not self.worker_momentum:
             return
         if self.name != "sgd":
@@ -138,6 +156,12 @@ class OptimConfig:
 
 @dataclass
 class TopologyConfig:
+    """Exchange topology and its overlap switches (one comment per field below).
+
+    ``early_update`` (gossip, one worker per rank: each bucket's optimizer step runs during
+    backward) is forced off while ``optim.clip_norm`` > 0: the update of the first bucket would
+    need the gradient norm over all of them. The engine logs the switch once.
+    """
     kind: str = "sharded"        # allreduce | allgather | sharded | gossip
     bucket_mb: float = 64.0      # bucket size in MB of gradient (bf16 on the wire)
     comm_dtype: str = "bf16"     # dtype of exchanged gradients
@@ -148,6 +172,8 @@ class TopologyConfig:
     gossip_clip: float = 0.0     # 0 disables neighbour-delta clipping
     gossip_async: bool = False   # delayed gossip: exchange overlaps the next step's compute
     early_update: bool = True    # gossip, 1 local worker: per-bucket optimizer step in backward
+                                 # (forced off while optim.clip_norm > 0: the update of the first
+                                 # bucket needs the norm over all of them)
     param_prefetch: bool = True  # sharded: bf16 parameter all-gather overlaps the next forward
     early_gram: bool = True      # Gram-space rules: per-bucket Gram as each exchange lands
     gram_lag: int = 1            # GPU runs: bucket b's Gram is enqueued on the compute stream at

@@ -519,3 +519,57 @@ def worker_momentum(rows: torch.Tensor, mom: torch.Tensor, beta: float) -> None:
         raise ValueError(f"worker_momentum: rows {tuple(rows.shape)} {rows.dtype} against mom "
                          f"{tuple(mom.shape)} {mom.dtype}")
     ref.worker_momentum(rows, mom, beta)
+
+
+# --------------------------------------------------------------------------- global-norm clipping
+CLIP_STATS = ref.CLIP_STATS   # fp64 elements of a clipping stats tensor: [norm, coef, non-finite
+                              # norms seen so far, squared norm]
+
+
+def sq_norm_workspace(segments, device=None) -> torch.Tensor:
+    """An fp64 workspace large enough for ``sq_norm`` over these segments (one partial per
+    workgroup; allocate once and reuse while the segment lengths stay the same)."""
+    segments = list(segments)
+    if segments and segments[0].is_cuda:
+        n = lib().sq_norm_workspace(segments[0].dtype == torch.bfloat16,
+                                    [int(s.numel()) for s in segments])
+        return torch.empty(max(int(n), 1), dtype=torch.float64, device=segments[0].device)
+    return torch.empty(1, dtype=torch.float64, device=device or "cpu")
+
+
+def sq_norm(segments, scale: float, work: Optional[torch.Tensor], out: torch.Tensor,
+            grid_cap: int = 0) -> torch.Tensor:
+    """out[0] (fp64) = sum over every element x of the segments of (float(x) * scale)^2
+    (``reference.sq_norm``). ``segments``: contiguous 1-D tensors of one dtype (bf16 / fp32) on
+    one device. GPU: fp64 per-workgroup partials into ``work`` (``sq_norm_workspace``; None
+    allocates one) summed in index order, no atomics: the same data gives the same bits."""
+    segments = [s.reshape(-1) for s in segments]
+    if not segments:
+        raise ValueError("sq_norm: no segments")
+    if segments[0].is_cuda:
+        if work is None:
+            work = sq_norm_workspace(segments)
+        lib().sq_norm(segments, float(scale), work, out, grid_cap)
+        return out
+    out.reshape(-1)[0] = ref.sq_norm(segments, scale)
+    return out
+
+
+def clip_coef(norm2: torch.Tensor, max_norm: float, base: float, w_out: torch.Tensor,
+              stats: torch.Tensor, reduced: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """w_out[0] (fp32) = base * min(1, max_norm / (sqrt(s) + 1e-6)) with s = ``reduced[0]`` when
+    given (the squared norm all-reduced over ranks), else ``norm2[0]``; ``stats`` (fp64
+    [CLIP_STATS]) = [norm, coef, += 1 when s is not finite (then coef = 0), s]
+    (``reference.clip_coef``). Nothing is read back to the host on the GPU path."""
+    if max_norm < 0:
+        raise ValueError(f"clip_coef: max_norm must not be negative (got {max_norm})")
+    if norm2.is_cuda:
+        lib().clip_coef(norm2, float(max_norm), float(base), w_out, stats, reduced)
+        return w_out
+    s = reduced if reduced is not None else norm2
+    w, norm, coef, bad = ref.clip_coef(s, max_norm, base)
+    w_out.reshape(-1)[0] = w
+    st = stats.reshape(-1)
+    st[0], st[1], st[3] = norm, coef, s.reshape(-1)[0]
+    st[2] += bad
+    return w_out

@@ -458,5 +458,38 @@ def worker_momentum(rows: torch.Tensor, mom: torch.Tensor, beta: float) -> None:
     rows.copy_(mom.to(rows.dtype))
 
 
+# --------------------------------------------------------------------------- global-norm clipping
+
+CLIP_STATS = 4   # [norm, coef, count of non-finite norms, squared norm] (fp64)
+
+
+def sq_norm(segments, scale: float = 1.0) -> torch.Tensor:
+    """fp64 scalar: sum over every element x of every segment of (float(x) * scale)^2. The product
+    is rounded to fp32 (what the update's fp32 multiply gives), the square and the sum are fp64
+    (the definition of ``sq_norm_partial``, csrc/kernels/clip_norm.hip)."""
+    sc = torch.tensor(scale, dtype=torch.float32)
+    tot = torch.zeros((), dtype=torch.float64)
+    for s in segments:
+        v = (s.detach().reshape(-1).float().cpu() * sc).double()
+        tot = tot + (v * v).sum()
+    return tot
+
+
+def clip_coef(norm2: torch.Tensor, max_norm: float, base: float = 1.0):
+    """(w, norm, coef, bad) of global-norm clipping from the squared norm (fp64 arithmetic):
+    norm = sqrt(norm2), coef = min(1, max_norm / (norm + 1e-6)) -- the arithmetic of
+    ``torch.nn.utils.clip_grad_norm_`` -- and w = fp32(fp32(base) * coef), the weight the update
+    multiplies the gradient by. A non-finite norm2 gives coef = 0 and bad = 1 (a zero gradient
+    instead of a poisoned state; ``clip_finalize``, csrc/kernels/clip_norm.hip)."""
+    s = norm2.detach().double().reshape(-1)[0].cpu()
+    ok = bool(torch.isfinite(s)) and float(s) >= 0.0
+    norm = s.sqrt() if ok else s
+    coef = torch.zeros((), dtype=torch.float64)
+    if ok:
+        coef = torch.clamp(max_norm / (norm + 1e-6), max=1.0)
+    w = (torch.tensor(base, dtype=torch.float32).double() * coef).float()
+    return w, norm, coef, int(not ok)
+
+
 __all__ = [n for n in dir() if not n.startswith("_") and n not in ("math", "torch", "Optional",
                                                                      "Tuple", "annotations")]

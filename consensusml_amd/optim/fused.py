@@ -13,6 +13,15 @@ the "aggregate" is the gradient itself), instead of a kernel chain per parameter
   * bf16 / fp16 parameters keep an fp32 master copy in the optimizer and are rewritten from it
     in the same pass; fp32 parameters are updated in place
   * ``grad_scale``: gradients are multiplied by it inside the kernel (AMP un-scaling)
+  * ``max_grad_norm`` (constructor keyword, 0 = off): global-norm clipping as
+    ``torch.nn.utils.clip_grad_norm_(model.parameters(), max_grad_norm)`` ahead of ``step()``
+    would do it. The norm is taken over ALL flat buffers of all param groups, after
+    ``grad_scale``, on the device (``csrc/kernels/clip_norm.hip``: fp64 partials, fixed order),
+    and the coefficient min(1, max_grad_norm / (norm + 1e-6)) reaches the update kernels as a
+    device weight: no host read, no synchronisation. ``grad_stats`` (fp64 [4] on the device)
+    holds [norm, coefficient, steps with a non-finite norm, squared norm] of the last step. A
+    non-finite norm gives coefficient 0: that step applies a ZERO gradient (weight decay and
+    the moments' decay still act) instead of writing NaN into the state
 
 State is exposed the torch.optim way: ``self.state[p]`` holds views into the flat state
 buffers under torch's keys (``momentum_buffer`` / ``exp_avg``, ``exp_avg_sq``, ``step``), plus
@@ -33,6 +42,7 @@ from typing import Dict, List, Optional, Tuple
 
 import torch
 
+from ..ops import kernels as K
 from ..ops.kernels import OptArgs, agg_update
 
 ALIGN = 8        # elements: every parameter starts 16-byte aligned in its flat buffer
@@ -92,8 +102,13 @@ class _FusedBase(torch.optim.Optimizer):
     _kind = "sgd"
     _state_keys: Tuple[str, ...] = ()
 
-    def __init__(self, params, defaults):
+    def __init__(self, params, defaults, max_grad_norm: float = 0.0):
+        if not (isinstance(max_grad_norm, (int, float)) and 0 <= max_grad_norm < float("inf")):
+            raise ValueError(f"max_grad_norm must be a finite number >= 0 (got {max_grad_norm!r})")
         super().__init__(params, defaults)
+        self.max_grad_norm = float(max_grad_norm)
+        self.grad_stats: Optional[torch.Tensor] = None
+        self._clip_bufs = None
         self._flats: List[List[_Flat]] = []
         for group in self.param_groups:
             by: Dict[Tuple[torch.device, torch.dtype], List[torch.nn.Parameter]] = {}
@@ -174,17 +189,51 @@ class _FusedBase(torch.optim.Optimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
+        for fl in self.flat_buffers():
+            fl.sync_foreign_grads()
+        # max_grad_norm: the device weight grad_scale * coefficient replaces the host-side scale
+        w = self._clip_weight(grad_scale) if self.max_grad_norm > 0 else None
         for group, flats in zip(self.param_groups, self._flats):
             group["step"] += 1
             o = self._opt_args(group, group["step"])
-            o.gscale = grad_scale
+            o.gscale = grad_scale if w is None else 1.0
             for fl in flats:
-                fl.sync_foreign_grads()
                 s1 = fl.states[0] if fl.states else None
                 s2 = fl.states[1] if len(fl.states) > 1 else None
-                agg_update(fl.grad[None], combine="weighted", n=1, opt=o, master=fl.master,
+                agg_update(fl.grad[None], combine="weighted", w=w, n=1, opt=o, master=fl.master,
                            s1=s1, s2=s2, param_out=fl.param if fl.lowp else None)
         return loss
+
+    def _clip_weight(self, grad_scale: float) -> Optional[torch.Tensor]:
+        """fp32 [1] on the device: grad_scale * min(1, max_grad_norm / (norm + 1e-6)), norm = the
+        L2 norm of grad_scale * (every flat gradient buffer of every param group)."""
+        flats = self.flat_buffers()
+        if not flats:
+            return None
+        dev = flats[0].grad.device
+        if any(fl.grad.device != dev for fl in flats):
+            raise ValueError("max_grad_norm needs all parameters on one device")
+        if self._clip_bufs is None:
+            by: Dict[torch.dtype, List[torch.Tensor]] = {}
+            for fl in flats:    # one sq_norm per gradient dtype (bf16 / fp32; fp16: via fp32)
+                by.setdefault(fl.grad.dtype, []).append(fl.grad)
+            parts = [(segs, K.sq_norm_workspace(segs, dev)) for segs in by.values()
+                     if segs[0].dtype != torch.float16]
+            f16 = by.get(torch.float16, [])
+            self._clip_bufs = (parts, f16,
+                               torch.zeros(len(parts) + 1, dtype=torch.float64, device=dev),
+                               torch.zeros(1, dtype=torch.float64, device=dev),
+                               torch.zeros(1, dtype=torch.float32, device=dev))
+            self.grad_stats = torch.zeros(K.CLIP_STATS, dtype=torch.float64, device=dev)
+        parts, f16, n2, tot, w = self._clip_bufs
+        for k, (segs, work) in enumerate(parts):
+            K.sq_norm(segs, grad_scale, work, n2[k:k + 1])
+        if f16:
+            f32 = [g.float() for g in f16]
+            K.sq_norm(f32, grad_scale, None, n2[len(parts):])
+        torch.sum(n2, 0, keepdim=True, out=tot)
+        K.clip_coef(tot, self.max_grad_norm, grad_scale, w, self.grad_stats)
+        return w
 
     def flat_buffers(self) -> List[_Flat]:
         return [fl for flats in self._flats for fl in flats]
@@ -196,11 +245,11 @@ class FusedSGD(_FusedBase):
     _state_keys = ("momentum_buffer",)
 
     def __init__(self, params, lr: float = 1e-3, momentum: float = 0.0,
-                 weight_decay: float = 0.0, nesterov: bool = False):
+                 weight_decay: float = 0.0, nesterov: bool = False, max_grad_norm: float = 0.0):
         if nesterov and momentum <= 0:
             raise ValueError("Nesterov momentum requires a momentum")
         super().__init__(params, dict(lr=lr, momentum=momentum, weight_decay=weight_decay,
-                                      nesterov=nesterov))
+                                      nesterov=nesterov), max_grad_norm=max_grad_norm)
 
     def _opt_args(self, group, step):
         return OptArgs(kind="sgd", lr=group["lr"], momentum=group["momentum"],
@@ -214,9 +263,9 @@ class FusedAdamW(_FusedBase):
     _state_keys = ("exp_avg", "exp_avg_sq")
 
     def __init__(self, params, lr: float = 1e-3, betas: Tuple[float, float] = (0.9, 0.999),
-                 eps: float = 1e-8, weight_decay: float = 1e-2):
+                 eps: float = 1e-8, weight_decay: float = 1e-2, max_grad_norm: float = 0.0):
         super().__init__(params, dict(lr=lr, betas=tuple(betas), eps=eps,
-                                      weight_decay=weight_decay))
+                                      weight_decay=weight_decay), max_grad_norm=max_grad_norm)
 
     def _opt_args(self, group, step):
         b1, b2 = group["betas"]
@@ -229,8 +278,9 @@ class FusedAdam(FusedAdamW):
     _kind = "adam"
 
     def __init__(self, params, lr: float = 1e-3, betas: Tuple[float, float] = (0.9, 0.999),
-                 eps: float = 1e-8, weight_decay: float = 0.0):
-        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
+                 eps: float = 1e-8, weight_decay: float = 0.0, max_grad_norm: float = 0.0):
+        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
+                         max_grad_norm=max_grad_norm)
 
 
 def build_optimizer(name: str, params, **kw) -> torch.optim.Optimizer:

@@ -26,10 +26,25 @@ Topologies:
 
 Workers = ranks x virtual_workers (micro-batches whose gradients are kept separately), so the
 robust rules can be exercised at n = 8 on a single GPU.
+
+Global-norm clipping (optim.clip_norm = c > 0): the norm of the aggregate g is a dependency on
+every coordinate, so the fused rule + optimizer pass becomes three stages, all on the device:
+  1. materialise   the rule kernels with no optimizer write the fp32 aggregate into ``gout``
+                   (1 / N of the model in the sharded topology)
+  2. norm          ops.kernels.sq_norm (fp64 partials, fixed order) -> sharded, N > 1: ONE
+                   all-reduce of the fp64 scalar -> ops.kernels.clip_coef writes the DEVICE weight
+                   w_clip = min(1, c / (||g|| + 1e-6)) and ``grad_stats``
+  3. update        the weighted kernel over the one fp32 row ``gout`` with w = w_clip
+Where the update already reads a single row (allreduce; gossip with one worker per rank) stage 1
+is skipped: the norm is taken of that row times the step's gradient scale and the update runs on
+it with w_clip = scale * coefficient. The coefficient never reaches the host. With
+``optim.worker_momentum`` the rows are momenta, so the clipped quantity is the aggregate of the
+momenta; centered clipping keeps the UNCLIPPED aggregate as its v0.
 """
 from __future__ import annotations
 
 import contextlib
+import logging
 import math
 
 import numpy as np
@@ -50,6 +65,7 @@ from .flat import Bucket, FlatModel
 
 
 GRAM_RULES = ("krum", "multi_krum", "geomed", "centered_clip", "bulyan")
+_log = logging.getLogger(__name__)
 
 
 def gossip_peers(graph: str, N: int, r: int, t: int, ring_weights=(1 / 3, 1 / 3, 1 / 3)):
@@ -186,9 +202,24 @@ class ConsensusEngine:
         # [centered-Gram row, non-finite rows of the previous pass] (weights.hip guard state)
         self.center = torch.zeros(2, dtype=torch.int32, device=dev)
         self.have_center = False    # self.center holds a medoid from an earlier step
+        # optim.clip_norm: global-norm clipping of the aggregate (module docstring). The direct
+        # path needs no aggregate buffer: the update reads one gradient row anyway.
+        self.clip_norm = float(cfg.optim.clip_norm)
+        self.clip = self.clip_norm > 0
+        self._clip_direct = self.topo == "allreduce" or (self.topo == "gossip" and self.V == 1)
         self.gout = None
-        if self.rule == "centered_clip":
+        if self.rule == "centered_clip" or (self.clip and not self._clip_direct):
             self.gout = torch.zeros(self.state_len, dtype=torch.float32, device=dev)
+        # [norm of the aggregate, clipping coefficient, steps whose norm was not finite (their
+        # coefficient is 0: a zero gradient), squared norm] of the last step, fp64 on the device
+        self.grad_stats = (torch.zeros(K.CLIP_STATS, dtype=torch.float64, device=dev)
+                           if self.clip else None)
+        self.w_clip = torch.zeros(1, dtype=torch.float32, device=dev) if self.clip else None
+        self._norm2 = torch.zeros(1, dtype=torch.float64, device=dev) if self.clip else None
+        self._norm2_red = (torch.zeros(1, dtype=torch.float64, device=dev)
+                           if self.clip and self.topo == "sharded" and self.group_active
+                           and self.N > 1 else None)
+        self._clip_work: Optional[torch.Tensor] = None
 
         # -------------------------------------------------- gradient capture + overlap hooks
         # Copy-on-ready: autograd produces fresh .grad tensors; when every parameter of a bucket
@@ -224,7 +255,11 @@ class ConsensusEngine:
         # produced that gradient), so updating it early is exact.
         self.early_update = (self.topo == "gossip" and self.V == 1 and dev.type == "cuda"
                              and cfg.fault.kind not in COLLUSION
-                             and cfg.topology.early_update)
+                             and cfg.topology.early_update and not self.clip)
+        if self.clip and self.topo == "gossip" and self.V == 1 and cfg.topology.early_update:
+            # the first bucket's update needs the norm over all of them
+            _log.info("optim.clip_norm > 0: topology.early_update is off (the update waits for "
+                      "the global gradient norm)")
         self._updated: set = set()
         self._opt_stream = torch.cuda.Stream(device=dev) if self.early_update else None
         # Sharded topology: the bf16 parameter all-gather of each bucket is not waited for at the
@@ -791,7 +826,7 @@ class ConsensusEngine:
                           param_out: torch.Tensor, opt: K.OptArgs,
                           gout: Optional[torch.Tensor]) -> None:
         cfg = self.cfg.agg
-        m, s1, s2 = self._state(state_off, length)
+        m, s1, s2 = self._state(state_off, length) if opt.kind != "none" else (None, None, None)
         if self.rule in K.COORD_RULES:
             lo, cnt, keep = K.near_range(self.rule, self.n, cfg.f, cfg.trim)
             K.agg_update(X, combine="sorted", lo=lo, cnt=cnt, n=self.n, D=length, opt=opt,
@@ -806,11 +841,14 @@ class ConsensusEngine:
             K.agg_update(X, combine="weighted", w=self.w, n=self.rows_total, D=length, opt=opt,
                          master=m, s1=s1, s2=s2, param_out=param_out, gout=gout)
 
-    def _aggregate_update_multi(self, segs, opt: K.OptArgs) -> None:
+    def _aggregate_update_multi(self, segs, opt: K.OptArgs,
+                                gout: Optional[torch.Tensor] = None) -> None:
         """``_aggregate_update`` of several buckets in one launch: segs = (X, length, pout, soff)."""
         cfg = self.cfg.agg
         ks = [(X, length, soff, pout) for X, length, pout, soff in segs]
-        st = dict(master=self.master, s1=self.s1, s2=self.s2, opt=opt)
+        st = dict(master=self.master, s1=self.s1, s2=self.s2, opt=opt, gout=gout)
+        if opt.kind == "none":
+            st.update(master=None, s1=None, s2=None)
         if self.rule in K.COORD_RULES:
             lo, cnt, keep = K.near_range(self.rule, self.n, cfg.f, cfg.trim)
             K.agg_update_multi(ks, combine="sorted", lo=lo, cnt=cnt, n=self.n, mix=self.M, keep=keep,
@@ -823,6 +861,31 @@ class ConsensusEngine:
         else:
             K.agg_update_multi(ks, combine="weighted", w=self.w, n=self.rows_total, **st)
 
+    # ================================================================ global-norm clipping
+    def _clip_weight(self, segments, scale: float, reduce: bool = False) -> None:
+        """Stage 2: w_clip <- scale * min(1, clip_norm / (||scale * segments|| + 1e-6)), on the
+        device. ``reduce``: the squared norm is this rank's part; one all-reduce (fp64 scalar,
+        issued by every rank at this point of the step) makes the coefficient the same everywhere."""
+        if self._clip_work is None:     # the segments are the same buffers every step
+            self._clip_work = K.sq_norm_workspace(segments, self.device)
+        K.sq_norm(segments, scale, self._clip_work, self._norm2)
+        red = None
+        if reduce:
+            red = self._norm2_red
+            red.copy_(self._norm2)
+            dist.all_reduce(red)
+        K.clip_coef(self._norm2, self.clip_norm, scale, self.w_clip, self.grad_stats, reduced=red)
+
+    def _clipped_row_update(self, row: torch.Tensor, scale: float) -> None:
+        """Stages 2 + 3 over ONE row of the whole state vector (a gradient row times ``scale``, or
+        the materialised fp32 aggregate with scale 1): norm, then the weighted kernel with the
+        device weight w_clip in place of the host-side gradient scale."""
+        fl = self.flat
+        self._clip_weight([row], scale)
+        m, s1, s2 = self._state(0, fl.total)
+        K.agg_update(row, combine="weighted", w=self.w_clip, n=1, D=fl.total, opt=self._opt_args(),
+                     master=m, s1=s1, s2=s2, param_out=fl.flat_param)
+
     # ================================================================ topologies
     def _step_allreduce(self) -> None:
         fl = self.flat
@@ -830,6 +893,9 @@ class ConsensusEngine:
             self._wait(b)
         if not self.group_active and self.V > 1:
             fl.flat_grad[0].copy_(fl.flat_grad.float().sum(0).to(fl.dtype))
+        if self.clip:       # direct path: every rank holds the same summed row, no collective
+            self._clipped_row_update(fl.flat_grad[0], 1.0 / self.n)
+            return
         opt = self._opt_args(gscale=1.0 / self.n)
         m, s1, s2 = self._state(0, fl.total)
         K.agg_update(fl.flat_grad[0], combine="weighted", n=1, opt=opt, master=m, s1=s1, s2=s2,
@@ -844,13 +910,15 @@ class ConsensusEngine:
             self._compute_weights(cols)
         if self.record_stats:
             self._record_stats(cols)
-        opt = self._opt_args()
+        opt = self._opt_args() if not self.clip else K.OptArgs(kind="none")
         for b, X, length in cols:
             gout = self.gout[b.offset:b.offset + b.length] if self.gout is not None else None
             self._aggregate_update(b, X, length, b.offset, fl.flat_param[b.offset:b.offset + b.length],
                                    opt, gout)
             if self.rule == "centered_clip":
-                X[self.n].copy_(gout.to(X.dtype))   # v0 <- new aggregate
+                X[self.n].copy_(gout.to(X.dtype))   # v0 <- new (unclipped) aggregate
+        if self.clip:       # every rank holds the full aggregate: no collective
+            self._clipped_row_update(self.gout, 1.0)
 
     def _step_sharded(self) -> None:
         fl = self.flat
@@ -873,12 +941,30 @@ class ConsensusEngine:
         # every bucket's rule + optimizer step in ONE launch (centered clipping writes its
         # aggregate back into each bucket's rows, so it stays per bucket)
         fused = self.rule != "centered_clip" and 1 <= len(cols) <= 16 and self.device.type == "cuda"
+        rule_opt = opt if not self.clip else K.OptArgs(kind="none")    # clipping: stage 1 only
         if fused:
-            self._aggregate_update_multi([(X, length) + shard(b) for b, X, length in order], opt)
+            self._aggregate_update_multi([(X, length) + shard(b) for b, X, length in order],
+                                         rule_opt, gout=self.gout if self.clip else None)
+        if self.clip:
+            for b, X, length in ([] if fused else order):
+                _, soff = shard(b)
+                gout = self.gout[soff:soff + length]
+                self._aggregate_update(b, X, length, soff, None, rule_opt, gout)
+                if self.rule == "centered_clip":
+                    X[self.n, :length].copy_(gout.to(X.dtype))    # v0 <- the UNCLIPPED aggregate
+            # stage 2 over this rank's shards (N > 1: + one all-reduce of the fp64 scalar), then
+            # stage 3: ONE weighted launch (n = 1, w = w_clip) over the gout segments
+            self._clip_weight([self.gout], 1.0, reduce=self._norm2_red is not None)
+            segs = []
+            for b, X, length in order:
+                pout, soff = shard(b)
+                segs.append((self.gout[soff:soff + length], length, soff, pout))
+            K.agg_update_multi(segs, combine="weighted", w=self.w_clip, n=1, opt=opt,
+                               master=self.master, s1=self.s1, s2=self.s2)
         # earliest layers (highest bucket index) first: the next forward needs them first
         for b, X, length in order:
             pout, soff = shard(b)
-            if not fused:
+            if not fused and not self.clip:
                 gout = self.gout[soff:soff + length] if self.gout is not None else None
                 self._aggregate_update(b, X, length, soff, pout, opt, gout)
                 if self.rule == "centered_clip":
@@ -952,7 +1038,14 @@ class ConsensusEngine:
 
     def _step_gossip(self) -> None:
         fl = self.flat
-        if not self.early_update:
+        if self.clip and self.V == 1:
+            # every rank clips its own local gradient; direct path: the row is the gradient
+            self._clipped_row_update(fl.flat_grad[0], 1.0)
+        elif self.clip:
+            K.agg_update(fl.flat_grad, combine="weighted", n=self.V,
+                         opt=K.OptArgs(kind="none", gscale=1.0 / self.V), gout=self.gout)
+            self._clipped_row_update(self.gout, 1.0)
+        elif not self.early_update:
             opt = self._opt_args(gscale=1.0 / self.V)
             m, s1, s2 = self._state(0, fl.total)
             K.agg_update(fl.flat_grad, combine="weighted", n=self.V, opt=opt, master=m, s1=s1,

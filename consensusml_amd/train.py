@@ -58,7 +58,13 @@ def main(argv=None) -> int:
         if wd is not None:
             wd.beat(s)
         if (s + 1) % 10 == 0 or s + 1 == cfg.steps:
-            tr.logger.log(step=s + 1, loss=float(loss), selection=tr.engine.sel_counts.tolist())
+            clip = {}
+            if tr.engine.grad_stats is not None:    # optim.clip_norm: read at logged steps only
+                gs = tr.engine.grad_stats.tolist()
+                clip = {"grad_norm": gs[0], "clip_coef": gs[1], "nonfinite_norms": int(gs[2])}
+                res.update(clip)
+            tr.logger.log(step=s + 1, loss=float(loss), selection=tr.engine.sel_counts.tolist(),
+                          **clip)
         if ckpt_now:
             tr.save()
     res["final_loss"] = float(loss) if cfg.steps > start else None

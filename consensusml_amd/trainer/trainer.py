@@ -122,6 +122,7 @@ class ConsensusTrainer:
         start = self.engine.step_count
         t0 = time.perf_counter()
         losses = []
+        clip_log: Dict[str, object] = {}   # optim.clip_norm: norm / coefficient of the last LOGGED step
         stats_ok = self.engine.topo in ("sharded", "allgather")
         for s in range(start, steps):
             ckpt_now = bool(self.cfg.ckpt_every and self.cfg.ckpt_dir
@@ -136,8 +137,9 @@ class ConsensusTrainer:
             losses.append(loss)
             if log_now:
                 lv = float(loss)
-                self.logger.log(step=s + 1, loss=lv, phases=self.timer.summary(),
-                                **self._log_stats())
+                stats = self._log_stats()
+                clip_log = {k: stats[k] for k in ("grad_norm", "clip_coef") if k in stats}
+                self.logger.log(step=s + 1, loss=lv, phases=self.timer.summary(), **stats)
             if ckpt_now:
                 save_checkpoint(self.cfg.ckpt_dir, self.engine, self.cfg, gens=self.gens,
                                 table=self._consensus_table())
@@ -150,6 +152,7 @@ class ConsensusTrainer:
         n_done = max(steps - start, 0)
         samples = n_done * self.cfg.batch_per_worker * self.engine.n
         return {
+            **clip_log,
             "final_model": self.model,
             "history": hist,
             "steps": steps,
@@ -164,11 +167,17 @@ class ConsensusTrainer:
 
     def _log_stats(self) -> Dict[str, object]:
         """Observability fields of a JSONL step record: selection counts and
-        aggregation weights of the rule, and -- when the step was recorded -- per-worker gradient
+        aggregation weights of the rule, with ``optim.clip_norm`` the norm of the aggregate and the
+        clipping coefficient of the last step, and -- when the step was recorded -- per-worker gradient
         norms, distances to the aggregate and Krum scores (whole model)."""
         e = self.engine
         out: Dict[str, object] = {"selection_counts": e.sel_counts.cpu().tolist(),
                                   "weights": e.w[: e.n].float().cpu().tolist()}
+        if e.grad_stats is not None:
+            # optim.clip_norm: the device-side statistics are read here only (a logged step
+            # synchronises for the loss anyway), never in the step itself
+            gs = e.grad_stats.cpu().tolist()
+            out["grad_norm"], out["clip_coef"] = gs[0], gs[1]
         st = e.last_stats
         if st is not None and st.get("step") == e.step_count - 1:   # recorded by the last step
             out["worker_grad_norm"] = st["sqnorm"].sum(0).sqrt().tolist()

@@ -1883,6 +1883,92 @@ void worker_momentum(Tensor& rows, Tensor& mom, double beta, int64_t grid_cap) {
                                             static_cast<int>(grid_cap), cur_stream()));
 }
 
+// ---------------------------------------------------------------- global-norm clipping
+// fp64 partials that sq_norm writes for these segment lengths (one launch per 16 segments)
+int64_t sq_norm_partials(int dt, const std::vector<int64_t>& lens, int64_t grid_cap) {
+  int64_t total = 0;
+  for (size_t a = 0; a < lens.size(); a += cml::kSqNormMaxSegs) {
+    const size_t b = std::min(lens.size(), a + cml::kSqNormMaxSegs);
+    const int64_t maxlen = *std::max_element(lens.begin() + a, lens.begin() + b);
+    total += static_cast<int64_t>(b - a) *
+             cml::sq_norm_grid(dt, maxlen, static_cast<int>(b - a), static_cast<int>(grid_cap));
+  }
+  return total;
+}
+
+int64_t sq_norm_workspace(bool bf16_rows, const std::vector<int64_t>& lens, int64_t grid_cap) {
+  TORCH_CHECK(grid_cap >= 0 && grid_cap <= (1 << 20), "sq_norm: grid_cap out of range");
+  return sq_norm_partials(bf16_rows ? cml::DT_BF16 : cml::DT_F32, lens, grid_cap);
+}
+
+// out[0] (fp64) = sum over every element x of the segments of (float(x) * scale)^2. segments:
+// contiguous 1-D tensors of one dtype (bf16 / fp32) on one device; work: fp64, at least
+// sq_norm_workspace(...) elements.
+void sq_norm(const std::vector<Tensor>& segments, double scale, Tensor& work, Tensor& out,
+             int64_t grid_cap) {
+  TORCH_CHECK(!segments.empty(), "sq_norm: no segments");
+  TORCH_CHECK(grid_cap >= 0 && grid_cap <= (1 << 20), "sq_norm: grid_cap out of range");
+  const int dt = dtype_of(segments[0]);
+  std::vector<cml::SqNormSeg> segs(segments.size());
+  std::vector<int64_t> lens(segments.size());
+  for (size_t i = 0; i < segments.size(); ++i) {
+    const Tensor& s = segments[i];
+    check_dev(s, "segment");
+    TORCH_CHECK(s.device() == segments[0].device() && s.scalar_type() == segments[0].scalar_type(),
+                "sq_norm: segments on one device with one dtype");
+    TORCH_CHECK(s.is_contiguous(), "sq_norm: segments must be contiguous");
+    segs[i] = cml::SqNormSeg{s.data_ptr(), s.numel()};
+    lens[i] = s.numel();
+  }
+  const int64_t npart = sq_norm_partials(dt, lens, grid_cap);
+  TORCH_CHECK(npart <= INT_MAX, "sq_norm: too many partials");
+  TORCH_CHECK(work.is_cuda() && work.device() == segments[0].device() &&
+                  work.scalar_type() == at::kDouble && work.is_contiguous() &&
+                  work.numel() >= npart,
+              "sq_norm: work must be a contiguous fp64 tensor of at least ", npart,
+              " elements on the segments' device");
+  TORCH_CHECK(out.is_cuda() && out.device() == segments[0].device() &&
+                  out.scalar_type() == at::kDouble && out.numel() >= 1 && out.is_contiguous(),
+              "sq_norm: out must be an fp64 tensor on the segments' device");
+  const c10::DeviceGuard guard(segments[0].device());
+  double* w = work.data_ptr<double>();
+  for (size_t a = 0; a < segs.size(); a += cml::kSqNormMaxSegs) {
+    const int ns = static_cast<int>(std::min(segs.size(), a + cml::kSqNormMaxSegs) - a);
+    CML_CHECK_HIP(cml::launch_sq_norm_partial(dt, segs.data() + a, ns, static_cast<float>(scale),
+                                              w, static_cast<int>(grid_cap), cur_stream()));
+    const int64_t maxlen = *std::max_element(lens.begin() + a, lens.begin() + a + ns);
+    w += static_cast<int64_t>(ns) * cml::sq_norm_grid(dt, maxlen, ns, static_cast<int>(grid_cap));
+  }
+  CML_CHECK_HIP(cml::launch_clip_finalize(work.data_ptr<double>(), static_cast<int>(npart),
+                                          out.data_ptr<double>(), nullptr, 0.0, 0.0f, nullptr,
+                                          nullptr, cur_stream()));
+}
+
+// w_out[0] (fp32) = base * min(1, max_norm / (sqrt(s) + 1e-6)), s = reduced[0] when given, else
+// norm2[0]; stats (fp64 [4]) = [norm, coef, non-finite count (+= 1 when s is not finite, coef = 0),
+// s]
+void clip_coef(const Tensor& norm2, double max_norm, double base, Tensor& w_out, Tensor& stats,
+               const optional<Tensor>& reduced) {
+  check_dev(norm2, "norm2");
+  TORCH_CHECK(norm2.scalar_type() == at::kDouble && norm2.numel() >= 1 && norm2.is_contiguous(),
+              "clip_coef: norm2 must be an fp64 tensor");
+  TORCH_CHECK(w_out.is_cuda() && w_out.device() == norm2.device() &&
+                  w_out.scalar_type() == at::kFloat && w_out.numel() >= 1 && w_out.is_contiguous(),
+              "clip_coef: w_out must be an fp32 tensor on norm2's device");
+  TORCH_CHECK(stats.is_cuda() && stats.device() == norm2.device() &&
+                  stats.scalar_type() == at::kDouble && stats.numel() >= cml::kClipStats &&
+                  stats.is_contiguous(),
+              "clip_coef: stats must be an fp64 tensor of at least ", cml::kClipStats, " elements");
+  const double* red = opt_ptr<const double>(reduced, at::kDouble, "reduced", 1);
+  if (red) TORCH_CHECK(reduced->device() == norm2.device(), "clip_coef: reduced on norm2's device");
+  TORCH_CHECK(max_norm >= 0.0, "clip_coef: max_norm must not be negative");
+  const c10::DeviceGuard guard(norm2.device());
+  CML_CHECK_HIP(cml::launch_clip_finalize(nullptr, 0, const_cast<double*>(norm2.data_ptr<double>()),
+                                          red, max_norm, static_cast<float>(base),
+                                          w_out.data_ptr<float>(), stats.data_ptr<double>(),
+                                          cur_stream()));
+}
+
 // ---------------------------------------------------------------- transformer ops
 void check_bf16c(const Tensor& t, const char* name) {
   check_dev(t, name);
@@ -2710,6 +2796,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("worker_momentum", &worker_momentum,
         "worker-side momentum: mom <- beta mom + rows, rows <- mom, in place over an [R, L] window",
         py::arg("rows"), py::arg("mom"), py::arg("beta"), py::arg("grid_cap") = 0);
+  m.def("sq_norm_workspace", &sq_norm_workspace, "fp64 partials sq_norm writes for these lengths",
+        py::arg("bf16_rows"), py::arg("lens"), py::arg("grid_cap") = 0);
+  m.def("sq_norm", &sq_norm, "out[0] = sum of (float(x) * scale)^2 over the segments, in fp64",
+        py::arg("segments"), py::arg("scale"), py::arg("work"), py::arg("out"),
+        py::arg("grid_cap") = 0);
+  m.def("clip_coef", &clip_coef, "global-norm clipping coefficient as a device weight + stats",
+        py::arg("norm2"), py::arg("max_norm"), py::arg("base"), py::arg("w_out"), py::arg("stats"),
+        py::arg("reduced") = py::none());
   m.def("bn_fwd", &bn_fwd, "fused NHWC BatchNorm(+res)(+ReLU) forward");
   m.def("bn_bwd", &bn_bwd, "fused NHWC BatchNorm(+res)(+ReLU) backward");
   m.def("bn_fwd2", &bn_fwd2, "relu(BN(x1) + BN(x2)) forward (downsample-block tail)");

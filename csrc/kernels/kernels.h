@@ -252,6 +252,32 @@ hipError_t launch_fault(int dtype, void* g, int64_t D, int kind, float scale, fl
 hipError_t launch_worker_momentum(int dtype, void* rows, int64_t ldr, float* mom, int64_t ldm,
                                   int R, int64_t L, float beta, int grid_cap, hipStream_t stream);
 
+// Global-norm clipping of the aggregate (clip_norm.hip, optim.clip_norm).
+// sq_norm_partial: sum over the elements of up to kSqNormMaxSegs contiguous segments (all bf16 or
+// all fp32) of (float(x) * scale)^2, the product rounded to fp32 and the square accumulated in
+// fp64. Workgroup (bx, segment sg) writes ONE fp64 partial to work[sg * gx + bx], gx =
+// sq_norm_grid(dtype, longest segment, nseg, grid_cap): nseg * gx partials per launch, every one of them written
+// (no atomics, nothing to clear), each a fixed-order sum. grid_cap: most workgroups over all
+// segments; <= 0 = the default.
+constexpr int kSqNormMaxSegs = 16;
+struct SqNormSeg {
+  const void* x;
+  int64_t len;
+};
+int sq_norm_grid(int dtype, int64_t maxlen, int nseg, int grid_cap);
+hipError_t launch_sq_norm_partial(int dtype, const SqNormSeg* segs, int nseg, float scale,
+                                  double* work, int grid_cap, hipStream_t stream);
+// clip_finalize (one wave). npart > 0: norm2[0] = partials[0] + partials[1] + ... in index order.
+// w_out != nullptr: with s = reduced ? reduced[0] : norm2[0] (reduced: the sum all-reduced over
+// ranks), norm = sqrt(s), coef = min(1, max_norm / (norm + 1e-6)) in fp64, w_out[0] = float(base *
+// coef), stats[0] = norm, stats[1] = coef, stats[3] = s. A non-finite s gives coef = 0 (the update
+// then applies a zero gradient: the weighted combine never reads a zero-weight row) and adds 1 to
+// stats[2]. kClipStats = the fp64 elements of stats.
+constexpr int kClipStats = 4;
+hipError_t launch_clip_finalize(const double* partials, int npart, double* norm2,
+                                const double* reduced, double max_norm, float base, float* w_out,
+                                double* stats, hipStream_t stream);
+
 // ---- transformer ops (transformer.hip); bf16 activations, fp32 statistics.
 // Cross-entropy over contiguous bf16 logits [R, V] (16-B aligned base): forward writes the
 // per-row logsumexp and loss (0 for ignored rows); backward writes
