@@ -169,7 +169,9 @@ class TopologyConfig:
     gossip_graph: str = "ring"   # ring | exp (one rotating peer 2^(t mod log2 N)) | exp_all
     gossip_chunk_mb: float = 256.0   # gossip exchange pipeline chunk (MB of bf16)
     gossip_weights: tuple = (1 / 3, 1 / 3, 1 / 3)   # ring: self, left, right
-    gossip_clip: float = 0.0     # 0 disables neighbour-delta clipping
+    gossip_clip: float = 0.0     # 0 disables neighbour-delta clipping; > 0 also drops a neighbour
+                                 # whose distance is not finite (NaN / Inf / fp32 overflow): its
+                                 # mixing weight stays with the local parameters
     gossip_async: bool = False   # delayed gossip: exchange overlaps the next step's compute
     early_update: bool = True    # gossip, 1 local worker: per-bucket optimizer step in backward
                                  # (forced off while optim.clip_norm > 0: the update of the first

@@ -443,7 +443,8 @@ def gossip_mix(master: torch.Tensor, left: torch.Tensor, right: torch.Tensor, w0
                w1: float, w2: float, clip: float = 0.0,
                param_out: Optional[torch.Tensor] = None,
                work: Optional[torch.Tensor] = None) -> None:
-    """In-place ring mixing of the fp32 master with the neighbours' bf16 parameters."""
+    """In-place ring mixing of the fp32 master with the neighbours' bf16 parameters (the k = 2
+    form of ``gossip_mix_k``, including its rule for non-finite neighbours under clipping)."""
     if master.is_cuda:
         if work is None:
             work = torch.empty(lib().gossip_workspace_bytes(master.numel()) // 4,
@@ -459,16 +460,24 @@ def gossip_mix(master: torch.Tensor, left: torch.Tensor, right: torch.Tensor, w0
 def gossip_mix_k(master: torch.Tensor, nbrs: List[torch.Tensor], w: List[float], w0: float,
                  clip: float = 0.0, param_out: Optional[torch.Tensor] = None,
                  work: Optional[torch.Tensor] = None,
-                 param_out2: Optional[torch.Tensor] = None) -> None:
+                 param_out2: Optional[torch.Tensor] = None, grid_cap: int = 0) -> None:
     """In-place k-neighbour mixing (1 <= k <= 8) of the fp32 master with the neighbours' bf16
     parameters: x <- (w0 + sum w_k) x + sum_k w_k clip_k(nb_k - x). ``param_out2``: a second
-    copy of the rounded parameters (the delayed-gossip send buffer) written in the same pass."""
+    copy of the rounded parameters (the delayed-gossip send buffer) written in the same pass.
+
+    With ``clip`` > 0 a neighbour whose squared distance to x (summed in fp32) is not finite --
+    it holds a NaN or an Inf, or the sum overflows -- is dropped: its term is exactly zero at
+    every coordinate and its weight stays with x; a non-finite x drops every neighbour.
+    ``clip`` == 0 gives no protection: a NaN propagates.
+
+    ``grid_cap`` > 0 caps the launch at that many workgroups, which then stride over the vector
+    (for tests of the multi-trip loops at small sizes); 0 is the default launch."""
     if master.is_cuda:
         if work is None:
             work = torch.empty(lib().gossip_workspace_bytes(master.numel()) // 4,
                                dtype=torch.float32, device=master.device)
         lib().gossip_mix_k(master, param_out, list(nbrs), [float(v) for v in w], w0, clip, work,
-                           param_out2)
+                           param_out2, grid_cap=grid_cap)
         return
     x = ref.gossip_mix_k(master, nbrs, w, w0, clip)
     master.copy_(x)

@@ -414,28 +414,41 @@ def adam_update(p, g, m, v, step: int, lr: float, beta1: float, beta2: float, ep
     return p, m, v
 
 
+def _clipped_delta(d: torch.Tensor, clip: float) -> torch.Tensor:
+    """c d with c = min(1, clip / ||d||); exactly zero at every coordinate where the fp32 squared
+    distance is not finite (a NaN, an Inf or an overflowing sum: the neighbour is dropped)."""
+    s = (d * d).sum().item()
+    if not math.isfinite(s):
+        return torch.zeros_like(d)
+    return d * min(1.0, clip / max(math.sqrt(s), 1e-30))
+
+
 def gossip_mix(x: torch.Tensor, left: torch.Tensor, right: torch.Tensor, w0: float, w1: float,
                w2: float, clip: float = 0.0) -> torch.Tensor:
+    """The ring (k = 2) form of ``gossip_mix_k``, with the same rule for non-finite neighbours."""
     x = x.float()
     dl = left.float() - x
     dr = right.float() - x
     if clip > 0:
-        nl = dl.norm().item()
-        nr = dr.norm().item()
-        dl = dl * min(1.0, clip / max(nl, 1e-30))
-        dr = dr * min(1.0, clip / max(nr, 1e-30))
+        dl = _clipped_delta(dl, clip)
+        dr = _clipped_delta(dr, clip)
     # w0 x + w1 (x + dl) + w2 (x + dr)
     return (w0 + w1 + w2) * x + w1 * dl + w2 * dr
 
 
 def gossip_mix_k(x: torch.Tensor, nbrs, w, w0: float, clip: float = 0.0) -> torch.Tensor:
-    """x <- (w0 + sum w_k) x + sum_k w_k c_k (nb_k - x), c_k = min(1, clip / ||nb_k - x||)."""
+    """x <- (w0 + sum w_k) x + sum_k w_k c_k (nb_k - x), c_k = min(1, clip / ||nb_k - x||).
+
+    With clip > 0 a neighbour whose squared distance (summed in fp32) is not finite -- it holds a
+    NaN or an Inf, or the sum overflows -- has c_k = 0: its term is exactly zero at every
+    coordinate and its weight stays with x. A non-finite x drops every neighbour. clip == 0
+    gives no protection: a NaN propagates."""
     x = x.float()
     out = (w0 + sum(w)) * x
     for nb, wk in zip(nbrs, w):
         d = nb.float() - x
         if clip > 0:
-            d = d * min(1.0, clip / max(d.norm().item(), 1e-30))
+            d = _clipped_delta(d, clip)
         out = out + wk * d
     return out
 

@@ -312,6 +312,14 @@ int64_t gossip_workspace_bytes(int64_t D) {
   return static_cast<int64_t>(cml::gossip_workspace_bytes(D));
 }
 
+// the distance slab: fp32 on the master's device (a host pointer would reach the kernels)
+void check_gossip_work(const Tensor& work, const Tensor& master, int64_t D) {
+  check_dev(work, "work");
+  TORCH_CHECK(work.device() == master.device(), "work must be on the master's device");
+  TORCH_CHECK(work.scalar_type() == at::kFloat && work.is_contiguous(), "work: fp32 contiguous");
+  TORCH_CHECK(work.numel() * work.element_size() >= gossip_workspace_bytes(D), "gossip workspace too small");
+}
+
 void gossip_mix(Tensor& master, const optional<Tensor>& param_out, const Tensor& left,
                 const Tensor& right, double w0, double w1, double w2, double clip, Tensor& work) {
   check_dev(master, "master");
@@ -320,7 +328,7 @@ void gossip_mix(Tensor& master, const optional<Tensor>& param_out, const Tensor&
   TORCH_CHECK(left.scalar_type() == right.scalar_type() && left.is_contiguous() &&
                   right.is_contiguous() && left.numel() >= D && right.numel() >= D,
               "neighbours: contiguous, same dtype, master's size");
-  TORCH_CHECK(work.numel() * work.element_size() >= gossip_workspace_bytes(D), "gossip workspace too small");
+  check_gossip_work(work, master, D);
   void* p = opt_ptr<void>(param_out, left.scalar_type(), "param_out", D);
   const c10::DeviceGuard guard(master.device());
   CML_CHECK_HIP(cml::launch_gossip_mix(dtype_of(left), master.data_ptr<float>(), p, left.data_ptr(), right.data_ptr(),
@@ -331,12 +339,13 @@ void gossip_mix(Tensor& master, const optional<Tensor>& param_out, const Tensor&
 
 void gossip_mix_k(Tensor& master, const optional<Tensor>& param_out, std::vector<Tensor> nbrs,
                   std::vector<double> w, double w0, double clip, Tensor& work,
-                  const optional<Tensor>& param_out2) {
+                  const optional<Tensor>& param_out2, int64_t grid_cap) {
   check_dev(master, "master");
   TORCH_CHECK(master.scalar_type() == at::kFloat && master.is_contiguous(), "master: fp32 contiguous");
   const int64_t D = master.numel();
   const int k = static_cast<int>(nbrs.size());
   TORCH_CHECK(k >= 1 && k <= 8 && w.size() == nbrs.size(), "1..8 neighbours, one weight each");
+  TORCH_CHECK(grid_cap >= 0 && grid_cap <= (1 << 20), "gossip_mix_k: grid_cap out of range");
   std::vector<const void*> ptr(k);
   std::vector<float> wf(k);
   for (int i = 0; i < k; ++i) {
@@ -346,13 +355,14 @@ void gossip_mix_k(Tensor& master, const optional<Tensor>& param_out, std::vector
     ptr[i] = nbrs[i].data_ptr();
     wf[i] = static_cast<float>(w[i]);
   }
-  TORCH_CHECK(work.numel() * work.element_size() >= gossip_workspace_bytes(D), "gossip workspace too small");
+  check_gossip_work(work, master, D);
   void* p = opt_ptr<void>(param_out, nbrs[0].scalar_type(), "param_out", D);
   void* p2 = opt_ptr<void>(param_out2, nbrs[0].scalar_type(), "param_out2", D);
   const c10::DeviceGuard guard(master.device());
   CML_CHECK_HIP(cml::launch_gossip_mix_k(dtype_of(nbrs[0]), master.data_ptr<float>(), p, ptr.data(),
                                          wf.data(), k, D, static_cast<float>(w0),
-                                         static_cast<float>(clip), work.data_ptr(), cur_stream(), p2));
+                                         static_cast<float>(clip), work.data_ptr(), cur_stream(), p2,
+                                         static_cast<int>(grid_cap)));
 }
 
 // x / res / y: NHWC-contiguous bf16 (4-D channels_last or 2-D [M, C]).
@@ -2786,7 +2796,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gossip_mix_k", &gossip_mix_k, "k-neighbour gossip mixing with neighbour clipping (optional "
         "second parameter output: the delayed-gossip send buffer)", py::arg("master"),
         py::arg("param_out"), py::arg("nbrs"), py::arg("w"), py::arg("w0"), py::arg("clip"),
-        py::arg("work"), py::arg("param_out2") = py::none());
+        py::arg("work"), py::arg("param_out2") = py::none(), py::arg("grid_cap") = 0);
   m.def("colsum_seg", &colsum_seg, "per-segment column sums into strided rows");
   m.def("norm_bwd_seg", &norm_bwd_seg, "LayerNorm / RMSNorm backward with per-segment dgamma / dbeta");
   m.def("conv1x1g_mode", &cml::conv1x1g_mode, "fused 1x1 kernel family: 0 old, 1 glds, 2 auto");

@@ -5,10 +5,13 @@
 // exponential graphs: r +- 2^i, RCCL send/recv, all directions at once). The mix
 //   x <- (w0 + sum_k w_k) x + sum_k w_k c_k (nb_k - x)
 // with c_k = min(1, clip / ||nb_k - x||) (robust gossip: a Byzantine neighbour moves us by at
-// most `clip`) is one streaming pass; the k distances need one reduction pass first. Partial
-// sums go to a per-workgroup slab and the mix kernel's workgroups each fold the slab (<= 2048
-// values, L2-resident) in a fixed order, so the result is deterministic and needs no extra
-// launch or host sync.
+// most `clip`) is one streaming pass; the k distances need one reduction pass first. With
+// clip > 0 a neighbour whose squared distance is not finite (it holds a NaN or an Inf, or the fp32
+// sum overflows) has c_k = 0 and is not read by the mix: its term is exactly zero at every
+// coordinate and its weight stays in (w0 + sum_k w_k), i.e. with x. A non-finite x drops every
+// neighbour. clip == 0 gives no protection: a NaN propagates. Partial sums go to a per-workgroup
+// slab and the mix kernel's workgroups each fold the slab (<= 2048 values, L2-resident) in a
+// fixed order, so the result is deterministic and needs no extra launch or host sync.
 #include <cstdlib>
 
 #include "common.h"
@@ -81,9 +84,11 @@ __global__ __launch_bounds__(kBlk) void nbr_sqdist_kernel(const float* __restric
   }
 }
 
-// x <- (w0 + sum_k w_k) x + sum_k w_k c_k (nb_k - x), c_k = min(1, clip / ||nb_k - x||); the
-// sum is formed from the last neighbour down (for K = 2: fmaf(c0, l - x, c1 (r - x)), the ring
-// kernel's expression). Each workgroup folds the distance slab itself (fixed order).
+// x <- (w0 + sum_k w_k) x + sum_k w_k c_k (nb_k - x), c_k = min(1, clip / ||nb_k - x||), or 0
+// where the distance is not finite (that neighbour is skipped, loads included: the branch is
+// uniform over the launch); the sum is formed from the last neighbour down (for K = 2:
+// fmaf(c0, l - x, c1 (r - x)), the ring kernel's expression). Each workgroup folds the distance
+// slab itself (fixed order).
 template <typename T, int K>
 __global__ __launch_bounds__(kBlk) void gossip_mix_kernel(float* __restrict__ x, T* __restrict__ p,
                                                          T* __restrict__ p2,
@@ -99,16 +104,23 @@ __global__ __launch_bounds__(kBlk) void gossip_mix_kernel(float* __restrict__ x,
         for (int b = threadIdx.x; b < nblk; b += 64) a += part[static_cast<int64_t>(k) * nblk + b];
         a = wave_sum(a);
       }
-      if (threadIdx.x == 0)
-        scl[k] = clip > 0.f ? fminf(1.f, clip / fmaxf(sqrtf(static_cast<float>(a)), 1e-30f)) : 1.f;
+      if (threadIdx.x == 0) {
+        const float s = static_cast<float>(a);
+        scl[k] = clip > 0.f
+                     ? (isfinite(s) ? fminf(1.f, clip / fmaxf(sqrtf(s), 1e-30f)) : 0.f)
+                     : 1.f;
+      }
     }
   }
   __syncthreads();
   float c[K];
-  float cs = w0;
+  bool on[K];   // false: a dropped neighbour (same value in every lane of every workgroup; read
+  float cs = w0;   // through readfirstlane so that the compiler sees a scalar branch condition)
 #pragma unroll
   for (int k = 0; k < K; ++k) {
-    c[k] = nb.w[k] * scl[k];
+    const float sk = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(scl[k])));
+    on[k] = sk != 0.f;
+    c[k] = nb.w[k] * sk;
     cs += nb.w[k];
   }
   const int64_t nv = D / 8;
@@ -116,18 +128,23 @@ __global__ __launch_bounds__(kBlk) void gossip_mix_kernel(float* __restrict__ x,
   for (int64_t t = static_cast<int64_t>(blockIdx.x) * kBlk + threadIdx.x; t < nv; t += stride) {
     float xv[8], acc[8];
     load_vec<float, 8>(x + t * 8, xv);
-    {
+    if (on[K - 1]) {
       float v[8];
       load_vec<T, 8>(nb.p[K - 1] + t * 8, v);
 #pragma unroll
       for (int e = 0; e < 8; ++e) acc[e] = c[K - 1] * (v[e] - xv[e]);
+    } else {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) acc[e] = 0.f;
     }
 #pragma unroll
     for (int k = K - 2; k >= 0; --k) {
-      float v[8];
-      load_vec<T, 8>(nb.p[k] + t * 8, v);
+      if (on[k]) {
+        float v[8];
+        load_vec<T, 8>(nb.p[k] + t * 8, v);
 #pragma unroll
-      for (int e = 0; e < 8; ++e) acc[e] = fmaf(c[k], v[e] - xv[e], acc[e]);
+        for (int e = 0; e < 8; ++e) acc[e] = fmaf(c[k], v[e] - xv[e], acc[e]);
+      }
     }
 #pragma unroll
     for (int e = 0; e < 8; ++e) xv[e] = fmaf(cs, xv[e], acc[e]);
@@ -144,9 +161,10 @@ __global__ __launch_bounds__(kBlk) void gossip_mix_kernel(float* __restrict__ x,
   if (blockIdx.x == 0) {
     for (int64_t e = nv * 8 + threadIdx.x; e < D; e += kBlk) {
       const float xe = x[e];
-      float acc = c[K - 1] * (ld1(nb.p[K - 1], e) - xe);
+      float acc = on[K - 1] ? c[K - 1] * (ld1(nb.p[K - 1], e) - xe) : 0.f;
 #pragma unroll
-      for (int k = K - 2; k >= 0; --k) acc = fmaf(c[k], ld1(nb.p[k], e) - xe, acc);
+      for (int k = K - 2; k >= 0; --k)
+        if (on[k]) acc = fmaf(c[k], ld1(nb.p[k], e) - xe, acc);
       const float v = fmaf(cs, xe, acc);
       x[e] = v;
       if (p) {
@@ -210,14 +228,15 @@ size_t gossip_workspace_bytes(int64_t) { return kMaxNbrs * kMaxBlk * sizeof(floa
 namespace {
 template <typename T, int K>
 void gossip_k(float* master, void* param_out, void* param_out2, const Nbrs<T>& nb, int64_t D,
-              float w0, float clip, void* work, hipStream_t stream) {
+              float w0, float clip, void* work, int grid_cap, hipStream_t stream) {
   float* part = reinterpret_cast<float*>(work);
-  const int nb_blocks = nblocks(D / 8, kMaxBlk);
+  const int nb_blocks = nblocks(D / 8, grid_cap > 0 && grid_cap < kMaxBlk ? grid_cap : kMaxBlk);
   if (clip > 0.f) nbr_sqdist_kernel<T, K><<<nb_blocks, kBlk, 0, stream>>>(master, nb, D, part);
-  static const int cap = [] {   // CML_GOSSIP_GRID_CAP (default 0: one vector per thread, the
+  static const int env_cap = [] {   // CML_GOSSIP_GRID_CAP (default 0: one vector per thread, the
     const char* e = getenv("CML_GOSSIP_GRID_CAP");   // fastest streaming form; 2048: the former
     return e ? atoi(e) : 0;                          // grid-stride launch)
   }();
+  const int cap = grid_cap > 0 ? grid_cap : env_cap;
   gossip_mix_kernel<T, K><<<nblocks(D / 8, cap > 0 ? cap : (1 << 30)), kBlk, 0, stream>>>(
       master, reinterpret_cast<T*>(param_out), reinterpret_cast<T*>(param_out2), nb, D, w0, clip,
       part, nb_blocks);
@@ -226,21 +245,21 @@ void gossip_k(float* master, void* param_out, void* param_out2, const Nbrs<T>& n
 template <typename T>
 hipError_t gossip_t(float* master, void* param_out, void* param_out2, const void* const* nbrs,
                     const float* w, int k, int64_t D, float w0, float clip, void* work,
-                    hipStream_t stream) {
+                    int grid_cap, hipStream_t stream) {
   Nbrs<T> nb{};
   for (int i = 0; i < k; ++i) {
     nb.p[i] = reinterpret_cast<const T*>(nbrs[i]);
     nb.w[i] = w[i];
   }
   switch (k) {
-    case 1: gossip_k<T, 1>(master, param_out, param_out2, nb, D, w0, clip, work, stream); break;
-    case 2: gossip_k<T, 2>(master, param_out, param_out2, nb, D, w0, clip, work, stream); break;
-    case 3: gossip_k<T, 3>(master, param_out, param_out2, nb, D, w0, clip, work, stream); break;
-    case 4: gossip_k<T, 4>(master, param_out, param_out2, nb, D, w0, clip, work, stream); break;
-    case 5: gossip_k<T, 5>(master, param_out, param_out2, nb, D, w0, clip, work, stream); break;
-    case 6: gossip_k<T, 6>(master, param_out, param_out2, nb, D, w0, clip, work, stream); break;
-    case 7: gossip_k<T, 7>(master, param_out, param_out2, nb, D, w0, clip, work, stream); break;
-    case 8: gossip_k<T, 8>(master, param_out, param_out2, nb, D, w0, clip, work, stream); break;
+    case 1: gossip_k<T, 1>(master, param_out, param_out2, nb, D, w0, clip, work, grid_cap, stream); break;
+    case 2: gossip_k<T, 2>(master, param_out, param_out2, nb, D, w0, clip, work, grid_cap, stream); break;
+    case 3: gossip_k<T, 3>(master, param_out, param_out2, nb, D, w0, clip, work, grid_cap, stream); break;
+    case 4: gossip_k<T, 4>(master, param_out, param_out2, nb, D, w0, clip, work, grid_cap, stream); break;
+    case 5: gossip_k<T, 5>(master, param_out, param_out2, nb, D, w0, clip, work, grid_cap, stream); break;
+    case 6: gossip_k<T, 6>(master, param_out, param_out2, nb, D, w0, clip, work, grid_cap, stream); break;
+    case 7: gossip_k<T, 7>(master, param_out, param_out2, nb, D, w0, clip, work, grid_cap, stream); break;
+    case 8: gossip_k<T, 8>(master, param_out, param_out2, nb, D, w0, clip, work, grid_cap, stream); break;
     default: return hipErrorInvalidValue;
   }
   return hipGetLastError();
@@ -249,15 +268,17 @@ hipError_t gossip_t(float* master, void* param_out, void* param_out2, const void
 
 hipError_t launch_gossip_mix_k(int dtype, float* master, void* param_out, const void* const* nbrs,
                                const float* w, int k, int64_t D, float w0, float clip, void* work,
-                               hipStream_t stream, void* param_out2) {
+                               hipStream_t stream, void* param_out2, int grid_cap) {
   if (k < 1 || k > kMaxNbrs) return hipErrorInvalidValue;
   uintptr_t a = reinterpret_cast<uintptr_t>(master) | reinterpret_cast<uintptr_t>(param_out) |
                 reinterpret_cast<uintptr_t>(param_out2);
   for (int i = 0; i < k; ++i) a |= reinterpret_cast<uintptr_t>(nbrs[i]);
   if (a % 16) return hipErrorInvalidValue;
   return dtype == DT_BF16
-             ? gossip_t<bf16>(master, param_out, param_out2, nbrs, w, k, D, w0, clip, work, stream)
-             : gossip_t<float>(master, param_out, param_out2, nbrs, w, k, D, w0, clip, work, stream);
+             ? gossip_t<bf16>(master, param_out, param_out2, nbrs, w, k, D, w0, clip, work,
+                              grid_cap, stream)
+             : gossip_t<float>(master, param_out, param_out2, nbrs, w, k, D, w0, clip, work,
+                               grid_cap, stream);
 }
 
 hipError_t launch_gossip_mix(int dtype, float* master, void* param_out, const void* left,

@@ -125,10 +125,14 @@ void set_conv1x1g_mode(int mode);
 void set_conv1x1g_ablate(int bits);
 
 size_t gossip_workspace_bytes(int64_t D);
-// k-neighbour mix (1 <= k <= 8): x <- (w0 + sum w_k) x + sum_k w_k clip_k(nbrs[k] - x)
+// k-neighbour mix (1 <= k <= 8): x <- (w0 + sum w_k) x + sum_k w_k clip_k(nbrs[k] - x); with
+// clip > 0 a neighbour at a non-finite distance (NaN / Inf / fp32 overflow) contributes exactly
+// zero. grid_cap > 0: at most that many workgroups in the mix launch and min(grid_cap, 1024) in
+// the distance launch (they stride over the vector); <= 0 = the default launch (env
+// CML_GOSSIP_GRID_CAP).
 hipError_t launch_gossip_mix_k(int dtype, float* master, void* param_out, const void* const* nbrs,
                                const float* w, int k, int64_t D, float w0, float clip, void* work,
-                               hipStream_t stream, void* param_out2 = nullptr);
+                               hipStream_t stream, void* param_out2 = nullptr, int grid_cap = 0);
 hipError_t launch_gossip_mix(int dtype, float* master, void* param_out, const void* left,
                              const void* right, int64_t D, float w0, float w1, float w2,
                              float clip, void* work, hipStream_t stream);
