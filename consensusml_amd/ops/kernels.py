@@ -221,10 +221,15 @@ def agg_update_multi(segs, *, combine: str, lo: int = 0, cnt: int = 1,
 
 def gram(X: torch.Tensor, rows: Optional[torch.Tensor] = None, n: Optional[int] = None,
          D: Optional[int] = None, out: Optional[torch.Tensor] = None,
-         accumulate: bool = False, center: Optional[torch.Tensor] = None) -> torch.Tensor:
+         accumulate: bool = False, center: Optional[torch.Tensor] = None,
+         grid_cap: int = 0) -> torch.Tensor:
     """G = X X^T in fp64 ([n, n]); MFMA kernel on GPU. ``accumulate``: out += X X^T.
     ``center`` (int32 [1] on X's device): the Gram of the rows relative to row ``center[0]``
-    (same distances, no cancellation for near-duplicate rows; see ``gram_center``)."""
+    (same distances, no cancellation for near-duplicate rows; see ``gram_center``).
+    ``grid_cap`` > 0: at most that many stage-1 workgroups on GPU (tests of the multi-trip loops
+    at small sizes; ignored on CPU)."""
+    if accumulate and out is None:
+        raise ValueError("accumulate needs out")
     X = _as2d(X)
     n = n if n is not None else (rows.numel() if rows is not None else X.shape[0])
     D = D if D is not None else X.shape[1]
@@ -234,10 +239,8 @@ def gram(X: torch.Tensor, rows: Optional[torch.Tensor] = None, n: Optional[int] 
         if X.data_ptr() % 16 or (X.stride(0) * X.element_size()) % 16:
             X = X[:n if rows is None else X.shape[0], :D].contiguous()
             X = torch.nn.functional.pad(X, (0, (-D) % 8))
-        if accumulate and out is None:
-            raise ValueError("accumulate needs out")
         ws = GramWorkspace.get(X.device, n, D)
-        lib().gram(X, n, D, rows, ws, out, accumulate, center)
+        lib().gram(X, n, D, rows, ws, out, accumulate, center, grid_cap)
         return out
     Xr = X[rows.long()] if rows is not None else X[:n]
     Xr = Xr[:, :D]
@@ -261,7 +264,7 @@ def gram_center(G: torch.Tensor, n: int, out: Optional[torch.Tensor] = None) -> 
     if out is None:
         out = torch.zeros(1, dtype=torch.int32, device=G.device)
     if G.is_cuda:
-        lib().gram_center(G.contiguous(), n, out)
+        lib().gram_center(G[:n, :n].contiguous(), n, out)   # the CPU branch's block
         return out
     out.reshape(-1)[0] = ref.gram_center(G[:n, :n])   # (element 1 of an engine center: guard state)
     return out

@@ -200,8 +200,9 @@ int64_t gram_workspace_bytes(int64_t n, int64_t D) {
 }
 
 void gram(const Tensor& X, int64_t n, int64_t D, const optional<Tensor>& rows, Tensor& work,
-          Tensor& G, bool accumulate, const optional<Tensor>& center) {
+          Tensor& G, bool accumulate, const optional<Tensor>& center, int64_t grid_cap) {
   check_dev(X, "X");
+  TORCH_CHECK(grid_cap >= 0 && grid_cap <= (1 << 20), "gram: grid_cap out of range");
   TORCH_CHECK(X.dim() == 2 && X.stride(1) == 1, "X must be 2-D with unit column stride");
   TORCH_CHECK(n >= 1 && n <= 64, "1 <= n <= 64 workers supported");
   TORCH_CHECK(D >= 1 && D <= X.size(1), "D out of range");
@@ -216,13 +217,14 @@ void gram(const Tensor& X, int64_t n, int64_t D, const optional<Tensor>& rows, T
   const c10::DeviceGuard guard(X.device());
   CML_CHECK_HIP(cml::launch_gram(dtype_of(X), X.data_ptr(), X.stride(0), static_cast<int>(n), r, D,
                                  work.data_ptr(), G.data_ptr<double>(), accumulate ? 1 : 0,
-                                 cur_stream(), c));
+                                 cur_stream(), c, static_cast<int>(grid_cap)));
 }
 
 // stage 1 of gram() into `work` (a per-bucket workspace); returns the partial block count
 int64_t gram_partial(const Tensor& X, int64_t n, int64_t D, Tensor& work,
-                     const optional<Tensor>& center) {
+                     const optional<Tensor>& center, int64_t grid_cap) {
   check_dev(X, "X");
+  TORCH_CHECK(grid_cap >= 0 && grid_cap <= (1 << 20), "gram_partial: grid_cap out of range");
   TORCH_CHECK(X.dim() == 2 && X.stride(1) == 1 && X.size(0) >= n, "X: 2-D, unit column stride, >= n rows");
   TORCH_CHECK(n >= 1 && n <= 64 && D >= 1 && D <= X.size(1), "gram_partial: 1 <= n <= 64, D in range");
   TORCH_CHECK(work.is_cuda() && work.is_contiguous() &&
@@ -232,7 +234,8 @@ int64_t gram_partial(const Tensor& X, int64_t n, int64_t D, Tensor& work,
   const c10::DeviceGuard guard(X.device());
   int nblk = 0;
   CML_CHECK_HIP(cml::launch_gram_partial(dtype_of(X), X.data_ptr(), X.stride(0), static_cast<int>(n),
-                                         nullptr, D, work.data_ptr(), cur_stream(), c, &nblk));
+                                         nullptr, D, work.data_ptr(), cur_stream(), c, &nblk,
+                                         static_cast<int>(grid_cap)));
   return nblk;
 }
 
@@ -2769,7 +2772,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gram_workspace_bytes", &gram_workspace_bytes);
   m.def("gram", &gram, "G = X X^T (fp64) on MFMA; center: rows relative to that row",
         py::arg("X"), py::arg("n"), py::arg("D"), py::arg("rows"), py::arg("work"), py::arg("G"),
-        py::arg("accumulate"), py::arg("center") = py::none());
+        py::arg("accumulate"), py::arg("center") = py::none(), py::arg("grid_cap") = 0);
   m.def("gram_center", &gram_center, "medoid of the finite rows of a Gram matrix");
   m.def("robust_weights", &robust_weights, "robust weights from a Gram matrix (+ selection counts, "
         "next center and the centered-pass guard in the same launch)",
@@ -2779,7 +2782,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("sel_counts") = py::none(), py::arg("pre") = 0, py::arg("mix_out") = py::none());
   m.def("gram_sum", &gram_sum, "sum of per-bucket Gram partials in bucket order");
   m.def("gram_partial", &gram_partial, "Gram stage 1 into a per-bucket workspace (block count)",
-        py::arg("X"), py::arg("n"), py::arg("D"), py::arg("work"), py::arg("center") = py::none());
+        py::arg("X"), py::arg("n"), py::arg("D"), py::arg("work"), py::arg("center") = py::none(),
+        py::arg("grid_cap") = 0);
   m.def("gram_reduce_multi", &gram_reduce_multi,
         "reduce several buckets' Gram partials into G in one launch (bucket order)");
   m.def("agg_update_multi", &agg_update_multi,

@@ -394,8 +394,9 @@ int gram_blocks(int64_t D, int cols) {
 // Stage 1 (and, with Gm != null, stage 2); returns the number of partial blocks.
 template <typename T, int TT, int G>
 int launch_gram_t(const T* X, int64_t ld, int n, const int* rows, int64_t D, float* part,
-                  double* Gm, int acc, const int* center, hipStream_t st) {
-  const int nb = gram_blocks(D, gram_cols<T, TT, G>());
+                  double* Gm, int acc, const int* center, int grid_cap, hipStream_t st) {
+  int nb = gram_blocks(D, gram_cols<T, TT, G>());
+  if (grid_cap > 0 && grid_cap < nb) nb = grid_cap;   // tests: the multi-trip loops at small D
   if (center)
     gram_partial_kernel<T, TT, G, true><<<nb, kGBlock, 0, st>>>(X, ld, n, rows, D, part, center);
   else
@@ -408,15 +409,15 @@ int launch_gram_t(const T* X, int64_t ld, int n, const int* rows, int64_t D, flo
 
 template <typename T>
 int launch_gram_dispatch(const T* x, int64_t ld, int n, const int* rows, int64_t D, float* part,
-                         double* G, int acc, const int* c, hipStream_t st) {
-  if (n == 1) return launch_gram_t<T, 1, 16>(x, ld, n, rows, D, part, G, acc, c, st);
-  if (n == 2) return launch_gram_t<T, 1, 8>(x, ld, n, rows, D, part, G, acc, c, st);
-  if (n <= 4) return launch_gram_t<T, 1, 4>(x, ld, n, rows, D, part, G, acc, c, st);
-  if (n <= 8) return launch_gram_t<T, 1, 2>(x, ld, n, rows, D, part, G, acc, c, st);
-  if (n <= 16) return launch_gram_t<T, 1, 1>(x, ld, n, rows, D, part, G, acc, c, st);
-  if (n <= 32) return launch_gram_t<T, 2, 1>(x, ld, n, rows, D, part, G, acc, c, st);
-  if (n <= 48) return launch_gram_t<T, 3, 1>(x, ld, n, rows, D, part, G, acc, c, st);
-  return launch_gram_t<T, 4, 1>(x, ld, n, rows, D, part, G, acc, c, st);
+                         double* G, int acc, const int* c, int cap, hipStream_t st) {
+  if (n == 1) return launch_gram_t<T, 1, 16>(x, ld, n, rows, D, part, G, acc, c, cap, st);
+  if (n == 2) return launch_gram_t<T, 1, 8>(x, ld, n, rows, D, part, G, acc, c, cap, st);
+  if (n <= 4) return launch_gram_t<T, 1, 4>(x, ld, n, rows, D, part, G, acc, c, cap, st);
+  if (n <= 8) return launch_gram_t<T, 1, 2>(x, ld, n, rows, D, part, G, acc, c, cap, st);
+  if (n <= 16) return launch_gram_t<T, 1, 1>(x, ld, n, rows, D, part, G, acc, c, cap, st);
+  if (n <= 32) return launch_gram_t<T, 2, 1>(x, ld, n, rows, D, part, G, acc, c, cap, st);
+  if (n <= 48) return launch_gram_t<T, 3, 1>(x, ld, n, rows, D, part, G, acc, c, cap, st);
+  return launch_gram_t<T, 4, 1>(x, ld, n, rows, D, part, G, acc, c, cap, st);
 }
 }  // namespace
 
@@ -427,7 +428,7 @@ size_t gram_workspace_bytes(int n, int64_t D) {
 
 hipError_t launch_gram(int dtype, const void* X, int64_t ld, int n, const int* rows, int64_t D,
                        void* work, double* G, int accumulate, hipStream_t stream,
-                       const int* center) {
+                       const int* center, int grid_cap) {
   if (n < 1 || n > 64 || D < 1) return hipErrorInvalidValue;
   const int es = dtype == DT_BF16 ? 2 : 4;
   const int vec = 16 / es;
@@ -435,25 +436,25 @@ hipError_t launch_gram(int dtype, const void* X, int64_t ld, int n, const int* r
   float* part = reinterpret_cast<float*>(work);
   if (dtype == DT_BF16)
     launch_gram_dispatch(reinterpret_cast<const bf16*>(X), ld, n, rows, D, part, G, accumulate,
-                         center, stream);
+                         center, grid_cap, stream);
   else
     launch_gram_dispatch(reinterpret_cast<const float*>(X), ld, n, rows, D, part, G, accumulate,
-                         center, stream);
+                         center, grid_cap, stream);
   return hipGetLastError();
 }
 
 hipError_t launch_gram_partial(int dtype, const void* X, int64_t ld, int n, const int* rows,
                                int64_t D, void* work, hipStream_t stream, const int* center,
-                               int* nblk) {
+                               int* nblk, int grid_cap) {
   if (n < 1 || n > 64 || D < 1) return hipErrorInvalidValue;
   const int es = dtype == DT_BF16 ? 2 : 4;
   if ((ld % (16 / es)) != 0 || (reinterpret_cast<uintptr_t>(X) % 16) != 0) return hipErrorInvalidValue;
   float* part = reinterpret_cast<float*>(work);
   *nblk = dtype == DT_BF16
               ? launch_gram_dispatch(reinterpret_cast<const bf16*>(X), ld, n, rows, D, part, nullptr,
-                                     0, center, stream)
+                                     0, center, grid_cap, stream)
               : launch_gram_dispatch(reinterpret_cast<const float*>(X), ld, n, rows, D, part,
-                                     nullptr, 0, center, stream);
+                                     nullptr, 0, center, grid_cap, stream);
   return hipGetLastError();
 }
 

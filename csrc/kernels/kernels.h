@@ -78,9 +78,10 @@ hipError_t launch_agg_update_multi(int dtype, int combine, int opt, const SrcArg
 size_t gram_workspace_bytes(int n, int64_t D);
 // center (device int, may be null): rows relative to worker row *center (centered Gram,
 // translation-invariant for every Gram-space rule, no cancellation for near-duplicate workers).
+// grid_cap > 0: at most that many stage-1 workgroups (tests of the multi-trip loops at small D).
 hipError_t launch_gram(int dtype, const void* X, int64_t ld, int n, const int* rows, int64_t D,
                        void* work, double* G, int accumulate, hipStream_t stream,
-                       const int* center = nullptr);
+                       const int* center = nullptr, int grid_cap = 0);
 // out[0] = the medoid of the finite rows of G [n, n] (the centered Gram's center).
 hipError_t launch_gram_center(const double* G, int n, int* out, hipStream_t stream);
 
@@ -108,7 +109,7 @@ hipError_t launch_robust_weights(int rule, const double* G, int n, int f, int m,
 // launch, bit-identical to one launch_gram per bucket into slots summed by launch_gram_sum.
 hipError_t launch_gram_partial(int dtype, const void* X, int64_t ld, int n, const int* rows,
                                int64_t D, void* work, hipStream_t stream, const int* center,
-                               int* nblk);
+                               int* nblk, int grid_cap = 0);
 hipError_t launch_gram_reduce_multi(const float* const* parts, const int* nblks, int nb, int n,
                                     double* G, hipStream_t stream);
 // G[e] = sum_b Gb[b][e] in b order (the early-Gram per-bucket partials), e < E.
