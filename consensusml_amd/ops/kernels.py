@@ -7,20 +7,21 @@ all-to-all receive buffers need no copy).
 """
 from __future__ import annotations
 
+import functools
 import math
 from dataclasses import dataclass
 from typing import List, Optional, Tuple
 
 import torch
 
+from ..config import COORD_RULES
 from . import reference as ref
 from .native import lib
 
 RULE_IDS = {"mean": 0, "krum": 1, "multi_krum": 2, "geomed": 3, "centered_clip": 4,
             "bulyan_select": 5, "nnm_only": 6}
-COORD_RULES = ("median", "trimmed_mean", "meamed", "phocas")
 PRE_IDS = {"none": 0, "nnm": 1}
-GRAM_RULES = ("krum", "multi_krum", "geomed", "centered_clip")
+WEIGHT_RULES = ("krum", "multi_krum", "geomed", "centered_clip")   # weights: robust_weights
 GOSSIP_MAX_NBRS = 8   # neighbour buffers one gossip_mix_k launch reads (kMaxNbrs, gossip_fault.hip)
 
 
@@ -51,6 +52,44 @@ def near_range(rule: str, n: int, f: int, trim: Optional[int] = None) -> Tuple[i
             raise ValueError(f"phocas needs n > 2*trim (n={n}, trim={b})")
         return b, n - 2 * b, n - f
     return (*sorted_range(rule, n, f if trim is None else trim), 0)
+
+
+@dataclass(frozen=True)
+class Combine:
+    """The keyword arguments of ``agg_update`` / ``agg_update_multi`` that a rule fixes."""
+    combine: str
+    n: int
+    lo: int = 0
+    cnt: int = 1
+    keep: Optional[int] = None
+    w: Optional[torch.Tensor] = None
+    rows: Optional[torch.Tensor] = None
+    mix: Optional[torch.Tensor] = None
+
+    def kwargs(self) -> dict:
+        return dict(vars(self))
+
+
+def rule_combine(rule: str, n: int, f: int, trim: Optional[int] = None, *,
+                 w: Optional[torch.Tensor] = None, sel: Optional[torch.Tensor] = None,
+                 mix: Optional[torch.Tensor] = None, rows_total: Optional[int] = None) -> Combine:
+    """How ``rule`` over n workers combines the rows -- the whole table:
+
+    coordinate rules  sorted, ``near_range(rule, n, f, trim)``, pre-mixed by ``mix`` if given
+    bulyan            sorted: the f-trimmed mean of the n - 2f rows ``sel`` holds (Bulyan's
+                      selection, ``robust_weights`` rule ``'bulyan_select'``)
+    everything else   (mean, Gram-space rules) weighted by ``w`` over ``rows_total`` or n rows
+    """
+    if rule in COORD_RULES:
+        lo, cnt, keep = near_range(rule, n, f, trim)
+        return Combine("sorted", n, lo, cnt, keep, mix=mix)
+    if rule == "bulyan":
+        theta = n - 2 * f
+        lo, cnt = sorted_range("trimmed_mean", theta, f)
+        return Combine("sorted", theta, lo, cnt, rows=sel[:theta])
+    if rule != "mean" and rule not in WEIGHT_RULES:
+        raise ValueError(f"unknown rule {rule!r}")
+    return Combine("weighted", rows_total or n, w=w)
 
 
 @dataclass
@@ -410,35 +449,29 @@ def aggregate(X: torch.Tensor, rule: str, f: int = 0, trim: Optional[int] = None
     out = torch.empty(D, dtype=torch.float32, device=X.device)
     if pre != "none" and rule in ("mean", "bulyan"):
         raise ValueError(f"pre={pre!r} is not defined for rule {rule!r}")
+    plan = functools.partial(rule_combine, rule, n, f, trim)
     if rule in ("mean",):
-        agg_update(X, combine="weighted", w=torch.full((n,), 1.0 / n, device=X.device), gout=out)
+        c = plan(w=torch.full((n,), 1.0 / n, device=X.device))
     elif rule in COORD_RULES:
-        lo, cnt, keep = near_range(rule, n, f, trim)
-        mix = None
-        if pre != "none":
-            mix = torch.empty(n, n, dtype=torch.float32, device=X.device)
+        mix = None if pre == "none" else torch.empty(n, n, dtype=torch.float32, device=X.device)
+        c = plan(mix=mix)
+        if mix is not None:
             robust_weights(gram(X), "nnm_only", n, f, pre=pre, mix_out=mix)
-        agg_update(X, combine="sorted", lo=lo, cnt=cnt, gout=out, mix=mix, keep=keep)
     elif rule in ("krum", "multi_krum", "geomed"):
-        G = gram(X)
-        w = robust_weights(G, rule, n, f, m, iters, eps, pre=pre)
-        agg_update(X, combine="weighted", w=w, gout=out)
+        c = plan(w=robust_weights(gram(X), rule, n, f, m, iters, eps, pre=pre))
     elif rule == "centered_clip":
         v0 = torch.zeros(D, dtype=X.dtype, device=X.device) if v0 is None else v0.to(X.dtype)
-        Y = torch.cat([X, v0[None]], 0)
-        G = gram(Y)
-        c = robust_weights(G, "centered_clip", n, f, tau=tau, iters=clip_iters, pre=pre)
+        X = torch.cat([X, v0[None]], 0)
         # non-finite workers carry weight 0 and are skipped by the weighted kernel
-        agg_update(Y, combine="weighted", w=c, n=n + 1, gout=out)
+        c = plan(w=robust_weights(gram(X), "centered_clip", n, f, tau=tau, iters=clip_iters,
+                                  pre=pre), rows_total=n + 1)
     elif rule == "bulyan":
-        G = gram(X)
         sel = torch.zeros(n + 1, dtype=torch.int32, device=X.device)
-        robust_weights(G, "bulyan_select", n, f, sel=sel)
-        theta = n - 2 * f
-        lo, cnt = sorted_range("trimmed_mean", theta, f)
-        agg_update(X, combine="sorted", lo=lo, cnt=cnt, rows=sel[:theta], n=theta, gout=out)
+        robust_weights(gram(X), "bulyan_select", n, f, sel=sel)
+        c = plan(sel=sel)
     else:
         raise ValueError(f"unknown rule {rule!r}")
+    agg_update(X, gout=out, **c.kwargs())
     return out
 
 

@@ -44,6 +44,7 @@ momenta; centered clipping keeps the UNCLIPPED aggregate as its v0.
 from __future__ import annotations
 
 import contextlib
+import functools
 import logging
 import math
 
@@ -64,7 +65,7 @@ from .faults import COLLUSION, apply_faults, byzantine_rows
 from .flat import Bucket, FlatModel
 
 
-GRAM_RULES = ("krum", "multi_krum", "geomed", "centered_clip", "bulyan")
+GRAM_PASS_RULES = K.WEIGHT_RULES + ("bulyan",)    # the rules that need a Gram pass
 _log = logging.getLogger(__name__)
 
 
@@ -125,7 +126,7 @@ class ConsensusEngine:
         self.pre = cfg.agg.pre
         # this configuration needs the Gram matrix: a Gram-space rule, or nearest-neighbour
         # mixing (whose mixing matrix comes from G, also for the coordinate rules)
-        self.needs_gram = self.rule in GRAM_RULES or self.pre == "nnm"
+        self.needs_gram = self.rule in GRAM_PASS_RULES or self.pre == "nnm"
         if self.topo == "allreduce" and self.rule != "mean":
             raise ValueError("the allreduce topology only implements the mean rule")
         pdtype = next(p for p in model.parameters() if p.requires_grad).dtype
@@ -479,23 +480,18 @@ class ConsensusEngine:
             for b in fl.buckets:       # buckets whose gradients were never all produced
                 if b.index not in self._updated:
                     if self.cfg.fault.kind != "none":
-                        apply_faults(fl.flat_grad, self.cfg.fault, self.rank, self.step_count,
-                                     self.group_active, self.cfg.seed + self.step_count,
-                                     cols=slice(b.offset, b.offset + b.length))
+                        self._inject(b)
                     self._bucket_update(b)
             torch.cuda.current_stream(self.device).wait_stream(self._opt_stream)
         elif not self.overlap or self.cfg.fault.kind in COLLUSION:
-            apply_faults(fl.flat_grad, self.cfg.fault, self.rank, self.step_count,
-                         self.group_active, self.cfg.seed + self.step_count)
+            self._inject()
         for b in fl.buckets:
             if b.index not in self._pending:
                 self._launch_bucket(b, inject=False)
         if self.topo == "allreduce":
             self._step_allreduce()
-        elif self.topo == "allgather":
-            self._step_allgather()
-        elif self.topo == "sharded":
-            self._step_sharded()
+        elif self.topo in ("allgather", "sharded"):
+            self._step_rows()
         else:
             self._step_gossip()
         self._pending.clear()
@@ -593,11 +589,8 @@ class ConsensusEngine:
 
     def _early_update(self, b: Bucket) -> None:
         """Gossip, V == 1: this bucket's local optimizer step on the side stream."""
-        fl = self.flat
         if self.cfg.fault.kind != "none":
-            apply_faults(fl.flat_grad, self.cfg.fault, self.rank, self.step_count,
-                         self.group_active, self.cfg.seed + self.step_count,
-                         cols=slice(b.offset, b.offset + b.length))
+            self._inject(b)
         st = self._opt_stream
         st.wait_stream(torch.cuda.current_stream(self.device))
         with torch.cuda.stream(st):
@@ -617,12 +610,16 @@ class ConsensusEngine:
                 self._flush(b, complete=False)
         self._flushed.clear()
 
+    def _inject(self, b: Optional[Bucket] = None) -> None:
+        """This step's fault injection into the local gradient rows: bucket b's columns, or all."""
+        cols = slice(b.offset, b.offset + b.length) if b is not None else None
+        apply_faults(self.flat.flat_grad, self.cfg.fault, self.rank, self.step_count,
+                     self.group_active, self.cfg.seed + self.step_count, cols=cols)
+
     def _launch_bucket(self, b: Bucket, inject: bool) -> None:
         fl = self.flat
         if inject and self.cfg.fault.kind != "none":
-            apply_faults(fl.flat_grad, self.cfg.fault, self.rank, self.step_count,
-                         self.group_active, self.cfg.seed + self.step_count,
-                         cols=slice(b.offset, b.offset + b.length))
+            self._inject(b)
         if not self.group_active or self.topo == "gossip":
             self._pending[b.index] = None
             return
@@ -666,16 +663,14 @@ class ConsensusEngine:
                                                           self._pass_center())
         else:
             X = self._cclip_rows(b) if self.rule == "centered_clip" else self._rows(b)
-            length = b.shard if self.topo == "sharded" else X.shape[1]
-            K.gram(X, n=self.rows_total, D=length, out=self.Gb[b.index],
+            K.gram(X, n=self.rows_total, D=self._length(b), out=self.Gb[b.index],
                    center=self._pass_center())
         self._gram_done.add(b.index)
 
     def _gram_args(self, b: Bucket):
         hit = self._gram_arg_cache.get(b.index)
         if hit is None:
-            X = self._rows(b)
-            length = b.shard if self.topo == "sharded" else X.shape[1]
+            X, length = self._rows(b), self._length(b)
             if X.data_ptr() % 16 or (X.stride(0) * X.element_size()) % 16 or X.stride(1) != 1:
                 hit = False          # unaligned rows: K.gram pads a copy every call
             else:
@@ -724,17 +719,18 @@ class ConsensusEngine:
     # ================================================================ robust weights
     def _rows(self, b: Bucket) -> torch.Tensor:
         """Worker matrix of bucket b as seen by this rank ([rows_total, cols])."""
-        fl = self.flat
-        if self.topo == "sharded":
-            if not self.group_active:
-                # world 1: the local rows ARE the full workers; shard == bucket
-                return fl.flat_grad[:, b.offset:b.offset + b.length]
-            return self.recv[b.index]
-        if self.topo == "allgather":
-            if not self.group_active:
-                return fl.flat_grad[:, b.offset:b.offset + b.length]
-            return self.recv[b.index]
-        raise RuntimeError("no worker matrix for this topology")
+        if self.topo not in ("sharded", "allgather"):
+            raise RuntimeError("no worker matrix for this topology")
+        if not self.group_active:
+            # world 1: the local rows ARE the full workers; shard == bucket
+            return self.flat.flat_grad[:, b.offset:b.offset + b.length]
+        return self.recv[b.index]
+
+    def _length(self, b: Bucket) -> int:
+        """Columns of bucket b in this rank's worker matrix: its shard of the sharded exchange,
+        else the whole bucket. (No process group means one rank, and FlatModel's shard is
+        length // world, so the local rows of ``_rows`` are ``b.shard`` wide as well.)"""
+        return b.shard if self.topo == "sharded" else b.length
 
     def _cclip_rows(self, b: Bucket) -> torch.Tensor:
         """Worker rows plus the previous-aggregate row (centered clipping)."""
@@ -779,8 +775,7 @@ class ConsensusEngine:
             self.G.zero_()
             for b, X, length in cols:
                 K.gram(X, n=self.rows_total, D=length, out=self.G, accumulate=True, center=center)
-        if self.group_active and self.topo == "sharded" and self.N > 1:
-            dist.all_reduce(self.G)      # (one rank: the sum over ranks is G itself)
+        self._reduce_G()
         if cfg.centered_gram and center is None:
             # no medoid yet (first step) or the two-pass scheme: a second pass relative to the
             # medoid of the uncentered G -- exact distances for near-duplicate workers (the rules
@@ -790,10 +785,9 @@ class ConsensusEngine:
             for b, X, length in cols:
                 K.gram(X, n=self.rows_total, D=length, out=self.G, accumulate=True,
                        center=self.center)
-            if self.group_active and self.topo == "sharded" and self.N > 1:
-                dist.all_reduce(self.G)
+            self._reduce_G()
         rule = "bulyan_select" if self.rule == "bulyan" else self.rule
-        if self.rule not in GRAM_RULES:
+        if self.rule not in GRAM_PASS_RULES:
             rule = "nnm_only"    # a coordinate rule with agg.pre=nnm: the mixing matrix only
         m = cfg.m if cfg.m is not None else self.n - cfg.f
         iters = cfg.clip_iters if rule == "centered_clip" else cfg.iters
@@ -811,55 +805,38 @@ class ConsensusEngine:
         if cfg.centered_gram:
             self.have_center = True
 
-    def _bucket_cols(self) -> list:
-        out = []
-        for b in self.flat.buckets:
-            if self.rule == "centered_clip":
-                X = self._cclip_rows(b)
-            else:
-                X = self._rows(b)
-            length = b.shard if (self.topo == "sharded" and self.group_active) else X.shape[1]
-            out.append((b, X, length))
-        return out
+    def _reduce_G(self) -> None:
+        """Sharded across ranks: sum the shards' partial Grams (one rank: G is the sum already)."""
+        if self.group_active and self.topo == "sharded" and self.N > 1:
+            dist.all_reduce(self.G)
 
-    def _aggregate_update(self, b: Bucket, X: torch.Tensor, length: int, state_off: int,
-                          param_out: torch.Tensor, opt: K.OptArgs,
-                          gout: Optional[torch.Tensor]) -> None:
+    def _bucket_cols(self) -> list:
+        rows = self._cclip_rows if self.rule == "centered_clip" else self._rows
+        return [(b, rows(b), self._length(b)) for b in self.flat.buckets]
+
+    @functools.cached_property
+    def _combine(self) -> K.Combine:
+        """The rule's share of every aggregation launch, over the persistent w / sel / M. Built
+        on first use, not in __init__: cfg.validate() accepts bulyan on a single worker with
+        f > 0, whose trimmed window does not exist, and that keeps failing in step()."""
         cfg = self.cfg.agg
+        return K.rule_combine(self.rule, self.n, cfg.f, cfg.trim, w=self.w, sel=self.sel,
+                              mix=self.M, rows_total=self.rows_total)
+
+    def _aggregate_update(self, X: torch.Tensor, length: int, state_off: int,
+                          param_out: Optional[torch.Tensor], opt: K.OptArgs,
+                          gout: Optional[torch.Tensor]) -> None:
         m, s1, s2 = self._state(state_off, length) if opt.kind != "none" else (None, None, None)
-        if self.rule in K.COORD_RULES:
-            lo, cnt, keep = K.near_range(self.rule, self.n, cfg.f, cfg.trim)
-            K.agg_update(X, combine="sorted", lo=lo, cnt=cnt, n=self.n, D=length, opt=opt,
-                         master=m, s1=s1, s2=s2, param_out=param_out, gout=gout, mix=self.M, keep=keep)
-        elif self.rule == "bulyan":
-            theta = self.n - 2 * cfg.f
-            lo, cnt = K.sorted_range("trimmed_mean", theta, cfg.f)
-            K.agg_update(X, combine="sorted", lo=lo, cnt=cnt, rows=self.sel[:theta], n=theta,
-                         D=length, opt=opt, master=m, s1=s1, s2=s2, param_out=param_out,
-                         gout=gout)
-        else:  # mean and Gram-space rules: weighted
-            K.agg_update(X, combine="weighted", w=self.w, n=self.rows_total, D=length, opt=opt,
-                         master=m, s1=s1, s2=s2, param_out=param_out, gout=gout)
+        K.agg_update(X, D=length, opt=opt, master=m, s1=s1, s2=s2, param_out=param_out,
+                     gout=gout, **self._combine.kwargs())
 
     def _aggregate_update_multi(self, segs, opt: K.OptArgs,
                                 gout: Optional[torch.Tensor] = None) -> None:
-        """``_aggregate_update`` of several buckets in one launch: segs = (X, length, pout, soff)."""
-        cfg = self.cfg.agg
-        ks = [(X, length, soff, pout) for X, length, pout, soff in segs]
-        st = dict(master=self.master, s1=self.s1, s2=self.s2, opt=opt, gout=gout)
-        if opt.kind == "none":
-            st.update(master=None, s1=None, s2=None)
-        if self.rule in K.COORD_RULES:
-            lo, cnt, keep = K.near_range(self.rule, self.n, cfg.f, cfg.trim)
-            K.agg_update_multi(ks, combine="sorted", lo=lo, cnt=cnt, n=self.n, mix=self.M, keep=keep,
-                               **st)
-        elif self.rule == "bulyan":
-            theta = self.n - 2 * cfg.f
-            lo, cnt = K.sorted_range("trimmed_mean", theta, cfg.f)
-            K.agg_update_multi(ks, combine="sorted", lo=lo, cnt=cnt, rows=self.sel[:theta],
-                               n=theta, **st)
-        else:
-            K.agg_update_multi(ks, combine="weighted", w=self.w, n=self.rows_total, **st)
+        """``_aggregate_update`` of several buckets in one launch: segs = (X, length, state
+        offset, param_out)."""
+        m, s1, s2 = (self.master, self.s1, self.s2) if opt.kind != "none" else (None, None, None)
+        K.agg_update_multi(segs, opt=opt, master=m, s1=s1, s2=s2, gout=gout,
+                           **self._combine.kwargs())
 
     # ================================================================ global-norm clipping
     def _clip_weight(self, segments, scale: float, reduce: bool = False) -> None:
@@ -901,28 +878,32 @@ class ConsensusEngine:
         K.agg_update(fl.flat_grad[0], combine="weighted", n=1, opt=opt, master=m, s1=s1, s2=s2,
                      param_out=fl.flat_param)
 
-    def _step_allgather(self) -> None:
+    def _place(self, b: Bucket):
+        """(offset into master / s1 / s2 / gout, bf16 parameters) that bucket b's update writes:
+        this rank's shard in the sharded topology across ranks, else the whole bucket."""
         fl = self.flat
-        for b in fl.buckets:
-            self._wait(b)
-        cols = self._bucket_cols()
-        if self.needs_gram:
-            self._compute_weights(cols)
-        if self.record_stats:
-            self._record_stats(cols)
-        opt = self._opt_args() if not self.clip else K.OptArgs(kind="none")
-        for b, X, length in cols:
-            gout = self.gout[b.offset:b.offset + b.length] if self.gout is not None else None
-            self._aggregate_update(b, X, length, b.offset, fl.flat_param[b.offset:b.offset + b.length],
-                                   opt, gout)
-            if self.rule == "centered_clip":
-                X[self.n].copy_(gout.to(X.dtype))   # v0 <- new (unclipped) aggregate
-        if self.clip:       # every rank holds the full aggregate: no collective
-            self._clipped_row_update(self.gout, 1.0)
+        if self.topo == "sharded" and self.group_active:
+            return b.shard_offset, fl.my_shard(fl.flat_param, b, self.rank)
+        return b.offset, fl.flat_param[b.offset:b.offset + b.length]
 
-    def _step_sharded(self) -> None:
-        fl = self.flat
-        for b in fl.buckets:
+    def _gather_params(self, b: Bucket, pout: torch.Tensor, works: list) -> None:
+        """Sharded across ranks: all-gather bucket b's updated parameter shards in place; the
+        work is left to the next forward's hooks (param_prefetch) or appended to ``works``."""
+        if not (self.topo == "sharded" and self.group_active and self.N > 1):
+            return      # (one rank: the shard IS the bucket, the gather would copy it onto itself)
+        full = self.flat.flat_param[b.offset:b.offset + b.length]
+        work = dist.all_gather_into_tensor(full, pout, async_op=True)
+        if self.param_prefetch:
+            self._ag_works[b.index] = work
+        else:
+            works.append(work)
+
+    def _step_rows(self) -> None:
+        """allgather / sharded: the rule over every bucket's worker rows, fused with the
+        optimizer step -- or, clipping, as the three stages of the module docstring -- and,
+        sharded across ranks, the parameter all-gathers."""
+        sharded = self.topo == "sharded"
+        for b in self.flat.buckets:
             self._wait(b)
         cols = self._bucket_cols()
         if self.needs_gram:
@@ -930,53 +911,40 @@ class ConsensusEngine:
         if self.record_stats:
             self._record_stats(cols)
         opt = self._opt_args()
-        works = []
-        order = list(reversed(cols)) if self.param_prefetch else cols
-
-        def shard(b):
-            if self.group_active:
-                return fl.my_shard(fl.flat_param, b, self.rank), b.shard_offset
-            return fl.flat_param[b.offset:b.offset + b.length], b.offset
-
-        # every bucket's rule + optimizer step in ONE launch (centered clipping writes its
-        # aggregate back into each bucket's rows, so it stays per bucket)
-        fused = self.rule != "centered_clip" and 1 <= len(cols) <= 16 and self.device.type == "cuda"
         rule_opt = opt if not self.clip else K.OptArgs(kind="none")    # clipping: stage 1 only
+        # prefetch: earliest layers (highest bucket index) first, the next forward needs them first
+        order = list(reversed(cols)) if self.param_prefetch else cols
+        segs = [(b, X, length) + self._place(b) for b, X, length in order]
+        # sharded: every bucket's rule + optimizer step in ONE launch (centered clipping writes
+        # its aggregate back into each bucket's rows, so it stays per bucket)
+        fused = (sharded and self.rule != "centered_clip" and 1 <= len(cols) <= 16
+                 and self.device.type == "cuda")
         if fused:
-            self._aggregate_update_multi([(X, length) + shard(b) for b, X, length in order],
-                                         rule_opt, gout=self.gout if self.clip else None)
-        if self.clip:
-            for b, X, length in ([] if fused else order):
-                _, soff = shard(b)
-                gout = self.gout[soff:soff + length]
-                self._aggregate_update(b, X, length, soff, None, rule_opt, gout)
-                if self.rule == "centered_clip":
-                    X[self.n, :length].copy_(gout.to(X.dtype))    # v0 <- the UNCLIPPED aggregate
+            self._aggregate_update_multi([s[1:] for s in segs], rule_opt,
+                                         gout=self.gout if self.clip else None)
+        works = []
+        for b, X, length, off, pout in segs:
+            if not fused:
+                gout = self.gout[off:off + length] if self.gout is not None else None
+                # (the sharded stage 1 names no parameters; allgather's does, unused)
+                self._aggregate_update(X, length, off, None if sharded and self.clip else pout,
+                                       rule_opt, gout)
+                if self.rule == "centered_clip":    # v0 <- the new, UNCLIPPED aggregate
+                    (X[self.n, :length] if sharded else X[self.n]).copy_(gout.to(X.dtype))
+            if not self.clip:       # the parameters follow their update at once
+                self._gather_params(b, pout, works)
+        if self.clip and sharded:
             # stage 2 over this rank's shards (N > 1: + one all-reduce of the fp64 scalar), then
             # stage 3: ONE weighted launch (n = 1, w = w_clip) over the gout segments
             self._clip_weight([self.gout], 1.0, reduce=self._norm2_red is not None)
-            segs = []
-            for b, X, length in order:
-                pout, soff = shard(b)
-                segs.append((self.gout[soff:soff + length], length, soff, pout))
-            K.agg_update_multi(segs, combine="weighted", w=self.w_clip, n=1, opt=opt,
-                               master=self.master, s1=self.s1, s2=self.s2)
-        # earliest layers (highest bucket index) first: the next forward needs them first
-        for b, X, length in order:
-            pout, soff = shard(b)
-            if not fused and not self.clip:
-                gout = self.gout[soff:soff + length] if self.gout is not None else None
-                self._aggregate_update(b, X, length, soff, pout, opt, gout)
-                if self.rule == "centered_clip":
-                    X[self.n, :length].copy_(gout.to(X.dtype))
-            if self.group_active and self.N > 1:
-                # (one rank: the shard IS the bucket, the gather would copy it onto itself)
-                full = fl.flat_param[b.offset:b.offset + b.length]
-                work = dist.all_gather_into_tensor(full, pout, async_op=True)
-                if self.param_prefetch:
-                    self._ag_works[b.index] = work
-                else:
-                    works.append(work)
+            K.agg_update_multi([(self.gout[off:off + length], length, off, pout)
+                                for _, _, length, off, pout in segs], combine="weighted",
+                               w=self.w_clip, n=1, opt=opt, master=self.master, s1=self.s1,
+                               s2=self.s2)
+            for b, _, _, _, pout in segs:
+                self._gather_params(b, pout, works)
+        elif self.clip:     # every rank holds the full aggregate: no collective
+            self._clipped_row_update(self.gout, 1.0)
         for w in works:
             w.wait()
 
@@ -1137,21 +1105,8 @@ class ConsensusEngine:
 
     def _aggregate_only(self, b: Bucket, X: torch.Tensor, length: int) -> torch.Tensor:
         """The rule's aggregate of bucket b's local columns (fp32), without an update."""
-        cfg = self.cfg.agg
         out = torch.empty(length, dtype=torch.float32, device=X.device)
-        none = K.OptArgs(kind="none")
-        if self.rule in K.COORD_RULES:
-            lo, cnt, keep = K.near_range(self.rule, self.n, cfg.f, cfg.trim)
-            K.agg_update(X, combine="sorted", lo=lo, cnt=cnt, n=self.n, D=length, opt=none,
-                         gout=out, mix=self.M, keep=keep)
-        elif self.rule == "bulyan":
-            theta = self.n - 2 * cfg.f
-            lo, cnt = K.sorted_range("trimmed_mean", theta, cfg.f)
-            K.agg_update(X, combine="sorted", lo=lo, cnt=cnt, rows=self.sel[:theta], n=theta,
-                         D=length, opt=none, gout=out)
-        else:
-            K.agg_update(X, combine="weighted", w=self.w, n=self.rows_total, D=length, opt=none,
-                         gout=out)
+        K.agg_update(X, D=length, opt=K.OptArgs(kind="none"), gout=out, **self._combine.kwargs())
         return out
 
     def _record_stats(self, cols) -> None:
@@ -1183,7 +1138,9 @@ class ConsensusEngine:
         self.last_stats = {"names": [s[0] for s in segs], "sqnorm": sq.cpu(), "dist2": dd.cpu(),
                            "agg_sqnorm": ag.cpu(), "step": self.step_count,
                            "weights": self.w[:n].double().cpu(),
-                           "scores": self.scores[:n].cpu() if self.rule in GRAM_RULES else None,
+                           # the Gram-pass set, not K.WEIGHT_RULES: bulyan reports Krum scores too
+                           "scores": (self.scores[:n].cpu() if self.rule in GRAM_PASS_RULES
+                                      else None),
                            "sel_counts": self.sel_counts.cpu().clone()}
         self.record_stats = False
 

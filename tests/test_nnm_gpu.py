@@ -22,12 +22,12 @@ from agg_oracle import (GUARD, OPTS, TOL_ADAM_M, TOL_ADAM_V, TOL_MASTER, TOL_SGD
 from consensusml_amd import TrainConfig
 from consensusml_amd.ops import kernels as K
 from consensusml_amd.ops import reference as ref
+from consensusml_amd.ops.kernels import WEIGHT_RULES as GRAM_RULES
 from consensusml_amd.parallel.dist import DistInfo
 from consensusml_amd.parallel.engine import ConsensusEngine
 
 pytestmark = pytest.mark.gpu
 
-GRAM_RULES = ("krum", "multi_krum", "geomed", "centered_clip")
 CPU = torch.device("cpu")
 
 
