@@ -281,106 +281,105 @@ class Bottleneck(nn.Module):
             return conv(x, res_link=link if conv.link_ok(x) else None), None
         return conv(x), None
 
-    def _forward_fused(self, x: torch.Tensor, use_links: bool) -> torch.Tensor:
-        """Training forward with the fused conv + BN kernels (ops.conv): bn1 / bn3 / down_bn get
-        their statistics from the conv epilogues, bn2 + ReLU is applied inside conv3."""
+    def _tap(self, x: torch.Tensor, dlink, use_links: bool) -> torch.Tensor:
+        """x as down_conv reads it: its dX parks on conv1's link ``dlink`` or, when x is the
+        fused stem's output, on the stem's pool link (ops.stem._StemFn takes it as a second
+        gradient); without either, x itself."""
+        tlink = dlink if dlink is not None else \
+            (getattr(x, "_cml_pool_link", None) if use_links else None)
+        return link_tap(x, tlink) if tlink is not None else x
+
+    def _head(self, x: torch.Tensor, use_links: bool):
+        """conv1 -> (z1, bn1's statistics or None, link, dlink). ``link``: the one our producer
+        made for x (identity block: bn3 parks the residual gradient there); ``dlink``: a new one
+        on which a downsample block's shortcut parks its dX for conv1's data-gradient GEMM."""
+        link = dlink = None
         if self.down_conv is None:
             link = getattr(x, "_cml_link", None) if use_links else None
-            z1, st1 = self._conv_bn(x, self.conv1, self.bn1, link)
-            dlink = None
-        else:
-            link = None
-            dlink = ResidualLink() if use_links and self.conv1.link_ok(x) else None
-            z1, st1 = self._conv_bn(x, self.conv1, self.bn1, dlink)
-        planes = self.conv3.in_channels
-        hw2 = (z1.shape[2] // self.conv2.stride[0]) * (z1.shape[3] // self.conv2.stride[0])
-        fuse3 = fused_conv1x1_policy(planes, planes * 4, hw2, 1, True)
+        elif use_links and self.conv1.link_ok(x):
+            dlink = ResidualLink()
+        z1, st1 = self._conv_bn(x, self.conv1, self.bn1, link if dlink is None else dlink)
+        return z1, st1, link, dlink
+
+    def _conv2_fused(self, z1: torch.Tensor, st1, fuse3: bool):
+        """bn1 + ReLU + conv2 -> (z2, bn2's statistics or None)."""
         pol = _P()
-        own3 = (fuse3 and pol.conv3x3_bn_stats and pol.own_dgrad3x3
-                and fconv.conv3x3_ok(z1, self.conv2))
-        if (own3 and pol.bn1_dgrad_sums and st1 is None and pol.bn1_sums_lib_conv1
-                and self.bn1.training and fused_ok(z1, self.bn1.weight)):
+        s1 = self.conv2.stride == (1, 1)
+        on = (pol.conv3x3_bn_stats and pol.own_dgrad3x3) if s1 else pol.own_conv3x3_s2
+        own3 = fuse3 and on and fconv.conv3x3_ok(z1, self.conv2)
+        pro = (own3 and pol.bn1_dgrad_sums and self.bn1.training
+               and fused_ok(z1, self.bn1.weight))
+        if pro and s1 and st1 is None and pol.bn1_sums_lib_conv1:
             # conv1 ran on the library (layers 3-4, 14 x 14 / 7 x 7): one statistics pass here
             # (the module BN would make the same one), so that bn1's backward also takes its sums
             # from the 3x3 data gradient's epilogue instead of a reduction pass over dy1 and z1
             st1 = fconv.bn_stats(z1, self.bn1)
-        own3s2 = (fuse3 and not own3 and pol.own_conv3x3_s2
-                  and fconv.conv3x3_s2_ok(z1, self.conv2))
-        if own3 and pol.bn1_dgrad_sums and st1 is not None and self.bn1.training:
-            # bn1's backward sums come from the 3x3 data gradient's epilogue
-            z2, st2 = fconv.bnrelu_conv3x3_bn_stats(z1, self.bn1, st1, self.conv2, self.bn2)
-        elif (own3s2 and pol.bn1_dgrad_sums and st1 is not None and self.bn1.training
-                and fused_ok(z1, self.bn1.weight)):
-            # stride-2 conv of a downsample block: the same, with the parity-class data gradient
-            z2, st2 = fconv.bnrelu_conv3x3_s2_bn_stats(z1, self.bn1, st1, self.conv2, self.bn2)
-        elif own3s2:
-            z2, st2 = fconv.conv3x3_s2_bn_stats(self.bn1(z1, stats=st1), self.conv2, self.bn2)
+        if pro and st1 is not None:
+            # bn1's backward sums come from the 3x3 data gradient's epilogue (stride 2: the
+            # parity-class one)
+            return fconv.bnrelu_conv3x3_bn_stats(z1, self.bn1, st1, self.conv2, self.bn2)
+        out = self.bn1(z1, stats=st1)
+        if own3:
+            return fconv.conv3x3_bn_stats(out, self.conv2, self.bn2)
+        z2 = self._conv2(out)
+        return z2, (fconv.bn_stats(z2, self.bn2) if fuse3 else None)
+
+    def _tail_fused(self, x, z2, st2, fuse3: bool, hw2: int, link, dlink, use_links: bool,
+                    out_link) -> torch.Tensor:
+        """bn2 + ReLU + conv3 + bn3 + shortcut + ReLU."""
+        planes = self.conv3.in_channels
+        down = self.down_conv
+        if not fuse3:
+            z, st3 = self.conv3(self.bn2(z2)), None
         else:
-            out = self.bn1(z1, stats=st1)
-            if own3:
-                z2, st2 = fconv.conv3x3_bn_stats(out, self.conv2, self.bn2)
-            else:
-                z2 = self._conv2(out)
-                st2 = fconv.bn_stats(z2, self.bn2) if fuse3 else None
-        if fuse3:
-            rec = self.down_conv is None and recompute_tail_policy(planes)
-            if rec or (self.down_conv is None and fused_bn3_bwd_policy(planes)):
-                out_link = ResidualLink() if use_links else None
-                tail = fconv.bnrelu_conv1x1_bn_res_recompute if rec \
-                    else fconv.bnrelu_conv1x1_bn_res
-                y = tail(z2, self.bn2, st2, self.conv3, self.bn3, x, link, out_link)
-                if out_link is not None:
-                    y._cml_link = out_link
-                return y
-            if (self.down_conv is not None and pol.recompute_down_tail and self.bn3.eps ==
-                    self.down_bn.eps and fconv.down_tail_recompute_s2_ok(x, planes, self.down_conv)):
-                # stride-2 downsample tail: the stride-1 recompute kernels on x[:, :, ::2, ::2];
-                # its gradient (zero-filled full resolution) parks on conv1's link as before
-                out_link = ResidualLink() if use_links else None
-                y = fconv.down_tail_recompute(z2, self.bn2, st2, self.conv3, self.bn3,
-                                              fconv.subsample2_link(x, dlink), self.down_conv,
-                                              self.down_bn, out_link)
-                if out_link is not None:
-                    y._cml_link = out_link
-                return y
-            if (self.down_conv is not None and pol.recompute_down_tail and self.bn3.eps ==
-                    self.down_bn.eps and fconv.down_tail_recompute_ok(x, planes, self.down_conv)):
-                out_link = ResidualLink() if use_links else None
-                tlink = dlink if dlink is not None else \
-                    (getattr(x, "_cml_pool_link", None) if use_links else None)
-                xin = link_tap(x, tlink) if tlink is not None else x
-                y = fconv.down_tail_recompute(z2, self.bn2, st2, self.conv3, self.bn3, xin,
-                                              self.down_conv, self.down_bn, out_link)
-                if out_link is not None:
-                    y._cml_link = out_link
-                return y
+            if down is None:
+                rec = recompute_tail_policy(planes)
+                if rec or fused_bn3_bwd_policy(planes):
+                    tail = fconv.bnrelu_conv1x1_bn_res_recompute if rec \
+                        else fconv.bnrelu_conv1x1_bn_res
+                    return tail(z2, self.bn2, st2, self.conv3, self.bn3, x, link, out_link)
+            elif _P().recompute_down_tail and self.bn3.eps == self.down_bn.eps:
+                xd = None
+                if fconv.down_tail_recompute_s2_ok(x, planes, down):
+                    # stride 2: the stride-1 recompute kernels on x[:, :, ::2, ::2]; its gradient
+                    # parks compact on conv1's link
+                    xd = fconv.subsample2_link(x, dlink)
+                elif fconv.down_tail_recompute_ok(x, planes, down):
+                    xd = self._tap(x, dlink, use_links)
+                if xd is not None:
+                    return fconv.down_tail_recompute(z2, self.bn2, st2, self.conv3, self.bn3, xd,
+                                                     down, self.down_bn, out_link)
             dg = conv1x1_policy(planes, planes * 4, hw2)[1]
             z, m3, i3 = fconv.bnrelu_conv1x1_bn_stats(z2, self.bn2, st2, self.conv3, self.bn3, dg,
                                                       own_wgrad_ok(planes, planes * 4)
                                                       or planes == 64)
             st3 = (m3, i3)
+        if down is None:
+            return self.bn3(z, residual=x, res_link=link, out_link=out_link, stats=st3)
+        if self._down_s2_compact_ok(x, dlink):
+            zd, std = self._down_conv_s2_compact(x, dlink), None
         else:
-            z, st3 = self.conv3(self.bn2(z2)), None
+            zd, std = self._conv_bn(self._tap(x, dlink, use_links), down, self.down_bn)
+        if (st3 is None) != (std is None):
+            # one side fused, the other not: let the unfused side compute its statistics
+            return self.bn3(z, residual=self.down_bn(zd, stats=std), out_link=out_link, stats=st3)
+        stats = None if st3 is None else st3 + std
+        return bn_add_bn_relu(z, self.bn3, zd, self.down_bn, out_link, stats=stats)
+
+    def _forward_fused(self, x: torch.Tensor, use_links: bool) -> torch.Tensor:
+        """Training forward with the fused conv + BN kernels (ops.conv): bn1 / bn3 / down_bn get
+        their statistics from the conv epilogues, bn2 + ReLU is applied inside conv3. Three
+        stages; each picks its rung once its input exists (a library conv's output layout is only
+        known then)."""
+        z1, st1, link, dlink = self._head(x, use_links)
+        planes, s = self.conv3.in_channels, self.conv2.stride[0]
+        hw2 = (z1.shape[2] // s) * (z1.shape[3] // s)
+        fuse3 = fused_conv1x1_policy(planes, planes * 4, hw2, 1, True)
+        z2, st2 = self._conv2_fused(z1, st1, fuse3)
         out_link = ResidualLink() if use_links else None
-        if self.down_conv is None:
-            y = self.bn3(z, residual=x, res_link=link, out_link=out_link, stats=st3)
-        else:
-            tlink = dlink if dlink is not None else \
-                (getattr(x, "_cml_pool_link", None) if use_links else None)
-            if self._down_s2_compact_ok(x, dlink):
-                zd, std = self._down_conv_s2_compact(x, dlink), None
-            else:
-                xin = link_tap(x, tlink) if tlink is not None else x
-                zd, std = self._conv_bn(xin, self.down_conv, self.down_bn)
-            stats = None if (st3 is None or std is None) else st3 + std
-            if stats is None and (st3 is not None or std is not None):
-                # one side fused, the other not: let the unfused side compute its statistics
-                y = self.bn3(z, residual=self.down_bn(zd, stats=std), out_link=out_link,
-                             stats=st3)
-            else:
-                y = bn_add_bn_relu(z, self.bn3, zd, self.down_bn, out_link, stats=stats)
+        y = self._tail_fused(x, z2, st2, fuse3, hw2, link, dlink, use_links, out_link)
         if out_link is not None:
-            y._cml_link = out_link
+            y._cml_link = out_link      # our consumer (an identity block) parks dres here
         return y
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
@@ -405,14 +404,10 @@ class Bottleneck(nn.Module):
             # autograd (ready nodes in reverse creation order) runs its backward first; the link
             # falls back to a normal add if that order ever changes.
             dlink = ResidualLink() if use_links and self.conv1.link_ok(x) else None
-            # otherwise, when x is the fused stem's output, its pool backward takes the parked
-            # gradient as a second input (ops.stem._StemFn)
-            tlink = dlink if dlink is not None else \
-                (getattr(x, "_cml_pool_link", None) if use_links else None)
             out = self.bn1(self.conv1(x, res_link=dlink))
             out = self.bn2(self._conv2(out))
             z = self.conv3(out)
-            zd = self.down_conv(link_tap(x, tlink) if tlink is not None else x)
+            zd = self.down_conv(self._tap(x, dlink, use_links))
             out_link = ResidualLink() if use_links and fused_ok(z, self.bn3.weight) else None
             # relu(bn3(z) + down_bn(zd)) in one op: the shortcut BN output is never stored
             y = bn_add_bn_relu(z, self.bn3, zd, self.down_bn, out_link) if _P().fuse_down_bn \

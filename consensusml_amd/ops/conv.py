@@ -235,6 +235,33 @@ class _BNReLUConv1x1BNStatsFn(torch.autograd.Function):
         return dz, dg, db, None, None, dw, None, None, None, None, None, None
 
 
+def _take_out_link(ol, gy: torch.Tensor):
+    """A tail backward's output gradient: ``gy`` (NHWC) plus whatever the consumer block parked on
+    ``out_link``, which is cleared. Also returns bn3's backward sums when the consumer's conv1
+    data-gradient epilogue left them there for exactly this ``gy`` (``masked_link_dgrad``), else
+    None."""
+    gy = gy.contiguous(memory_format=torch.channels_last)
+    sums = None
+    if ol is not None:
+        extra = ol.take_tensor()
+        if ol.sums is not None and extra is None and ol.sums[2] == gy.data_ptr():
+            sums = ol.sums
+        ol.sums = ol.bn_ctx = None
+        if extra is not None:
+            gy = (gy + extra).contiguous(memory_format=torch.channels_last)
+    return gy, sums
+
+
+def _park_masked(gy: torch.Tensor, mask: torch.Tensor, res_link) -> Optional[torch.Tensor]:
+    """The residual gradient m * g of a tail: parked on ``res_link`` as a ``MaskedGrad`` for the
+    block's conv1 data-gradient epilogue (returns None), or materialised."""
+    mg = MaskedGrad(gy, mask)
+    if res_link is not None and not res_link.closed and res_link.grad is None:
+        res_link.grad = mg
+        return None
+    return mg.materialize()
+
+
 class _BNReLUConv1x1BNResFn(torch.autograd.Function):
     """Identity-block tail y = relu(bn3(conv3(relu(bn2(z2)))) + res) with bn3's backward applied
     inside conv3's gradient kernels.
@@ -264,15 +291,7 @@ class _BNReLUConv1x1BNResFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gy):
         z, g2, b2, mean2, invstd2, w, sc, bi, z3, mask, g3, b3, m3, i3 = ctx.saved_tensors
-        gy = gy.contiguous(memory_format=torch.channels_last)
-        sums, ol = None, ctx.out_link
-        if ol is not None:
-            extra = ol.take_tensor()
-            if ol.sums is not None and extra is None and ol.sums[2] == gy.data_ptr():
-                sums = ol.sums
-            ol.sums = ol.bn_ctx = None
-            if extra is not None:
-                gy = (gy + extra).contiguous(memory_format=torch.channels_last)
+        gy, sums = _take_out_link(ctx.out_link, gy)
         M = gy.numel() // gy.shape[1]
         if sums is None:
             sums = lib().bn_bwd_sums(gy, None, z3, mask, g3, b3, m3, i3, True)
@@ -283,13 +302,7 @@ class _BNReLUConv1x1BNResFn(torch.autograd.Function):
             dw = lib().wgrad1x1(gy, z, w.dtype, sc, bi, z3, mask, ca, cb, cc).view_as(w)
         dy2 = lib().conv1x1_bnbwd(gy, z3, mask, ca, cb, cc, w.reshape(Co, Ci).t().contiguous())
         dz, dg2, db2, _ = lib().bn_bwd(dy2, None, z, None, g2, b2, mean2, invstd2, True, False)
-        dres = None
-        if ctx.needs_input_grad[8]:
-            mg = MaskedGrad(gy, mask)
-            if ctx.res_link is not None and not ctx.res_link.closed and ctx.res_link.grad is None:
-                ctx.res_link.grad = mg
-            else:
-                dres = mg.materialize()
+        dres = _park_masked(gy, mask, ctx.res_link) if ctx.needs_input_grad[8] else None
         return (dz, dg2, db2, None, None, dw, dg3, db3, dres) + (None,) * 6
 
 
@@ -465,13 +478,7 @@ class _RecomputeTailFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gy):
         z, g2, b2, mean2, invstd2, w, sc, bi, mask, g3, m3, i3 = ctx.saved_tensors
-        gy = gy.contiguous(memory_format=torch.channels_last)
-        ol = ctx.out_link
-        if ol is not None:
-            extra = ol.take_tensor()
-            ol.sums = ol.bn_ctx = None
-            if extra is not None:
-                gy = (gy + extra).contiguous(memory_format=torch.channels_last)
+        gy, _ = _take_out_link(ctx.out_link, gy)
         M = gy.numel() // gy.shape[1]
         Co = w.shape[0]
         dev = gy.device
@@ -489,13 +496,7 @@ class _RecomputeTailFn(torch.autograd.Function):
                                                     need_dw)
         dw = dw.view_as(w) if need_dw else None
         dz, dg2, db2 = _cat_dgrad_bn2(L, gy, mask, z, sc, bi, w_cat, bias, g2, b2, mean2, invstd2)
-        dres = None
-        if ctx.needs_input_grad[8]:
-            mg = MaskedGrad(gy, mask)
-            if ctx.res_link is not None and not ctx.res_link.closed and ctx.res_link.grad is None:
-                ctx.res_link.grad = mg
-            else:
-                dres = mg.materialize()
+        dres = _park_masked(gy, mask, ctx.res_link) if ctx.needs_input_grad[8] else None
         return (dz, dg2, db2, None, None, dw, dg3, db3, dres) + (None,) * 6
 
 
@@ -557,13 +558,7 @@ class _RecomputeDownTailFn(torch.autograd.Function):
     def backward(ctx, gy):
         (z, g2, b2, mean2, invstd2, w3, sc, bi, mask, g3, m3, i3, x, wd, gd, md,
          idd) = ctx.saved_tensors
-        gy = gy.contiguous(memory_format=torch.channels_last)
-        ol = ctx.out_link
-        if ol is not None:
-            extra = ol.take_tensor()
-            ol.sums = ol.bn_ctx = None
-            if extra is not None:
-                gy = (gy + extra).contiguous(memory_format=torch.channels_last)
+        gy, _ = _take_out_link(ctx.out_link, gy)
         M = gy.numel() // gy.shape[1]
         Co = w3.shape[0]
         dev = gy.device
@@ -871,29 +866,30 @@ class _Conv3x3Fn(torch.autograd.Function):
     def backward(ctx, dy):
         x, w = ctx.saved_tensors
         dy = dy.contiguous(memory_format=torch.channels_last)
+        dgrad, wgrad = _BWD3X3[getattr(ctx, "stride", 1)]
         dx = dw = None
         if ctx.needs_input_grad[0]:
             # w_rot[ci][ky][kx][co] = w[co][ci][2 - ky][2 - kx], flattened k = tap Co + co
             wr = getattr(ctx, "wr", None)
             if wr is None:
                 wr = _w3x3_layouts(w, False)[1]
-            dx = lib().conv_gemm(dy, wr, 9, _zero_row(dy.device))
+            dx = dgrad(dy, wr)[0]
         if ctx.needs_input_grad[1]:
-            dw = _wgrad3x3(dy, x, w)
+            dw = wgrad(dy, x, w)
         return dx, dw
 
 
 class _Conv3x3BNStatsFn(torch.autograd.Function):
-    """(z, mean, invstd): 3x3 / stride 1 / padding 1 conv on ``conv_gemm.hip`` with the next BN's
-    training statistics accumulated in its epilogue (no separate statistics pass over z); backward
-    as ``_Conv3x3Fn``."""
+    """(z, mean, invstd): 3x3 / stride 1 or 2 / padding 1 conv on ``conv_gemm.hip`` (stride 2: its
+    stride-2 gather) with the next BN's training statistics accumulated in its epilogue (no
+    separate statistics pass over z); backward as ``_Conv3x3Fn``, by ``_BWD3X3[stride]``."""
 
     @staticmethod
-    def forward(ctx, x, w, rmean, rvar, eps, momentum, aff=None):
+    def forward(ctx, x, w, rmean, rvar, eps, momentum, stride=1, aff=None):
         wf, wr = _w3x3_layouts(w, True)   # both layouts now: the backward reuses wr
-        y, mean, invstd = _conv_gemm_bn(x, wf, rmean, rvar, eps, momentum, 1, aff)
+        y, mean, invstd = _conv_gemm_bn(x, wf, rmean, rvar, eps, momentum, stride, aff)
         ctx.save_for_backward(x, w)
-        ctx.wr = wr
+        ctx.wr, ctx.stride = wr, stride
         ctx.mark_non_differentiable(mean, invstd)
         ctx.set_materialize_grads(False)   # no zero-filled grads for the statistics outputs
         return y, mean, invstd
@@ -901,7 +897,7 @@ class _Conv3x3BNStatsFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy, _dm, _di):
         dx, dw = _Conv3x3Fn.backward(ctx, dy)
-        return dx, dw, None, None, None, None, None
+        return dx, dw, None, None, None, None, None, None
 
 
 def _conv_gemm_bn(x, wf, rmean, rvar, eps, momentum, stride, aff):
@@ -918,19 +914,20 @@ class _BNReLUConv3x3BNStatsFn(torch.autograd.Function):
     """(z2, mean2, invstd2) = conv3x3(relu(bn1(z1))) and bn2's training statistics, with bn1's
     batch statistics (mean1, invstd1) given by its producer. Forward as ``bn_act`` +
     ``_Conv3x3BNStatsFn`` (y1 is materialised: the implicit GEMM stages it with global_load_lds).
-    Backward: the 3x3 data-gradient GEMM also takes bn1's BN + ReLU backward sums in its epilogue
-    (``conv_gemm_bnsums``, ReLU bit recomputed from z1), so bn1's backward is its apply pass only
-    (the separate reduction re-read dy1 and z1)."""
+    Backward: the 3x3 data-gradient GEMM (stride 2: the parity-class one) also takes bn1's BN +
+    ReLU backward sums in its epilogue (``_BWD3X3``, ReLU bit recomputed from z1), so bn1's
+    backward is its apply pass only (the separate reduction re-read dy1 and z1)."""
 
     @staticmethod
-    def forward(ctx, z1, g1, b1, mean1, invstd1, eps1, w, rmean, rvar, eps, momentum, aff=None):
+    def forward(ctx, z1, g1, b1, mean1, invstd1, eps1, w, rmean, rvar, eps, momentum, stride=1,
+                aff=None):
         L = lib()
         y1 = L.bn_fwd(z1, None, g1, b1, None, None, mean1, invstd1, eps1, momentum, True, False,
                       False)[0]
         wf, wr = _w3x3_layouts(w, True)   # both layouts now: the backward reuses wr
-        z2, m2, i2 = _conv_gemm_bn(y1, wf, rmean, rvar, eps, momentum, 1, aff)
+        z2, m2, i2 = _conv_gemm_bn(y1, wf, rmean, rvar, eps, momentum, stride, aff)
         ctx.save_for_backward(z1, g1, b1, mean1, invstd1, y1, w)
-        ctx.wr = wr
+        ctx.wr, ctx.stride = wr, stride
         ctx.aff1 = _cached_affine(g1, b1, mean1)   # bn1's affine, for the backward
         ctx.mark_non_differentiable(m2, i2)
         ctx.set_materialize_grads(False)   # no zero-filled grads for the statistics outputs
@@ -941,20 +938,20 @@ class _BNReLUConv3x3BNStatsFn(torch.autograd.Function):
         z1, g1, b1, mean1, invstd1, y1, w = ctx.saved_tensors
         dz2 = dz2.contiguous(memory_format=torch.channels_last)
         L = lib()
-        wr = ctx.wr   # rotated / transposed layout, made by the forward
-        dw, h = _wgrad_fork(_wgrad3x3, dz2, y1, w) if ctx.needs_input_grad[6] else (None, None)
+        dgrad, wgrad = _BWD3X3[ctx.stride]
+        dw, h = _wgrad_fork(wgrad, dz2, y1, w) if ctx.needs_input_grad[6] else (None, None)
         sc, bi = ctx.aff1 or _affine(g1, b1, mean1, invstd1)
-        # bn1's parameter gradients come out of the sums' finalize launch (no bn_bwd_coeffs)
-        own_dgb = g1.dtype == torch.bfloat16 and b1.dtype == torch.bfloat16
-        dg1, db1 = (torch.empty_like(g1), torch.empty_like(b1)) if own_dgb else (None, None)
-        dy1, s1, q1 = L.conv_gemm_bnsums(dz2, wr, 9, _zero_row(dz2.device), z1, sc, bi, mean1,
-                                         invstd1, dg1, db1)
-        if not own_dgb:
+        bn1 = (z1, sc, bi, mean1, invstd1)
+        if _own_dgb(g1, b1):   # bn1's parameter gradients from the sums' finalize launch
+            dg1, db1 = torch.empty_like(g1), torch.empty_like(b1)
+            dy1, s1, q1 = dgrad(dz2, ctx.wr, *bn1, dg1, db1)
+        else:
+            dy1, s1, q1 = dgrad(dz2, ctx.wr, *bn1)
             M = z1.numel() // z1.shape[1]
             _, _, _, dg1, db1 = L.bn_bwd_coeffs(s1, q1, g1, mean1, invstd1, M)
         dz1 = L.bn_bwd_apply(dy1, z1, g1, b1, mean1, invstd1, s1, q1)
         dw = _wgrad_join(dw, h)
-        return dz1, dg1, db1, None, None, None, dw, None, None, None, None, None
+        return dz1, dg1, db1, None, None, None, dw, None, None, None, None, None, None
 
 
 def _wgrad3x3_s2(dy: torch.Tensor, x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
@@ -976,98 +973,24 @@ def _wgrad3x3_s2(dy: torch.Tensor, x: torch.Tensor, w: torch.Tensor) -> torch.Te
         dy, x, w, None, [2, 2], [1, 1], [1, 1], False, [0, 0], 1, [False, True, False])[1]
 
 
-class _Conv3x3S2BNStatsFn(torch.autograd.Function):
-    """(z, mean, invstd): stride-2 / padding-1 3x3 conv on ``conv_gemm.hip`` (stride-2 gather)
-    with the next BN's statistics in the epilogue. Backward: the data gradient as four
-    output-parity-class implicit GEMMs of 4 / 2 / 2 / 1 taps (``conv_gemm_s2dgrad``: no multiply
-    by the structural zeros of a stride-2 transposed conv, every dx pixel written once, no fill);
-    weight gradient on MIOpen."""
-
-    @staticmethod
-    def forward(ctx, x, w, rmean, rvar, eps, momentum, aff=None):
-        wf, wr = _w3x3_layouts(w, True)
-        y, mean, invstd = _conv_gemm_bn(x, wf, rmean, rvar, eps, momentum, 2, aff)
-        ctx.save_for_backward(x, w)
-        ctx.wr = wr
-        ctx.mark_non_differentiable(mean, invstd)
-        ctx.set_materialize_grads(False)
-        return y, mean, invstd
-
-    @staticmethod
-    def backward(ctx, dy, _dm, _di):
-        x, w = ctx.saved_tensors
-        dy = dy.contiguous(memory_format=torch.channels_last)
-        dx = lib().conv_gemm_s2dgrad(dy, ctx.wr, _zero_row(dy.device))[0] \
-            if ctx.needs_input_grad[0] else None
-        dw = _wgrad3x3_s2(dy, x, w) if ctx.needs_input_grad[1] else None
-        return dx, dw, None, None, None, None, None
+def _dgrad3x3(dy: torch.Tensor, wr: torch.Tensor, *bn):
+    """Stride-1 3x3 data gradient: the forward implicit GEMM of dy with the rotated weights ->
+    (dx,); with ``bn`` = (z, sc, bi, mean, invstd[, dgamma_out, dbeta_out]) also the backward sums
+    of the BN + ReLU that produced the conv's input -> (dx, s, q) (``conv_gemm_bnsums``)."""
+    if bn:
+        return lib().conv_gemm_bnsums(dy, wr, 9, _zero_row(dy.device), *bn)
+    return (lib().conv_gemm(dy, wr, 9, _zero_row(dy.device)),)
 
 
-class _BNReLUConv3x3S2BNStatsFn(torch.autograd.Function):
-    """``_BNReLUConv3x3BNStatsFn`` for the stride-2 3x3 conv of a downsample block: the
-    parity-class data gradient also takes bn1's BN + ReLU backward sums in its epilogue, so bn1's
-    backward is its apply pass only."""
-
-    @staticmethod
-    def forward(ctx, z1, g1, b1, mean1, invstd1, eps1, w, rmean, rvar, eps, momentum, aff=None):
-        L = lib()
-        y1 = L.bn_fwd(z1, None, g1, b1, None, None, mean1, invstd1, eps1, momentum, True, False,
-                      False)[0]
-        wf, wr = _w3x3_layouts(w, True)
-        z2, m2, i2 = _conv_gemm_bn(y1, wf, rmean, rvar, eps, momentum, 2, aff)
-        ctx.save_for_backward(z1, g1, b1, mean1, invstd1, y1, w)
-        ctx.wr = wr
-        ctx.aff1 = _cached_affine(g1, b1, mean1)
-        ctx.mark_non_differentiable(m2, i2)
-        ctx.set_materialize_grads(False)
-        return z2, m2, i2
-
-    @staticmethod
-    def backward(ctx, dz2, _dm, _di):
-        z1, g1, b1, mean1, invstd1, y1, w = ctx.saved_tensors
-        dz2 = dz2.contiguous(memory_format=torch.channels_last)
-        L = lib()
-        dw, h = _wgrad_fork(_wgrad3x3_s2, dz2, y1, w) if ctx.needs_input_grad[6] else (None, None)
-        sc, bi = ctx.aff1 or _affine(g1, b1, mean1, invstd1)
-        if _own_dgb(g1, b1):   # bn1's parameter gradients from the sums' finalize launch
-            dg1, db1 = torch.empty_like(g1), torch.empty_like(b1)
-            dy1, s1, q1 = L.conv_gemm_s2dgrad(dz2, ctx.wr, _zero_row(dz2.device), z1, sc, bi,
-                                              mean1, invstd1, dg1, db1)
-        else:
-            dy1, s1, q1 = L.conv_gemm_s2dgrad(dz2, ctx.wr, _zero_row(dz2.device), z1, sc, bi,
-                                              mean1, invstd1)
-            M = z1.numel() // z1.shape[1]
-            _, _, _, dg1, db1 = L.bn_bwd_coeffs(s1, q1, g1, mean1, invstd1, M)
-        dz1 = L.bn_bwd_apply(dy1, z1, g1, b1, mean1, invstd1, s1, q1)
-        dw = _wgrad_join(dw, h)
-        return dz1, dg1, db1, None, None, None, dw, None, None, None, None, None
+def _dgrad3x3_s2(dy: torch.Tensor, wr: torch.Tensor, *bn):
+    """``_dgrad3x3`` for stride 2: four output-parity-class implicit GEMMs of 4 / 2 / 2 / 1 taps
+    (``conv_gemm_s2dgrad``: no multiply by the structural zeros of a stride-2 transposed conv,
+    every dx pixel written once, no fill)."""
+    return lib().conv_gemm_s2dgrad(dy, wr, _zero_row(dy.device), *bn)
 
 
-def conv3x3_s2_ok(x: torch.Tensor, conv) -> bool:
-    """Stride-2 padding-1 3x3 convs on NHWC bf16 GPU tensors with 64-multiple channels and an even
-    input (every dx pixel then belongs to exactly one parity class)."""
-    return (x.is_cuda and x.dtype == torch.bfloat16 and conv.weight.dtype == torch.bfloat16
-            and x.dim() == 4 and x.is_contiguous(memory_format=torch.channels_last)
-            and x.shape[2] % 2 == 0 and x.shape[3] % 2 == 0
-            and conv.kernel_size == (3, 3) and conv.stride == (2, 2) and conv.padding == (1, 1)
-            and conv.dilation == (1, 1) and conv.groups == 1 and conv.bias is None
-            and conv.in_channels % 64 == 0 and conv.out_channels % 64 == 0)
-
-
-def conv3x3_s2_bn_stats(x: torch.Tensor, conv, bn):
-    """(z, (mean, invstd)) of a stride-2 ``conv(x)`` and bn's training statistics; callers check
-    ``conv3x3_s2_ok``."""
-    z, m, i = _Conv3x3S2BNStatsFn.apply(x, conv.weight, bn.running_mean, bn.running_var, bn.eps,
-                                        bn.momentum, _fin_aff(bn))
-    return z, (m, i)
-
-
-def bnrelu_conv3x3_s2_bn_stats(z1: torch.Tensor, bn_a, stats_a, conv, bn):
-    """``bnrelu_conv3x3_bn_stats`` for a stride-2 conv; callers check ``conv3x3_s2_ok`` on z1."""
-    z, m, i = _BNReLUConv3x3S2BNStatsFn.apply(z1, bn_a.weight, bn_a.bias, stats_a[0], stats_a[1],
-                                              bn_a.eps, conv.weight, bn.running_mean,
-                                              bn.running_var, bn.eps, bn.momentum, _fin_aff(bn))
-    return z, (m, i)
+# stride -> (data gradient, weight gradient) of the 3x3 Functions
+_BWD3X3 = {1: (_dgrad3x3, _wgrad3x3), 2: (_dgrad3x3_s2, _wgrad3x3_s2)}
 
 
 # PerfPolicy.bn1_dgrad_sums -- bn1 + ReLU -> 3x3 conv with bn1's backward sums in the data-gradient
@@ -1079,7 +1002,7 @@ def bnrelu_conv3x3_bn_stats(z1: torch.Tensor, bn_a, stats_a, conv, bn):
     bn's training statistics; callers check ``conv3x3_ok`` on z1 first."""
     z, m, i = _BNReLUConv3x3BNStatsFn.apply(z1, bn_a.weight, bn_a.bias, stats_a[0], stats_a[1],
                                             bn_a.eps, conv.weight, bn.running_mean, bn.running_var,
-                                            bn.eps, bn.momentum, _fin_aff(bn))
+                                            bn.eps, bn.momentum, conv.stride[0], _fin_aff(bn))
     return z, (m, i)
 
 
@@ -1087,22 +1010,25 @@ def conv3x3_bn_stats(x: torch.Tensor, conv, bn):
     """(z, (mean, invstd)) of ``conv(x)`` and bn's training statistics (running stats updated),
     from one implicit-GEMM kernel; callers check ``conv3x3_ok`` first."""
     z, m, i = _Conv3x3BNStatsFn.apply(x, conv.weight, bn.running_mean, bn.running_var, bn.eps,
-                                      bn.momentum, _fin_aff(bn))
+                                      bn.momentum, conv.stride[0], _fin_aff(bn))
     return z, (m, i)
 
 
 def conv3x3_ok(x: torch.Tensor, conv) -> bool:
-    """Stride-1 padding-1 3x3 convs on NHWC bf16 GPU tensors with 64-multiple channels."""
+    """Padding-1 3x3 convs on NHWC bf16 GPU tensors with 64-multiple channels: stride 1, or
+    stride 2 on an even input (every dx pixel then belongs to exactly one parity class)."""
     return (x.is_cuda and x.dtype == torch.bfloat16 and conv.weight.dtype == torch.bfloat16
             and x.dim() == 4 and x.is_contiguous(memory_format=torch.channels_last)
-            and conv.kernel_size == (3, 3) and conv.stride == (1, 1) and conv.padding == (1, 1)
+            and conv.kernel_size == (3, 3) and conv.padding == (1, 1)
+            and (conv.stride == (1, 1) or (conv.stride == (2, 2) and x.shape[2] % 2 == 0
+                                           and x.shape[3] % 2 == 0))
             and conv.dilation == (1, 1) and conv.groups == 1 and conv.bias is None
             and conv.in_channels % 64 == 0 and conv.out_channels % 64 == 0)
 
 
 def conv3x3(x: torch.Tensor, conv) -> torch.Tensor:
-    """``conv(x)`` with the data gradient on the HIP implicit GEMM where eligible."""
-    if conv3x3_ok(x, conv) and torch.is_grad_enabled():
+    """``conv(x)`` with the data gradient on the HIP implicit GEMM where eligible (stride 1)."""
+    if conv.stride == (1, 1) and conv3x3_ok(x, conv) and torch.is_grad_enabled():
         return _Conv3x3Fn.apply(x, conv.weight)
     return conv(x)
 

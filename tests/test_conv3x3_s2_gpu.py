@@ -6,6 +6,7 @@ import copy
 import pytest
 import torch
 
+import resnet_trace as RT
 from consensusml_amd import perf
 from consensusml_amd.ops.native import lib
 
@@ -82,7 +83,7 @@ def test_downsample_block_s2_matches_library_conv(cuda, monkeypatch, inplanes, p
     import consensusml_amd.models.resnet as R
     from consensusml_amd.ops import conv as fconv
     calls = []
-    for name in ("bnrelu_conv3x3_s2_bn_stats", "conv3x3_s2_bn_stats"):
+    for name in ("bnrelu_conv3x3_bn_stats", "conv3x3_bn_stats"):   # they read the stride off conv
         fn = getattr(fconv, name)
         monkeypatch.setattr(fconv, name,
                             lambda *a, _fn=fn, _n=name, **k: (calls.append(_n), _fn(*a, **k))[1])
@@ -133,3 +134,37 @@ def test_layer4_downsample_compact_matches_strided(cuda, monkeypatch):
     assert _rel(outs[True].float(), outs[False].float()) < 2e-2
     for a, r in zip(grads[True], grads[False]):
         assert _rel(a.float(), r.float()) < 3e-2
+
+
+@pytest.mark.parametrize("stride", [1, 2])
+def test_prologue_backward_same_bits_with_and_without_fin_dgamma(cuda, stride):
+    """The bn1 + ReLU -> 3x3 Function honours PerfPolicy.fin_dgamma at both strides
+    (``ops.conv._own_dgb``): bn1's parameter gradients from the data gradient's finalize launch, or
+    from a ``bn_bwd_coeffs`` launch over the same sums. Same inputs, same dz2: the same bits."""
+    from consensusml_amd.ops import conv as fconv
+    N, C, H = 2, 64, 8
+    g0 = torch.Generator(device=cuda).manual_seed(40 + stride)
+    z1 = _nhwc(torch.randn(N, C, H, H, device=cuda, generator=g0).bfloat16())
+    g1 = (torch.rand(C, device=cuda, generator=g0) + 0.5).bfloat16()
+    b1 = (torch.randn(C, device=cuda, generator=g0) * 0.1).bfloat16()
+    mean1 = z1.float().mean((0, 2, 3))
+    invstd1 = (z1.float().var((0, 2, 3), unbiased=False) + 1e-5).rsqrt()
+    w = (torch.randn(C, C, 3, 3, device=cuda, generator=g0) * (9 * C) ** -0.5).bfloat16()
+    dz2 = _nhwc(torch.randn(N, C, H // stride, H // stride, device=cuda, generator=g0).bfloat16())
+    dgrad = "lib.conv_gemm_bnsums" if stride == 1 else "lib.conv_gemm_s2dgrad"
+    got = {}
+    for fin in (True, False):
+        with perf.use_policy(perf.policy().replace(fin_dgamma=fin)), RT.tracing([]) as tr:
+            zi, gi, bi = (t.clone().requires_grad_(True) for t in (z1, g1, b1))
+            rm, rv = torch.zeros(C, device=cuda), torch.ones(C, device=cuda)
+            z2, _, _ = fconv._BNReLUConv3x3BNStatsFn.apply(zi, gi, bi, mean1, invstd1, 1e-5, w, rm,
+                                                           rv, 1e-5, 0.1, stride)
+            z2.backward(dz2)
+        got[fin] = (zi.grad, gi.grad, bi.grad)
+        # off: a bn_bwd_coeffs launch, and no dgamma / dbeta outputs on the data gradient
+        fns = [r["fn"] for r in tr.records]
+        assert fns.count(dgrad) == 1 and fns.count("lib.bn_bwd_coeffs") == (0 if fin else 1), fns
+        nargs = len(tr.records[fns.index(dgrad)]) - 1
+        assert nargs == (9 if stride == 1 else 8) + (2 if fin else 0), tr.records
+    for name, a, b in zip(("dz1", "dg1", "db1"), got[True], got[False]):
+        assert a.dtype == b.dtype and torch.equal(a, b), name

@@ -20,7 +20,7 @@ def _nhwc(t):
 def test_side_wgrad_bit_identical(cuda, N, C, H, stride):
     from consensusml_amd import perf
     from consensusml_amd.ops import conv as fconv
-    fn = fconv._BNReLUConv3x3BNStatsFn if stride == 1 else fconv._BNReLUConv3x3S2BNStatsFn
+    fn = fconv._BNReLUConv3x3BNStatsFn
     g0 = torch.Generator(device=cuda).manual_seed(C + H)
     z1 = _nhwc(torch.randn(N, C, H, H, device=cuda, generator=g0).bfloat16())
     g1 = (torch.rand(C, device=cuda, generator=g0) + 0.5).bfloat16()
@@ -38,7 +38,8 @@ def test_side_wgrad_bit_identical(cuda, N, C, H, stride):
             for _ in range(2):   # the second call reuses the side stream's freed blocks
                 zi, gi, bi, wi = (t.clone().requires_grad_(True) for t in (z1, g1, b1, w))
                 rm, rv = torch.zeros(C, device=cuda), torch.ones(C, device=cuda)
-                z2, _, _ = fn.apply(zi, gi, bi, mean1, invstd1, 1e-5, wi, rm, rv, 1e-5, 0.1)
+                z2, _, _ = fn.apply(zi, gi, bi, mean1, invstd1, 1e-5, wi, rm, rv, 1e-5, 0.1,
+                                    stride)
                 z2.backward(gz)
                 res.append([t.grad.clone() for t in (zi, gi, bi, wi)] + [z2.detach().clone()])
         torch.cuda.synchronize()
