@@ -882,9 +882,16 @@ std::vector<Tensor> wgrad1x1_ex(const Tensor& dy_in, const Tensor& x, const opti
   const float* bi = opt_ptr<const float>(pro_bi, at::kFloat, "pro_bi", Ci);
   TORCH_CHECK((sc == nullptr) == (bi == nullptr), "wgrad1x1_ex: pro_sc and pro_bi together");
   const c10::DeviceGuard guard(x.device());
+  const float* da = opt_ptr<const float>(dz_a, at::kFloat, "dz_a", Co);
+  const float* db = opt_ptr<const float>(dz_b, at::kFloat, "dz_b", Co);
   int S = 1, cps = 1;
-  cml::wgrad1x1_plan(P, static_cast<int>(Co), static_cast<int>(Ci), &S, &cps, sc != nullptr,
-                     static_cast<int>(dmode), colsum);
+  // (the launcher takes the same route: a Gram product sizes its partials from the Gram plan)
+  if (cml::gram1x1_route(dy.data_ptr(), x.data_ptr(), static_cast<int>(Co), static_cast<int>(Ci),
+                         sc, bi, static_cast<int>(dmode), da, db, false))
+    cml::gram1x1_plan(P, static_cast<int>(Co), &S, &cps);
+  else
+    cml::wgrad1x1_plan(P, static_cast<int>(Co), static_cast<int>(Ci), &S, &cps, sc != nullptr,
+                       static_cast<int>(dmode), colsum);
   auto f32 = x.options().dtype(at::kFloat);
   Tensor part = at::empty({S, Co, Ci}, f32);
   Tensor dw = at::empty({Co, Ci}, f32);
@@ -896,9 +903,7 @@ std::vector<Tensor> wgrad1x1_ex(const Tensor& dy_in, const Tensor& x, const opti
   CML_CHECK_HIP(cml::launch_wgrad1x1_ex(
       dy.data_ptr(), x.data_ptr(), part.data_ptr<float>(), dw.data_ptr(), false, P,
       static_cast<int>(Co), static_cast<int>(Ci), sc, bi, cur_stream(), static_cast<int>(dmode),
-      nullptr, opt_ptr<const uint8_t>(dz_mask, at::kByte, "dz_mask", P * Co / 8),
-      opt_ptr<const float>(dz_a, at::kFloat, "dz_a", Co),
-      opt_ptr<const float>(dz_b, at::kFloat, "dz_b", Co),
+      nullptr, opt_ptr<const uint8_t>(dz_mask, at::kByte, "dz_mask", P * Co / 8), da, db,
       opt_ptr<const float>(dz_c, at::kFloat, "dz_c", Co),
       colsum ? cs_part.data_ptr<float>() : nullptr, colsum ? cs.data_ptr<float>() : nullptr));
   return {dw, cs};

@@ -452,6 +452,20 @@ hipError_t launch_wgrad1x1(const void* dy, const void* x, float* part, void* dw,
                            const uint8_t* dz_mask = nullptr, const float* dz_a = nullptr,
                            const float* dz_b = nullptr, const float* dz_c = nullptr);
 
+// Gram matrix G = y^T y (fp32 [p][p], bitwise symmetric) of z [M][p] NHWC bf16 rows and the
+// column sums cy [p] of y (gram1x1.hip), p in {64, 128, 256}: y = bf16(max(z sc + bi, 0)) with
+// sc / bi (fp32 [p], both or neither), else y = z. part: splits x p x p floats (gram1x1_plan);
+// cs_part (splits x p floats) / cy both or neither. Deterministic (fixed-order fold, no atomics).
+void gram1x1_plan(int64_t M, int p, int* splits, int* cps);
+hipError_t launch_gram1x1(const void* z, float* part, float* G, int64_t M, int p, const float* sc,
+                          const float* bi, float* cs_part, float* cy, hipStream_t st);
+// True when a launch_wgrad1x1_ex call is such a Gram product and runs on launch_gram1x1 (dy and x
+// the same storage, fp32 dW, and dmode 3 with the x prologue's own pointers or no prologue at
+// all); `part` is then sized from gram1x1_plan. CML_GRAM_SYRK=0 turns the route off (A/B).
+bool gram1x1_route(const void* dy, const void* x, int Co, int Ci, const float* pro_sc,
+                   const float* pro_bi, int dmode, const float* dz_a, const float* dz_b,
+                   bool dw_bf16);
+
 // dW = sum of S fp32 partial slabs of n floats (n % 4 == 0), fixed order, bf16 or fp32 out.
 // Weight gradient of a 3x3 / stride 2 / padding 1 conv (wgrad1x1.hip's LDS-DMA kernel on the
 // implicit im2col of x): dy [N][H/2][W/2][Co], x [N][H][W][Ci] NHWC bf16 -> dw [Co][3][3][Ci]

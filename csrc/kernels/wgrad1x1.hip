@@ -15,39 +15,10 @@
 // registers with unconditional (clamped) loads while the current one is multiplied.
 #include "common.h"
 #include "kernels.h"
+#include "wgrad_frag.h"
 
 namespace cml {
 namespace {
-
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-
-
-__device__ __forceinline__ f32x16 mfma(bf16x8_t a, bf16x8_t b, f32x16 c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ s16x4 ld_tr(const char* p) {
-  return __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(p));
-}
-__device__ __forceinline__ bf16x8_t cat(s16x4 a, s16x4 b) {
-  return __builtin_bit_cast(bf16x8_t, __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7));
-}
-// component-wise select: a select of whole uint4 values becomes a select of their addresses and
-// pushes the prefetch registers into scratch memory
-__device__ __forceinline__ uint4 keep_if(bool ok, uint4 v) {
-  return make_uint4(ok ? v.x : 0u, ok ? v.y : 0u, ok ? v.z : 0u, ok ? v.w : 0u);
-}
-// byte offset of 16-B chunk ch of row `row` in a [rows][ROWB] image; the XOR spreads the 4 rows x
-// 64 B of each transposed read over all 64 banks. 256-B (and 512-B) rows: every row starts on the
-// same bank, so chunk bits 0..3 are permuted by the row. 128-B rows (64 channels): row parity
-// already selects the bank half, and rows 2-3 of each group of 4 take the other 64 B of it.
-template <int ROWB>
-__device__ __forceinline__ int img_off(int row, int ch) {
-  if constexpr (ROWB == 128) return ROWB * row + 16 * (ch ^ (((row >> 1) & 1) << 2));
-  return ROWB * row + 16 * (ch ^ (((row & 3) << 2) | ((row >> 2) & 3)));
-}
 
 // TM (co) x TN (ci) tile, (TM / 64) x (TN / 64) waves of 64 x 64 (four 32 x 32 accumulators).
 // PRO: x is the pre-BN activation z of a BN + ReLU whose output the conv consumed; the staging
@@ -992,13 +963,21 @@ void staged_plan(int64_t P, int Co, int Ci, int* splits, int* cps, bool pro) {
   *splits = (nchunk + c - 1) / c;
 }
 
+// every launch_wgrad1x1_ex call but the Gram products; launch_wgrad1x1 takes it directly, its
+// callers size `part` from wgrad1x1_plan alone
+hipError_t wgrad1x1_general(const void* dy, const void* x, float* part, void* dw, bool dw_bf16,
+                            int64_t P, int Co, int Ci, const float* pro_sc, const float* pro_bi,
+                            hipStream_t st, int dmode, const void* dz_z, const uint8_t* dz_mask,
+                            const float* dz_a, const float* dz_b, const float* dz_c,
+                            float* cs_part, float* cs);
+
 hipError_t launch_wgrad1x1(const void* dy, const void* x, float* part, void* dw, bool dw_bf16,
                            int64_t P, int Co, int Ci, const float* pro_sc, const float* pro_bi,
                            hipStream_t st, const void* dz_z, const uint8_t* dz_mask,
                            const float* dz_a, const float* dz_b, const float* dz_c) {
-  return launch_wgrad1x1_ex(dy, x, part, dw, dw_bf16, P, Co, Ci, pro_sc, pro_bi, st,
-                            dz_z ? DP_FULL : DP_NONE, dz_z, dz_mask, dz_a, dz_b, dz_c, nullptr,
-                            nullptr);
+  return wgrad1x1_general(dy, x, part, dw, dw_bf16, P, Co, Ci, pro_sc, pro_bi, st,
+                          dz_z ? DP_FULL : DP_NONE, dz_z, dz_mask, dz_a, dz_b, dz_c, nullptr,
+                          nullptr);
 }
 
 hipError_t launch_wgrad1x1_ex(const void* dy, const void* x, float* part, void* dw, bool dw_bf16,
@@ -1006,6 +985,19 @@ hipError_t launch_wgrad1x1_ex(const void* dy, const void* x, float* part, void* 
                               hipStream_t st, int dmode, const void* dz_z, const uint8_t* dz_mask,
                               const float* dz_a, const float* dz_b, const float* dz_c,
                               float* cs_part, float* cs) {
+  // a symmetric product of a tensor with itself: the one-read Gram kernel (gram1x1.hip)
+  if (gram1x1_route(dy, x, Co, Ci, pro_sc, pro_bi, dmode, dz_a, dz_b, dw_bf16))
+    return launch_gram1x1(x, part, reinterpret_cast<float*>(dw), P, Co, pro_sc, pro_bi, cs_part,
+                          cs, st);
+  return wgrad1x1_general(dy, x, part, dw, dw_bf16, P, Co, Ci, pro_sc, pro_bi, st, dmode, dz_z,
+                          dz_mask, dz_a, dz_b, dz_c, cs_part, cs);
+}
+
+hipError_t wgrad1x1_general(const void* dy, const void* x, float* part, void* dw, bool dw_bf16,
+                            int64_t P, int Co, int Ci, const float* pro_sc, const float* pro_bi,
+                            hipStream_t st, int dmode, const void* dz_z, const uint8_t* dz_mask,
+                            const float* dz_a, const float* dz_b, const float* dz_c,
+                            float* cs_part, float* cs) {
   if (dmode == DP_FULL && (!dz_z || !dz_mask || !dz_a || !dz_b || !dz_c)) return hipErrorInvalidValue;
   if (dmode == DP_MASK && (!dz_mask || !dz_a || !dz_c)) return hipErrorInvalidValue;
   if (dmode == DP_BNRELU && (!dz_a || !dz_b)) return hipErrorInvalidValue;

@@ -13,7 +13,8 @@ CLASSES = [
     ("3x3 weight gradient (wgrad3x3.hip, wgrad DMA stride-2)",
      r"cml::.*(wgrad3x3|wgrad_dma_kernel<\d+, \d+, \d+, \d+, true)"),
     ("recompute-tail algebra (tail_prep.hip, bn_stats_gram)", r"cml::.*(tail_|bn_stats_gram)"),
-    ("1x1 weight gradient (wgrad1x1.hip)", r"cml::.*(wgrad1x1|wgrad_dma_kernel|wgrad_fold)"),
+    ("1x1 weight gradient (wgrad1x1.hip)",
+     r"cml::.*(wgrad1x1|wgrad_dma_kernel|wgrad_fold|gram64_kernel|gram_wide_kernel|gram_fold_kernel)"),
     ("3x3 conv fwd + data gradient (conv_gemm.hip, gemm.hip conv mode, conv3x3p.hip)",
      r"cml::.*(conv_gemm|gemm_nt_kernel<\d, true(, \d+(, (true|false))?)?>|conv3x3p)"),
     ("own GEMM (gemm.hip: 1x1 convs as GEMMs, transformer linears)", r"cml::.*gemm_nt_kernel"),
