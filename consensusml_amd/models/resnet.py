@@ -15,7 +15,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from ..ops import conv as fconv
-from ..ops.bn import BatchNormAct2d, ResidualLink, bn_add_bn_relu, fused_ok, link_tap
+from ..ops.bn import (BatchNormAct2d, DeferredBN1, ResidualLink, bn_add_bn_relu, fused_ok,
+                      link_tap)
 from ..ops.pool import bn_relu_max_pool2d, max_pool2d
 from ..ops.stem import stem_conv_bn_relu_pool, stem_ok
 
@@ -266,7 +267,7 @@ class Bottleneck(nn.Module):
                 and fconv.fused_conv_ok(x, self.conv1.weight)
                 and fused_ok(x, self.bn3.weight))
 
-    def _conv_bn(self, x, conv: "Conv1x1", bn, link=None):
+    def _conv_bn(self, x, conv: "Conv1x1", bn, link=None, hand=None):
         """(z, stats) of a 1x1 conv followed by a BN: fused kernel when the policy picks it, else
         the library conv (stats None: the BN computes them)."""
         st = conv.stride[0]
@@ -275,7 +276,7 @@ class Bottleneck(nn.Module):
             dg = st == 1 and conv1x1_policy(conv.in_channels, conv.out_channels, hw)[1]
             # stride 2: ops.conv._wgrad takes the stride-2 DMA kernel's single-tap form
             own = own_wgrad_ok(conv.in_channels, conv.out_channels) if st == 1 else True
-            z, m, i = fconv.conv1x1_bn_stats(x, conv, bn, st, dg, own, link if dg else None)
+            z, m, i = fconv.conv1x1_bn_stats(x, conv, bn, st, dg, own, link if dg else None, hand)
             return z, (m, i)
         if st == 1:
             return conv(x, res_link=link if conv.link_ok(x) else None), None
@@ -290,18 +291,20 @@ class Bottleneck(nn.Module):
         return link_tap(x, tlink) if tlink is not None else x
 
     def _head(self, x: torch.Tensor, use_links: bool):
-        """conv1 -> (z1, bn1's statistics or None, link, dlink). ``link``: the one our producer
-        made for x (identity block: bn3 parks the residual gradient there); ``dlink``: a new one
-        on which a downsample block's shortcut parks its dX for conv1's data-gradient GEMM."""
+        """conv1 -> (z1, bn1's statistics or None, link, dlink, hand). ``link``: the one our
+        producer made for x (identity block: bn3 parks the residual gradient there); ``dlink``: a
+        new one on which a downsample block's shortcut parks its dX for conv1's data-gradient
+        GEMM; ``hand``: bn1's backward handed from conv2's Function to conv1's (DeferredBN1)."""
         link = dlink = None
+        hand = DeferredBN1() if _P().fused_conv1_bwd else None
         if self.down_conv is None:
             link = getattr(x, "_cml_link", None) if use_links else None
         elif use_links and self.conv1.link_ok(x):
             dlink = ResidualLink()
-        z1, st1 = self._conv_bn(x, self.conv1, self.bn1, link if dlink is None else dlink)
-        return z1, st1, link, dlink
+        z1, st1 = self._conv_bn(x, self.conv1, self.bn1, link if dlink is None else dlink, hand)
+        return z1, st1, link, dlink, hand
 
-    def _conv2_fused(self, z1: torch.Tensor, st1, fuse3: bool):
+    def _conv2_fused(self, z1: torch.Tensor, st1, fuse3: bool, hand=None):
         """bn1 + ReLU + conv2 -> (z2, bn2's statistics or None)."""
         pol = _P()
         s1 = self.conv2.stride == (1, 1)
@@ -317,7 +320,7 @@ class Bottleneck(nn.Module):
         if pro and st1 is not None:
             # bn1's backward sums come from the 3x3 data gradient's epilogue (stride 2: the
             # parity-class one)
-            return fconv.bnrelu_conv3x3_bn_stats(z1, self.bn1, st1, self.conv2, self.bn2)
+            return fconv.bnrelu_conv3x3_bn_stats(z1, self.bn1, st1, self.conv2, self.bn2, hand)
         out = self.bn1(z1, stats=st1)
         if own3:
             return fconv.conv3x3_bn_stats(out, self.conv2, self.bn2)
@@ -371,11 +374,11 @@ class Bottleneck(nn.Module):
         their statistics from the conv epilogues, bn2 + ReLU is applied inside conv3. Three
         stages; each picks its rung once its input exists (a library conv's output layout is only
         known then)."""
-        z1, st1, link, dlink = self._head(x, use_links)
+        z1, st1, link, dlink, hand = self._head(x, use_links)
         planes, s = self.conv3.in_channels, self.conv2.stride[0]
         hw2 = (z1.shape[2] // s) * (z1.shape[3] // s)
         fuse3 = fused_conv1x1_policy(planes, planes * 4, hw2, 1, True)
-        z2, st2 = self._conv2_fused(z1, st1, fuse3)
+        z2, st2 = self._conv2_fused(z1, st1, fuse3, hand)
         out_link = ResidualLink() if use_links else None
         y = self._tail_fused(x, z2, st2, fuse3, hw2, link, dlink, use_links, out_link)
         if out_link is not None:

@@ -56,6 +56,44 @@ class ResidualLink:
         return g.materialize() if hasattr(g, "materialize") else g
 
 
+class DeferredBN1:
+    """Hand-off of bn1's backward between the two Functions around z1 = conv1(x) of a bottleneck.
+
+    bn1's apply pass writes dz1 only for conv1's two gradient kernels to read it back. With this
+    object (made per forward by ``Bottleneck._head``, plain slots, cleared when taken):
+      * conv1's forward (``ops.conv._Conv1x1BNStatsFn``) clears it and sets ``armed`` when its
+        backward can run ``lib().conv1_bn_bwd``;
+      * the 3x3 Function's backward (``_BNReLUConv3x3BNStatsFn``), when armed, skips the apply pass:
+        it leaves ``rec`` = (z1, gamma1, beta1, mean1, invstd1, sdz, sdzx, dy1.data_ptr()) here
+        and returns the UNAPPLIED dy1 as z1's gradient;
+      * conv1's backward takes ``rec``, checks that the gradient it received is that dy1 (anything
+        else raises: an unapplied gradient is never used as if it were dz1) and forms dz1 on chip.
+    The 3x3 backward always runs before conv1's (z1 is its input), so the graph orders the
+    hand-off; a step that aborts in between leaves ``rec`` behind, which the next forward clears."""
+    __slots__ = ("armed", "rec")
+
+    def __init__(self):
+        self.armed = False
+        self.rec = None
+
+    def clear(self) -> None:
+        self.armed = False
+        self.rec = None
+
+    def take(self):
+        r, self.rec = self.rec, None
+        return r
+
+
+def check_deferred_grad(rec, dy: torch.Tensor) -> None:
+    """Raise unless ``dy`` is the very gradient the 3x3 backward left unapplied (``rec[-1]``)."""
+    if dy.data_ptr() != rec[-1] or dy.shape != rec[0].shape:
+        raise RuntimeError(
+            "deferred bn1 backward: conv1 received a gradient that is not the dy1 its 3x3 conv "
+            "left unapplied (z1 has another consumer, or a hook replaced the gradient); refusing "
+            "to treat it as dz1")
+
+
 class MaskedGrad:
     """A residual gradient m * g left unmaterialised: g is the block-output gradient (NHWC bf16)
     and m the forward's ReLU bit mask ([M, C/8] bytes, bit k of byte j = channel 8 j + k). The

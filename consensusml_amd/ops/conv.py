@@ -30,7 +30,7 @@ import torch
 import torch.nn.functional as F
 
 from ..perf import policy as _P
-from .bn import MaskedGrad
+from .bn import MaskedGrad, check_deferred_grad
 from .native import lib
 
 
@@ -181,10 +181,46 @@ def _wgrad(dy: torch.Tensor, x: torch.Tensor, w: torch.Tensor, stride: int, own:
     return dw
 
 
+def _conv1_bwd_armed(ctx, x: torch.Tensor, w: torch.Tensor, stride: int, link) -> bool:
+    """Whether conv1's backward can take bn1's apply pass (``lib().conv1_bn_bwd``): policy on and
+    enough pixels, a shape the kernel has a plan for, stride 1, both input gradients wanted, and
+    no producer BN that wants its backward sums from the data gradient's epilogue."""
+    pol = _P()
+    M = x.shape[0] * x.shape[2] * x.shape[3]
+    return bool(pol.fused_conv1_bwd and stride == 1 and M >= pol.fused_conv1_bwd_min_pixels
+                and ctx.needs_input_grad[0] and ctx.needs_input_grad[1]
+                and (link is None or link.bn_ctx is None)
+                and w.dtype == torch.bfloat16 and x.dtype == torch.bfloat16
+                and lib().conv1_bn_bwd_ok(M, w.shape[0], w.shape[1]))
+
+
+def _conv1_bn_bwd(rec, dy: torch.Tensor, x: torch.Tensor, w: torch.Tensor, link):
+    """(dx, dw) of conv1 from the UNAPPLIED dy1 and bn1's record in one kernel, or None when the
+    gradient parked on ``link`` is of a kind the kernel does not add (the caller applies bn1's
+    backward and takes today's path; the parked gradient is put back)."""
+    z1, g1, b1, mean1, invstd1, s1, q1, _ = rec
+    g = link.take() if link is not None else None
+    kw = {}
+    if isinstance(g, MaskedGrad):
+        kw = dict(link=g.g, lmask=g.mask)
+    elif isinstance(g, S2Grad) and g.H == x.shape[2] and g.W == x.shape[3]:
+        kw = dict(link=g.g, link_s2=True)
+    elif g is not None:
+        link.grad = g
+        return None
+    dx, dw = lib().conv1_bn_bwd(dy, z1, g1, b1, mean1, invstd1, s1, q1, x, w.reshape(w.shape[0], -1),
+                                w.dtype, **kw)
+    return dx, dw.view_as(w)
+
+
 class _Conv1x1BNStatsFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w, rmean, rvar, stride, eps, momentum, dgrad_gemm, own_wgrad, link,
-                aff=None):
+                aff=None, hand=None):
+        if hand is not None:   # a record an aborted step left behind must not reach this backward
+            hand.clear()
+            hand.armed = _conv1_bwd_armed(ctx, x, w, stride, link)
+        ctx.hand = hand
         out = lib().conv1x1_bn_fwd(x, w, None, None, rmean, rmean, rvar, stride, True, eps,
                                    momentum, *(aff or (None, None)))
         y, mean, invstd = out[:3]
@@ -201,13 +237,20 @@ class _Conv1x1BNStatsFn(torch.autograd.Function):
     def backward(ctx, dy, _dm, _di):
         x, w = ctx.saved_tensors
         dy = dy.contiguous(memory_format=torch.channels_last)
+        rec = ctx.hand.take() if ctx.hand is not None else None
+        if rec is not None:   # dy is bn1's UNAPPLIED output gradient (ops.bn.DeferredBN1)
+            check_deferred_grad(rec, dy)
+            out = _conv1_bn_bwd(rec, dy, x, w, ctx.link)
+            if out is not None:
+                return out + (None,) * 10
+            dy = lib().bn_bwd_apply(dy, *rec[:7])
         # the weight gradient on the side stream (large batches) while the data gradient runs
         dw, h = _wgrad_fork(lambda d, a, b: _wgrad(d, a, b, ctx.stride, ctx.own_wgrad), dy, x, w,
                             conv1x1=True) if ctx.needs_input_grad[1] else (None, None)
         dx = _dgrad(dy, x, w, ctx.stride, ctx.dgrad_gemm, ctx.link, ctx.wt) \
             if ctx.needs_input_grad[0] else None
         dw = _wgrad_join(dw, h)
-        return dx, dw, None, None, None, None, None, None, None, None, None
+        return dx, dw, None, None, None, None, None, None, None, None, None, None
 
 
 class _BNReLUConv1x1BNStatsFn(torch.autograd.Function):
@@ -920,8 +963,9 @@ class _BNReLUConv3x3BNStatsFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, z1, g1, b1, mean1, invstd1, eps1, w, rmean, rvar, eps, momentum, stride=1,
-                aff=None):
+                aff=None, hand=None):
         L = lib()
+        ctx.hand = hand
         y1 = L.bn_fwd(z1, None, g1, b1, None, None, mean1, invstd1, eps1, momentum, True, False,
                       False)[0]
         wf, wr = _w3x3_layouts(w, True)   # both layouts now: the backward reuses wr
@@ -949,9 +993,16 @@ class _BNReLUConv3x3BNStatsFn(torch.autograd.Function):
             dy1, s1, q1 = dgrad(dz2, ctx.wr, *bn1)
             M = z1.numel() // z1.shape[1]
             _, _, _, dg1, db1 = L.bn_bwd_coeffs(s1, q1, g1, mean1, invstd1, M)
-        dz1 = L.bn_bwd_apply(dy1, z1, g1, b1, mean1, invstd1, s1, q1)
+        hand = ctx.hand
+        if hand is not None and hand.armed and ctx.needs_input_grad[0]:
+            # conv1's backward forms dz1 on chip: z1's "gradient" is the unapplied dy1
+            dy1 = dy1.contiguous(memory_format=torch.channels_last)
+            hand.rec = (z1, g1, b1, mean1, invstd1, s1, q1, dy1.data_ptr())
+            dz1 = dy1
+        else:
+            dz1 = L.bn_bwd_apply(dy1, z1, g1, b1, mean1, invstd1, s1, q1)
         dw = _wgrad_join(dw, h)
-        return dz1, dg1, db1, None, None, None, dw, None, None, None, None, None, None
+        return dz1, dg1, db1, None, None, None, dw, None, None, None, None, None, None, None
 
 
 def _wgrad3x3_s2(dy: torch.Tensor, x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
@@ -997,12 +1048,14 @@ _BWD3X3 = {1: (_dgrad3x3, _wgrad3x3), 2: (_dgrad3x3_s2, _wgrad3x3_s2)}
 # epilogue (off: bn_act + conv3x3_bn_stats, bn1's backward with its own reduction pass)
 
 
-def bnrelu_conv3x3_bn_stats(z1: torch.Tensor, bn_a, stats_a, conv, bn):
+def bnrelu_conv3x3_bn_stats(z1: torch.Tensor, bn_a, stats_a, conv, bn, hand=None):
     """(z, (mean, invstd)) of ``conv(relu(bn_a(z1)))`` (bn_a's batch statistics ``stats_a``) and
-    bn's training statistics; callers check ``conv3x3_ok`` on z1 first."""
+    bn's training statistics; callers check ``conv3x3_ok`` on z1 first. ``hand``: the
+    ``ops.bn.DeferredBN1`` shared with the conv that produced z1."""
     z, m, i = _BNReLUConv3x3BNStatsFn.apply(z1, bn_a.weight, bn_a.bias, stats_a[0], stats_a[1],
                                             bn_a.eps, conv.weight, bn.running_mean, bn.running_var,
-                                            bn.eps, bn.momentum, conv.stride[0], _fin_aff(bn))
+                                            bn.eps, bn.momentum, conv.stride[0], _fin_aff(bn),
+                                            hand)
     return z, (m, i)
 
 
@@ -1034,11 +1087,13 @@ def conv3x3(x: torch.Tensor, conv) -> torch.Tensor:
 
 
 def conv1x1_bn_stats(x: torch.Tensor, conv, bn, stride: int = 1, dgrad_gemm: bool = False,
-                     own_wgrad: bool = False, link=None):
+                     own_wgrad: bool = False, link=None, hand=None):
     """(z, mean, invstd): 1x1 conv output and its training BN statistics (bn's running stats are
-    updated). ``conv`` / ``bn``: nn.Conv2d-like (weight) and BatchNormAct2d modules."""
+    updated). ``conv`` / ``bn``: nn.Conv2d-like (weight) and BatchNormAct2d modules. ``hand``: a
+    bottleneck conv1's ``ops.bn.DeferredBN1``."""
     return _Conv1x1BNStatsFn.apply(x, conv.weight, bn.running_mean, bn.running_var, stride,
-                                   bn.eps, bn.momentum, dgrad_gemm, own_wgrad, link, _fin_aff(bn))
+                                   bn.eps, bn.momentum, dgrad_gemm, own_wgrad, link, _fin_aff(bn),
+                                   hand)
 
 
 def bnrelu_conv1x1_bn_stats(z: torch.Tensor, bn_a, stats_a, conv, bn_b, dgrad_gemm: bool = False,

@@ -66,6 +66,12 @@ class PerfPolicy:
     down_s2_compact: bool = True          # non-recompute stride-2 downsample (layer 4) as a
                                           # stride-1 GEMM of x[:, :, ::2, ::2], compact gradient
     bn_affine_kernel: bool = True         # one-launch BN affine (sc, bi)
+    fused_conv1_bwd: bool = True          # bn1's backward apply inside conv1's data + weight
+                                          # gradient kernel (conv1_bwd.hip; p 64 / 128, Cin 256 / 512)
+    fused_conv1_bwd_min_pixels: int = 65536   # ... from this many pixels N H W on: the kernel is
+                                          # persistent, one workgroup per CU over 64-pixel tiles,
+                                          # and below a few tiles per CU the three launches win
+                                          # (profiles/conv1_bwd/)
     # ---------------------------------------------------------------- 3x3 convolutions
     own_dgrad3x3: bool = True             # conv_gemm.hip data gradient
     conv3x3_bn_stats: bool = True         # conv_gemm.hip forward + BN statistics epilogue
@@ -150,6 +156,8 @@ class PerfPolicy:
             s2_link_dgrad=_env_bool("CML_S2_LINK_DGRAD", True),
             down_s2_compact=_env_bool("CML_DOWN_S2_COMPACT", True),
             bn_affine_kernel=_env_bool("CML_BN_AFFINE_KERNEL", True),
+            fused_conv1_bwd=_env_bool("CML_FUSED_CONV1_BWD", True),
+            fused_conv1_bwd_min_pixels=_env_int("CML_FUSED_CONV1_BWD_MIN_PIXELS", 65536),
             own_dgrad3x3=_env_bool("CML_DGRAD3X3", True),
             conv3x3_bn_stats=_env_bool("CML_CONV3X3_BN_STATS", True),
             bn1_dgrad_sums=_env_bool("CML_BN1_DGRAD_SUMS", True),

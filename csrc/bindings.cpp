@@ -1368,6 +1368,93 @@ Tensor bn_bwd_apply(const Tensor& dy_in, const Tensor& x, const Tensor& gamma, c
   return dx;
 }
 
+// conv1's backward with bn1's apply pass inside: dy1, z1 [N, p, H, W], x [N, Cin, H, W] NHWC bf16,
+// w [p, Cin(, 1, 1)] bf16, bn1's parameters / statistics / backward sums as bn_bwd_apply takes them.
+// link: none; [N, Cin, H, W] with lmask [M, Cin/8] (masked residual gradient); or, with link_s2,
+// [N, Cin, ceil(H/2), ceil(W/2)] added at the even pixels. -> {dx, dw (dtype), dz1 if want_dz}.
+// splits != 0: that many pixel ranges (tests: more ranges than tiles).
+bool conv1_bn_bwd_ok(int64_t M, int64_t p, int64_t Cin) {
+  int S;
+  return cml::conv1_bwd_plan(M, static_cast<int>(p), static_cast<int>(Cin), &S);
+}
+
+std::vector<Tensor> conv1_bn_bwd(const Tensor& dy_in, const Tensor& z, const Tensor& gamma,
+                                 const Tensor& beta, const Tensor& mean, const Tensor& invstd,
+                                 const Tensor& sdz, const Tensor& sdzx, const Tensor& x,
+                                 const Tensor& w, at::ScalarType dtype,
+                                 const optional<Tensor>& link_in,
+                                 const optional<Tensor>& lmask, bool link_s2, bool want_dz,
+                                 int64_t splits) {
+  check_nhwc(x, "x");
+  check_nhwc(z, "z");
+  TORCH_CHECK(x.dim() == 4 && z.dim() == 4, "conv1_bn_bwd: 4-D NHWC x / z");
+  Tensor dy = dy_in.contiguous(at::MemoryFormat::ChannelsLast);
+  check_nhwc(dy, "dy");
+  const int64_t N = x.size(0), Cin = x.size(1), H = x.size(2), W = x.size(3), M = N * H * W;
+  const int64_t p = z.size(1);
+  TORCH_CHECK(dy.sizes() == z.sizes() && z.size(0) == N && z.size(2) == H && z.size(3) == W,
+              "conv1_bn_bwd: dy / z / x shapes");
+  check_dev(w, "w");
+  TORCH_CHECK(w.scalar_type() == at::kBFloat16 && w.is_contiguous() && w.numel() == p * Cin &&
+                  w.size(0) == p, "conv1_bn_bwd: w must be contiguous bf16 [p, Cin]");
+  TORCH_CHECK(gamma.is_cuda() && beta.is_cuda() && gamma.scalar_type() == at::kBFloat16 &&
+                  beta.scalar_type() == at::kBFloat16 && gamma.is_contiguous() &&
+                  beta.is_contiguous() && gamma.numel() == p && beta.numel() == p,
+              "conv1_bn_bwd: bf16 gamma / beta [p]");
+  TORCH_CHECK(dtype == at::kBFloat16 || dtype == at::kFloat, "conv1_bn_bwd: bf16 or fp32 dw");
+  TORCH_CHECK(splits >= 0 && splits <= 4096, "conv1_bn_bwd: splits out of range");
+  int S = 0;
+  TORCH_CHECK(cml::conv1_bwd_plan(M, static_cast<int>(p), static_cast<int>(Cin), &S,
+                                  static_cast<int>(splits)),
+              "conv1_bn_bwd: p in {64, 128} and Cin in {256, 512} only");
+  const bool has_link = link_in.has_value() && link_in->defined();
+  int kind = 0;
+  Tensor link;
+  const uint8_t* lm = nullptr;
+  if (has_link && link_s2) {
+    kind = 2;
+    link = link_in->contiguous(at::MemoryFormat::ChannelsLast);
+    check_nhwc(link, "link");
+    TORCH_CHECK(link.dim() == 4 && link.size(0) == N && link.size(1) == Cin &&
+                    link.size(2) == (H + 1) / 2 && link.size(3) == (W + 1) / 2,
+                "conv1_bn_bwd: link [N, Cin, ceil(H/2), ceil(W/2)]");
+    TORCH_CHECK(!(lmask.has_value() && lmask->defined()), "conv1_bn_bwd: no mask with link_s2");
+  } else if (has_link) {
+    kind = 1;
+    link = *link_in;
+    check_nhwc(link, "link");
+    TORCH_CHECK(link.sizes() == x.sizes(), "conv1_bn_bwd: link shape");
+    lm = opt_ptr<const uint8_t>(lmask, at::kByte, "lmask", M * Cin / 8);
+    TORCH_CHECK(lm != nullptr, "conv1_bn_bwd: a full-resolution link needs its bit mask");
+  } else {
+    TORCH_CHECK(!link_s2, "conv1_bn_bwd: link_s2 without a link");
+  }
+  const float* mu = opt_ptr<const float>(mean, at::kFloat, "mean", p);
+  const float* is = opt_ptr<const float>(invstd, at::kFloat, "invstd", p);
+  const float* s1 = opt_ptr<const float>(sdz, at::kFloat, "sdz", p);
+  const float* q1 = opt_ptr<const float>(sdzx, at::kFloat, "sdzx", p);
+  TORCH_CHECK(mu && is && s1 && q1, "conv1_bn_bwd: mean, invstd, sdz, sdzx are required");
+  for (const Tensor* t : {static_cast<const Tensor*>(&dy), &z, &x})
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(t->data_ptr()) % 16 == 0,
+                "conv1_bn_bwd: 16-B aligned activations");
+  TORCH_CHECK(!has_link || reinterpret_cast<uintptr_t>(link.data_ptr()) % 16 == 0,
+              "conv1_bn_bwd: 16-B aligned link");
+  const c10::DeviceGuard guard(x.device());
+  Tensor dx = at::empty_like(x);
+  Tensor dw = at::empty({p, Cin, 1, 1}, x.options().dtype(dtype));
+  Tensor part = at::empty({S, p, Cin}, x.options().dtype(at::kFloat));
+  Tensor dz;
+  if (want_dz) dz = at::empty_like(z);
+  CML_CHECK_HIP(cml::launch_conv1_bwd(
+      dy.data_ptr(), z.data_ptr(), gamma.data_ptr(), beta.data_ptr(), mu, is, s1, q1, x.data_ptr(),
+      w.data_ptr(), has_link ? link.data_ptr() : nullptr, lm, kind, static_cast<int>(N),
+      static_cast<int>(H), static_cast<int>(W), dx.data_ptr(), part.data_ptr<float>(), S,
+      dw.data_ptr(), dtype == at::kBFloat16, want_dz ? dz.data_ptr() : nullptr, M,
+      static_cast<int>(p), static_cast<int>(Cin), cur_stream()));
+  if (want_dz) return {dx, dw, dz};
+  return {dx, dw};
+}
+
 // dX = dY W (1x1, stride 1: x = dY [N, K, H, W] NHWC, w [No, K] -- W^T of the conv's weight)
 // plus, at the even pixels, link [N, No, ceil(H/2), ceil(W/2)]: a parallel stride-2 conv's
 // compact data gradient (never scattered to full resolution).
@@ -2852,6 +2939,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("zero") = py::none(),
         "weight gradient of a 3x3 stride-1 conv (MFMA, split-K, all nine taps per workgroup: "
         "wgrad3x3.hip) for shapes with wgrad3x3_direct_ok");
+  m.def("conv1_bn_bwd_ok", &conv1_bn_bwd_ok, py::arg("M"), py::arg("p"), py::arg("Cin"),
+        "whether conv1_bn_bwd takes the shape");
+  m.def("conv1_bn_bwd", &conv1_bn_bwd, py::arg("dy"), py::arg("z"), py::arg("gamma"),
+        py::arg("beta"), py::arg("mean"), py::arg("invstd"), py::arg("sdz"), py::arg("sdzx"),
+        py::arg("x"), py::arg("w"), py::arg("dtype"), py::arg("link") = py::none(),
+        py::arg("lmask") = py::none(), py::arg("link_s2") = false, py::arg("want_dz") = false,
+        py::arg("splits") = 0,
+        "conv1's data and weight gradients with bn1's backward apply formed on chip");
   m.def("conv1x1_link_s2", &conv1x1_link_s2,
         "1x1 data gradient + a stride-2 conv's compact data gradient at the even pixels");
   m.def("subsample2", &subsample2, "x[:, :, ::2, ::2] of an NHWC bf16 tensor, dense NHWC");

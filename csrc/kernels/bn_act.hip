@@ -220,10 +220,8 @@ __device__ __forceinline__ void chan_affine(int g, const float* mean, const floa
   ld8(gamma + 8 * g, ga);
   ld8(beta + 8 * g, be);
 #pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    sc[k] = invstd[8 * g + k] * ga[k];
-    bi[k] = be[k] - mean[8 * g + k] * sc[k];
-  }
+  for (int k = 0; k < 8; ++k)
+    bn_chan_affine(mean[8 * g + k], invstd[8 * g + k], ga[k], be[k], sc[k], bi[k]);
 }
 
 // MASK (RES + RELU blocks): also write the ReLU mask as one bit per element ([M, C/8] bytes), so
@@ -297,7 +295,7 @@ __device__ __forceinline__ void load_dz(const bf16* __restrict__ dy, const bf16*
     for (int k = 0; k < 8; ++k) dz[k] = ((bits >> k) & 1u) ? dz[k] : 0.f;
   } else if constexpr (RM == RM_RECOMP) {
 #pragma unroll
-    for (int k = 0; k < 8; ++k) dz[k] = fmaf(v[k], sc[k], bi[k]) > 0.f ? dz[k] : 0.f;
+    for (int k = 0; k < 8; ++k) dz[k] = bn_relu_keep(dz[k], v[k], sc[k], bi[k]);
   }
 }
 
@@ -408,10 +406,8 @@ __global__ __launch_bounds__(kBT) void bn_bwd_apply_kernel(const bf16* __restric
       const int64_t ru = r + u * rstride;
       float o[8];
 #pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        const float xh = (v[u][k] - mu[k]) * is[k];
-        o[k] = sc[k] * (dz[u][k] - a[k] - xh * b[k]);
-      }
+      for (int k = 0; k < 8; ++k)
+        o[k] = bn_bwd_elem(dz[u][k], v[u][k], mu[k], is[k], sc[k], a[k], b[k]);
       store_bf16<8>(dx + ru * C + 8 * g, o);
       if constexpr (DRES) store_bf16<8>(dres + ru * C + 8 * g, dz[u]);
     }

@@ -57,6 +57,26 @@ __device__ __forceinline__ uint32_t mask_pk(uint32_t w, uint32_t bits) {
   return w & m;
 }
 
+// ---------------------------------------------------------------- BN + ReLU backward, per element
+// Shared by bn_act.hip's apply pass and conv1_bwd.hip, which forms the same gradient on chip: the
+// two must agree bit for bit, so the contractions are written out instead of left to the compiler.
+// A training BN's affine of one channel: sc = gamma invstd, bi = beta - mean sc.
+__device__ __forceinline__ void bn_chan_affine(float mean, float invstd, float gamma, float beta,
+                                               float& sc, float& bi) {
+  sc = invstd * gamma;
+  bi = fmaf(-mean, sc, beta);
+}
+// the output gradient where the recomputed ReLU let the value through
+__device__ __forceinline__ float bn_relu_keep(float dy, float z, float sc, float bi) {
+  return fmaf(z, sc, bi) > 0.f ? dy : 0.f;
+}
+// dz = sc (dy - a - xhat b) with a = sum(dy) / M, b = sum(dy xhat) / M
+__device__ __forceinline__ float bn_bwd_elem(float dy, float z, float mu, float is, float sc,
+                                             float a, float b) {
+  const float xh = (z - mu) * is;
+  return sc * fmaf(-xh, b, dy - a);
+}
+
 // ---------------------------------------------------------------- vector loads of VEC elements
 // VEC elements of T starting at p -> float out[VEC]. Vector widths: 16 B per lane where possible.
 template <typename T, int VEC>

@@ -466,6 +466,24 @@ bool gram1x1_route(const void* dy, const void* x, int Co, int Ci, const float* p
                    const float* pro_bi, int dmode, const float* dz_a, const float* dz_b,
                    bool dw_bf16);
 
+// Backward of a bottleneck's conv1 with bn1's apply pass inside (conv1_bwd.hip): dz1 =
+// bn_bwd_apply(dy1, z1; gamma .. sdzx) formed once per 32-pixel tile on chip (bit-identical to
+// launch_bn_bwd_apply, rounded to bf16 once) and used by both products, dx [M][Cin] = dz1 W1
+// (+ link by conv1x1_common.h's EL rule) and dw [p][Cin] = dz1^T x (bf16 or fp32).
+// dy1, z1 [M][p], x [M][Cin] NHWC bf16 rows, w [p][Cin] bf16, p in {64, 128}, Cin in {256, 512}.
+// link_kind 0: none; 1: link [M][Cin] with the bit mask lmask [M][Cin / 8]; 2: the compact
+// stride-2 gradient link [Nimg][ceil(H/2)][ceil(W/2)][Cin] added at the even pixels (M = Nimg H W).
+// part: splits x p x Cin floats with splits from conv1_bwd_plan (false: shape not supported;
+// want != 0: that many pixel ranges, empty ones included). dz_out: optional copy of dz1 (tests).
+// Deterministic: one slab per workgroup, fixed-order fold, no atomics.
+bool conv1_bwd_plan(int64_t M, int p, int Cin, int* splits, int want = 0);
+hipError_t launch_conv1_bwd(const void* dy, const void* z, const void* gamma, const void* beta,
+                            const float* mean, const float* invstd, const float* sdz,
+                            const float* sdzx, const void* x, const void* w, const void* link,
+                            const uint8_t* lmask, int link_kind, int Nimg, int H, int W, void* dx,
+                            float* part, int splits, void* dw, bool dw_bf16, void* dz_out,
+                            int64_t M, int p, int Cin, hipStream_t st);
+
 // dW = sum of S fp32 partial slabs of n floats (n % 4 == 0), fixed order, bf16 or fp32 out.
 // Weight gradient of a 3x3 / stride 2 / padding 1 conv (wgrad1x1.hip's LDS-DMA kernel on the
 // implicit im2col of x): dy [N][H/2][W/2][Co], x [N][H][W][Ci] NHWC bf16 -> dw [Co][3][3][Ci]
