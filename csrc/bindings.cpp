@@ -3077,6 +3077,32 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("out") = py::none(), py::arg("bias") = py::none(), py::arg("cin") = py::none());
   m.def("gemm_nt_ok", &gemm_nt_ok, "shape eligibility of gemm_nt's 256 x 256 kernel");
   m.def("gemm_conv_tm", &gemm_conv_tm, "m-tile of gemm.hip's 3x3 conv mode for M x N, C (256, 512, 0)");
+  m.def("dispatch_settings", [] {
+    int gm, tall, variant, narrow, smallm, smallv, gemm2, s2;
+    cml::gemm_dispatch_settings(&gm, &tall);
+    cml::conv_gemm_settings(&variant, &narrow, &smallm, &smallv, &gemm2, &s2);
+    py::dict d;
+    d["gemm_gm"] = gm;
+    d["w4_sched"] = cml::gemm_w4_sched_setting();
+    d["gemm2_tall"] = tall;
+    d["conv_gemm_variant"] = variant;
+    d["conv_gemm_narrow"] = narrow;
+    d["conv_gemm_smallm"] = smallm;
+    d["conv_gemm_smallv"] = smallv;
+    d["conv_gemm2"] = gemm2;
+    d["gemm2_s2"] = s2;
+    return d;
+  }, "the read-once GEMM / conv dispatch values as this process read them");
+  m.def("conv_gemm_route", [](int64_t Nimg, int64_t H, int64_t W, int64_t C, int64_t N,
+                              int64_t taps, int64_t stride) {
+    int BM = 0, BN = 0;
+    const int r = cml::conv_gemm_route(static_cast<int>(Nimg), static_cast<int>(H),
+                                       static_cast<int>(W), static_cast<int>(C), static_cast<int>(N),
+                                       static_cast<int>(taps), static_cast<int>(stride), &BM, &BN);
+    TORCH_CHECK(r >= 0, "conv_gemm_route: shape not accepted by conv_gemm");
+    const char* names[] = {"conv3x3p", "gemm2", "conv_gemm"};
+    return py::make_tuple(std::string(names[r]), BM, BN);
+  }, "(path, BM, BN) of the kernel conv_gemm launches for this shape: conv3x3p | gemm2 | conv_gemm");
   m.def("gemm_nt_pick", &gemm_nt_pick, "EP_STORE tile choice of gemm_nt: 256, 128 or 0 (none)");
   m.attr("CMB_SORTED") = static_cast<int>(cml::CMB_SORTED);
   m.attr("CMB_WEIGHTED") = static_cast<int>(cml::CMB_WEIGHTED);

@@ -386,16 +386,23 @@ int pick_variant(int64_t M, int N, int* BM, int* BN);
 // The 128-channel convs (layer 2: variant 2's 256 x 128 tiles, 0.6-0.67 PFLOP/s) take gemm.hip's
 // 512 x 128 tile when the grid has enough of them (gemm_conv_tm == 512).
 // Returns the m-tile (256 / 512) or 0.
-int use_gemm2(int64_t M, int N, int C, int taps, int stride) {
+bool gemm2_on() {
   static const bool on = [] {
     const char* e = getenv("CML_CONV_GEMM2");
     return !e || e[0] != '0';
   }();
-  // CML_GEMM2_S2=0: the stride-2 forwards stay on conv_gemm.hip (A/B)
+  return on;
+}
+// CML_GEMM2_S2=0: the stride-2 forwards stay on conv_gemm.hip (A/B)
+bool gemm2_s2_on() {
   static const bool s2 = [] {
     const char* e = getenv("CML_GEMM2_S2");
     return !e || e[0] != '0';
   }();
+  return s2;
+}
+int use_gemm2(int64_t M, int N, int C, int taps, int stride) {
+  const bool on = gemm2_on(), s2 = gemm2_s2_on();
   if (!on || taps != 9 || (stride != 1 && !(stride == 2 && s2))) return 0;
   const int tm = gemm_conv_tm(M, N, C);
   if (tm == 512) return 512;
@@ -450,6 +457,39 @@ namespace {
 // the tile (BM, BN) launch_v picks for M x N
 void tile_of(int64_t M, int N, int* BM, int* BN) { (void)pick_variant(M, N, BM, BN); }
 }  // namespace
+
+void conv_gemm_settings(int* variant, int* narrow, int* smallm, int* smallv, int* gemm2, int* s2) {
+  *variant = gemm_variant();
+  *narrow = narrow_variant();
+  *smallm = smallm_tiles();
+  *smallv = smallm_variant();
+  *gemm2 = gemm2_on() ? 1 : 0;
+  *s2 = gemm2_s2_on() ? 1 : 0;
+}
+
+// launch_conv_gemm's predicates in its order: 0 = conv3x3p.hip (128-row slabs of 64 channels),
+// 1 = gemm.hip's conv mode (BM = its m-tile), 2 = this file's launch_v; -1 = rejected
+int conv_gemm_route(int Nimg, int H, int W, int C, int N, int taps, int stride, int* BM, int* BN) {
+  *BM = *BN = 0;
+  if (stride != 1 && stride != 2) return -1;
+  const int OH = (H - 1) / stride + 1, OW = (W - 1) / stride + 1;
+  const int64_t M = static_cast<int64_t>(Nimg) * OH * OW;
+  if (C % kBK || N % 64 || (taps != 1 && taps != 9) || M < 1 || M >= (1ll << 31) ||
+      static_cast<int64_t>(Nimg) * H * W >= (1ll << 31) || static_cast<int64_t>(taps) * C > 65536)
+    return -1;
+  if (conv3x3p_eligible(Nimg, H, W, C, N, taps, stride)) {
+    *BM = 128;
+    *BN = 64;
+    return 0;
+  }
+  if (const int tm = use_gemm2(M, N, C, taps, stride)) {
+    *BM = tm;
+    *BN = 65536 / tm;
+    return 1;
+  }
+  tile_of(M, N, BM, BN);
+  return 2;
+}
 
 size_t conv_gemm_part_floats(int64_t M, int N) {
   int BM, BN;

@@ -559,6 +559,11 @@ int gemm_conv_tm(int64_t M, int N, int C) {
 
 bool gemm_conv_eligible(int64_t M, int N, int C) { return gemm_conv_tm(M, N, C) != 0; }
 
+void gemm_dispatch_settings(int* gm, int* tall) {
+  *gm = gemm_gm();
+  *tall = tall_min_tiles();
+}
+
 hipError_t launch_gemm_conv(const GemmArgs& a0, int ep, hipStream_t st) {
   GemmArgs a = a0;
   a.conv = 1;

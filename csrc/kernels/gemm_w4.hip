@@ -333,6 +333,8 @@ int w4_ablate() {
 
 }  // namespace
 
+int gemm_w4_sched_setting() { return w4_sched(); }
+
 bool gemm_w4_eligible(int64_t M, int64_t N, int64_t K, int mode) {
   if (M < 8 || N < 8 || K < 64 || K % 64 || M % 8 || N % 8) return false;
   const int64_t tiles = ((M + 255) / 256) * ((N + 255) / 256);

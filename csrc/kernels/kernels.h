@@ -742,5 +742,14 @@ hipError_t launch_gemm_w4(const GemmArgs& a, int mode, hipStream_t st);
 // segments, fixed order); out bf16 [nseg][ldo] or fp32 when out_f32
 hipError_t launch_colsum_fold(const float* part, int64_t M, int N, int nseg, void* out, int64_t ldo,
                               int out_f32, hipStream_t st);
+// The read-once dispatch values of gemm.hip (CML_GEMM_GM, CML_GEMM2_TALL), gemm_w4.hip
+// (CML_W4_SCHED) and conv_gemm.hip (CML_CONV_GEMM_VARIANT / _NARROW / _SMALLM / _SMALLV,
+// CML_CONV_GEMM2, CML_GEMM2_S2) as this process read them, and the kernel launch_conv_gemm takes
+// for a shape (0 = conv3x3p.hip, 1 = gemm.hip's conv mode, 2 = conv_gemm.hip, -1 = rejected; BM x BN
+// its tile). Reports for tests: nothing here changes what is launched.
+void gemm_dispatch_settings(int* gm, int* tall);
+int gemm_w4_sched_setting();
+void conv_gemm_settings(int* variant, int* narrow, int* smallm, int* smallv, int* gemm2, int* s2);
+int conv_gemm_route(int Nimg, int H, int W, int C, int N, int taps, int stride, int* BM, int* BN);
 
 }  // namespace cml

@@ -1,10 +1,16 @@
-"""Stride-1 3x3 convolutions on gemm.hip's schedule (``launch_gemm_conv``: implicit-GEMM A
-operand gathered per tap by the DMA path, 16x16x32 MFMAs, four staggered phases per k-tile), which
-conv_gemm.hip routes to when the 256 x 256 tile grid applies and the pixel count is a multiple of
-256: plain output, the BN-statistics epilogue and the BN + ReLU backward sums epilogue, against
-fp32 / fp64 PyTorch oracles. Shapes: ResNet-50 layer-3 / layer-4 channel counts (256 / 512),
-image borders on every side (padded taps read the zero row); and the 512 x 128 tall tile of the
-128-channel (layer-2) convs, taken from 1024 such tiles (672 images of 28 x 28)."""
+"""3x3 convolutions through ``conv_gemm`` at ResNet-50 layer-3 / layer-4 channel counts
+(256 / 512) and the 128-channel (layer-2) convs: plain output, the BN-statistics epilogue and the
+BN + ReLU backward sums epilogue, against fp32 / fp64 PyTorch oracles, with image borders on every
+side (padded taps read the zero row).
+
+Which kernel runs (``ROUTES``, asserted through ``conv_gemm_route``): conv_gemm.hip hands a
+stride-1 3x3 conv to gemm.hip's schedule (``launch_gemm_conv``: implicit-GEMM A operand gathered
+per tap by the DMA path, 16x16x32 MFMAs, four staggered phases per k-tile) only when its own
+256 x 256 variant applies, and that needs at least CML_CONV_GEMM_SMALLM = 512 such tiles. The
+square shapes here have 4 to 98, so they run conv_gemm.hip's 128 x 128 tiles; only the 512 x 128
+tall tile of the 128-channel convs, taken from 1024 such tiles (672 images of 28 x 28), reaches
+gemm.hip. gemm.hip's square conv mode and conv_gemm.hip's 256 x 256 variant are covered, exactly,
+by test_conv_gemm_exact_gpu.py."""
 import pytest
 import torch
 import torch.nn.functional as F
@@ -33,6 +39,11 @@ def _rel(a, b):
 SHAPES = [(4, 256, 256, 16), (16, 512, 512, 8), (4, 64, 256, 16), (64, 256, 512, 14),
           (672, 128, 128, 28), (672, 64, 128, 28), (256, 512, 512, 7)]
 TALL = [(672, 128, 128, 28), (672, 64, 128, 28)]
+# the kernel and tile each SHAPES entry takes today (conv_gemm_route, default environment)
+ROUTES = {(4, 256, 256, 16): ("conv_gemm", 128, 128), (16, 512, 512, 8): ("conv_gemm", 128, 128),
+          (4, 64, 256, 16): ("conv_gemm", 128, 128), (64, 256, 512, 14): ("conv_gemm", 128, 128),
+          (672, 128, 128, 28): ("gemm2", 512, 128), (672, 64, 128, 28): ("gemm2", 512, 128),
+          (256, 512, 512, 7): ("conv_gemm", 128, 128)}
 
 
 @pytest.mark.parametrize("N,C,Co,H", TALL)
@@ -48,6 +59,7 @@ def test_gemm_conv_forward_vs_fp32(cuda, N, C, Co, H):
     x = _nhwc((torch.randn(N, C, H, H, device=cuda, generator=g0) + 0.25).bfloat16())
     w = (torch.randn(Co, C, 3, 3, device=cuda, generator=g0) * (9 * C) ** -0.5).bfloat16()
     assert (N * H * H) % 256 == 0
+    assert tuple(_lib().conv_gemm_route(N, H, H, C, Co, 9, 1)) == ROUTES[(N, C, Co, H)]
     wf = w.permute(0, 2, 3, 1).reshape(Co, 9 * C).contiguous()
     y = _lib().conv_gemm(x, wf, 9)
     ref = F.conv2d(x.float(), w.float(), padding=1)
@@ -124,6 +136,7 @@ def test_gemm_conv_deterministic(cuda, N, C, Co, H):
 # tall tile takes the 128-channel one (672 x 28 x 28 outputs); the 256-channel shape stays on
 # conv_gemm.hip (the square tile was no faster there) and checks that route too
 S2_SHAPES = [(672, 128, 128, 56), (768, 128, 256, 28)]
+S2_ROUTES = {(672, 128, 128, 56): ("gemm2", 512, 128), (768, 128, 256, 28): ("conv_gemm", 256, 256)}
 
 
 @pytest.mark.parametrize("N,C,Co,H", S2_SHAPES)
@@ -134,6 +147,7 @@ def test_gemm_conv_stride2_forward_and_stats(cuda, N, C, Co, H):
     wf = w.permute(0, 2, 3, 1).reshape(Co, 9 * C).contiguous()
     Ho = (H - 1) // 2 + 1
     zero = torch.zeros(256, device=cuda, dtype=torch.bfloat16)
+    assert tuple(_lib().conv_gemm_route(N, H, H, C, Co, 9, 2)) == S2_ROUTES[(N, C, Co, H)]
     y = _lib().conv_gemm(x, wf, 9, zero, 2)
     ref = F.conv2d(x.float(), w.float(), stride=2, padding=1)
     assert y.shape == ref.shape
