@@ -8,6 +8,7 @@ BASELINE.json config: "ResNet-50 bf16 DP=8 with Krum".
 """
 from __future__ import annotations
 
+import contextlib
 from typing import List, Optional
 
 import torch
@@ -327,6 +328,23 @@ class Bottleneck(nn.Module):
         z2 = self._conv2(out)
         return z2, (fconv.bn_stats(z2, self.bn2) if fuse3 else None)
 
+    def _next_head(self, z2: torch.Tensor, hw2: int):
+        """The successor's conv1 / bn1 for this block's recompute tail to compute as well
+        (ops.conv.tail_head_spec), or None: no successor set for this forward (``tail_heads``),
+        or one that would not take the fused conv1 + statistics path on our output."""
+        nxt = self.__dict__.get("_cml_next")
+        if nxt is None or not _P().fused_tail_head:
+            return None
+        c, bn = nxt.conv1, nxt.bn1
+        cout = self.conv3.out_channels
+        if not (nxt.training and _P().fused_conv1x1 and c.in_channels == cout
+                and c.weight.dtype == torch.bfloat16 and cout % 64 == 0
+                and c.out_channels % 64 == 0 and z2.is_cuda and z2.dtype == torch.bfloat16
+                and nxt.bn3.weight.dtype == torch.bfloat16 and _P().fused_bn
+                and fused_conv1x1_policy(cout, c.out_channels, hw2, 1, False)):
+            return None
+        return fconv.tail_head_spec(z2, cout, c, bn)
+
     def _tail_fused(self, x, z2, st2, fuse3: bool, hw2: int, link, dlink, use_links: bool,
                     out_link) -> torch.Tensor:
         """bn2 + ReLU + conv3 + bn3 + shortcut + ReLU."""
@@ -337,10 +355,13 @@ class Bottleneck(nn.Module):
         else:
             if down is None:
                 rec = recompute_tail_policy(planes)
-                if rec or fused_bn3_bwd_policy(planes):
-                    tail = fconv.bnrelu_conv1x1_bn_res_recompute if rec \
-                        else fconv.bnrelu_conv1x1_bn_res
-                    return tail(z2, self.bn2, st2, self.conv3, self.bn3, x, link, out_link)
+                if rec:
+                    return fconv.bnrelu_conv1x1_bn_res_recompute(
+                        z2, self.bn2, st2, self.conv3, self.bn3, x, link, out_link,
+                        self._next_head(z2, hw2))
+                if fused_bn3_bwd_policy(planes):
+                    return fconv.bnrelu_conv1x1_bn_res(z2, self.bn2, st2, self.conv3, self.bn3, x,
+                                                       link, out_link)
             elif _P().recompute_down_tail and self.bn3.eps == self.down_bn.eps:
                 xd = None
                 if fconv.down_tail_recompute_s2_ok(x, planes, down):
@@ -350,8 +371,9 @@ class Bottleneck(nn.Module):
                 elif fconv.down_tail_recompute_ok(x, planes, down):
                     xd = self._tap(x, dlink, use_links)
                 if xd is not None:
+                    head = self._next_head(z2, hw2) if down.stride == (1, 1) else None
                     return fconv.down_tail_recompute(z2, self.bn2, st2, self.conv3, self.bn3, xd,
-                                                     down, self.down_bn, out_link)
+                                                     down, self.down_bn, out_link, head)
             dg = conv1x1_policy(planes, planes * 4, hw2)[1]
             z, m3, i3 = fconv.bnrelu_conv1x1_bn_stats(z2, self.bn2, st2, self.conv3, self.bn3, dg,
                                                       own_wgrad_ok(planes, planes * 4)
@@ -420,6 +442,31 @@ class Bottleneck(nn.Module):
         return y
 
 
+@contextlib.contextmanager
+def tail_heads(owner: nn.Module, blocks):
+    """For one forward of ``blocks`` (Bottlenecks run back to back, each on its predecessor's
+    output): let a layer-1 recompute tail also compute its successor's conv1 and bn1 statistics
+    (PerfPolicy.fused_tail_head, tail_head.hip). The successor is a plain attribute set around the
+    forward, never a registered submodule: ``state_dict`` keys and ``parameters()`` order stay as
+    they are. The tail reads a weight of a unit whose forward has not begun, so nothing is set
+    while ``owner``'s engine still exchanges any of those parameters (ops.conv.params_pending)."""
+    pairs = []
+    if _P().fused_tail_head and torch.is_grad_enabled():
+        pairs = [(a, b) for a, b in zip(blocks[:-1], blocks[1:])
+                 if a.training and b.training and a.conv3.in_channels == 64
+                 and a.conv3.out_channels == b.conv1.in_channels]
+        ps = [p for _, b in pairs for p in (b.conv1.weight, b.bn1.weight, b.bn1.bias)]
+        if pairs and fconv.params_pending(owner, ps):
+            pairs = []
+    try:
+        for a, b in pairs:
+            object.__setattr__(a, "_cml_next", b)
+        yield
+    finally:
+        for a, _ in pairs:
+            a.__dict__.pop("_cml_next", None)
+
+
 class ResNet(nn.Module):
     def __init__(self, layers: List[int], num_classes: int = 1000, width: int = 64):
         super().__init__()
@@ -482,7 +529,8 @@ class ResNet(nn.Module):
         batched = (pol.batch_wlayouts and self.training and torch.is_grad_enabled()
                    and not fconv.params_pending(self, ws) and fconv.prefetch_wlayouts(ws))
         try:
-            x = self.layer4(self.layer3(self.layer2(self.layer1(x))))
+            with tail_heads(self, blocks):
+                x = self.layer4(self.layer3(self.layer2(self.layer1(x))))
         finally:
             if batched:
                 fconv.clear_wlayouts()

@@ -216,16 +216,21 @@ def _conv1_bn_bwd(rec, dy: torch.Tensor, x: torch.Tensor, w: torch.Tensor, link)
 class _Conv1x1BNStatsFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w, rmean, rvar, stride, eps, momentum, dgrad_gemm, own_wgrad, link,
-                aff=None, hand=None):
+                aff=None, hand=None, head=None):
         if hand is not None:   # a record an aborted step left behind must not reach this backward
             hand.clear()
             hand.armed = _conv1_bwd_armed(ctx, x, w, stride, link)
         ctx.hand = hand
-        out = lib().conv1x1_bn_fwd(x, w, None, None, rmean, rmean, rvar, stride, True, eps,
-                                   momentum, *(aff or (None, None)))
-        y, mean, invstd = out[:3]
-        if aff is not None:   # the next BN's affine from the statistics' finalize launch
-            _stash_affine(mean, out[3], out[4], aff)
+        if head is not None:
+            # x's producer (a layer-1 recompute tail, tail_head.hip) already made this conv's
+            # output, its statistics, the running-statistics update and the affine (_take_head)
+            y, mean, invstd = head.z1n, head.mean, head.invstd
+        else:
+            out = lib().conv1x1_bn_fwd(x, w, None, None, rmean, rmean, rvar, stride, True, eps,
+                                       momentum, *(aff or (None, None)))
+            y, mean, invstd = out[:3]
+            if aff is not None:   # the next BN's affine from the statistics' finalize launch
+                _stash_affine(mean, out[3], out[4], aff)
         ctx.wt = cached_wt(w)
         ctx.save_for_backward(x, w)
         ctx.stride, ctx.dgrad_gemm, ctx.own_wgrad, ctx.link = stride, dgrad_gemm, own_wgrad, link
@@ -242,7 +247,7 @@ class _Conv1x1BNStatsFn(torch.autograd.Function):
             check_deferred_grad(rec, dy)
             out = _conv1_bn_bwd(rec, dy, x, w, ctx.link)
             if out is not None:
-                return out + (None,) * 10
+                return out + (None,) * 11
             dy = lib().bn_bwd_apply(dy, *rec[:7])
         # the weight gradient on the side stream (large batches) while the data gradient runs
         dw, h = _wgrad_fork(lambda d, a, b: _wgrad(d, a, b, ctx.stride, ctx.own_wgrad), dy, x, w,
@@ -250,7 +255,7 @@ class _Conv1x1BNStatsFn(torch.autograd.Function):
         dx = _dgrad(dy, x, w, ctx.stride, ctx.dgrad_gemm, ctx.link, ctx.wt) \
             if ctx.needs_input_grad[0] else None
         dw = _wgrad_join(dw, h)
-        return dx, dw, None, None, None, None, None, None, None, None, None, None
+        return (dx, dw) + (None,) * 11
 
 
 class _BNReLUConv1x1BNStatsFn(torch.autograd.Function):
@@ -389,6 +394,85 @@ def _affine(gamma: torch.Tensor, beta: torch.Tensor, mean: torch.Tensor, invstd:
     return ab[0], ab[1]
 
 
+# PerfPolicy.fused_tail_head -- a layer-1 recompute tail also computes the NEXT block's conv1
+# (1x1, 256 -> p') and bn1's statistics from the y tile it holds on chip (tail_head.hip), so conv1's
+# launch and its read of y (4 of the layer's 64-channel tensors) disappear. The result travels on y
+# (``y._cml_head``) to the consumer's ``conv1x1_bn_stats``, like the residual link.
+
+
+class TailHead:
+    """The successor's conv1 / bn1 modules, given to a tail that may compute them."""
+    __slots__ = ("conv", "bn")
+
+    def __init__(self, conv, bn):
+        self.conv, self.bn = conv, bn
+
+
+class HeadResult:
+    """conv1's output and statistics made by the producer of ``y`` for the weight ``w`` (the
+    parameter object and its version when it was read)."""
+    __slots__ = ("y", "w", "wv", "z1n", "mean", "invstd")
+
+    def __init__(self, y, w, wv, z1n, mean, invstd):
+        self.y, self.w, self.wv = weakref.ref(y), w, wv
+        self.z1n, self.mean, self.invstd = z1n, mean, invstd
+
+
+def tail_head_spec(z: torch.Tensor, cout: int, conv, bn) -> Optional[TailHead]:
+    """A ``TailHead`` when the tail of ``z`` (bn2's input, p channels; ``cout`` output channels)
+    can also run the successor's ``conv`` (stride-1 1x1, cout -> p') and ``bn``'s training
+    statistics: policy on and enough pixels, bf16 NHWC on the GPU, a shape with a plan."""
+    pol = _P()
+    w = conv.weight
+    M = z.shape[0] * z.shape[2] * z.shape[3]
+    ok = (pol.fused_tail_head and M >= pol.fused_tail_head_min_pixels
+          and torch.is_grad_enabled() and z.is_cuda and z.dtype == torch.bfloat16
+          and w.dtype == torch.bfloat16 and w.dim() == 4 and w.shape[1] == cout
+          and w.shape[2] == 1 and w.shape[3] == 1 and tuple(conv.stride) == (1, 1)
+          and w.device == z.device and w.data_ptr() % 16 == 0
+          and bn.training and bn.running_mean is not None and bn.running_var is not None
+          and lib().tail_head_ok(M, z.shape[1], cout, w.shape[0]))
+    return TailHead(conv, bn) if ok else None
+
+
+def _head_args(head: TailHead):
+    """The trailing arguments of the ``*_head`` launches, and bn's (gamma, beta) or None."""
+    bn = head.bn
+    aff = _fin_aff(bn)
+    return (head.conv.weight.detach(), bn.running_mean, bn.running_var, bn.eps,
+            bn.momentum) + (aff or (None, None)), aff
+
+
+def _head_out(out, aff):
+    """(z1n, mean, invstd) of a ``*_head`` launch's result, bn's affine parked on the mean."""
+    z1n, mean, invstd = out[2:5]
+    if aff is not None:
+        _stash_affine(mean, out[5], out[6], aff)
+    return z1n, mean, invstd
+
+
+def _give_head(out, head: TailHead, wv: int) -> torch.Tensor:
+    """Park a tail's (y, z1n, mean, invstd) on y for the consumer (``_take_head``)."""
+    y, z1n, mean, invstd = out
+    y._cml_head = HeadResult(y, head.conv.weight, wv, z1n, mean, invstd)
+    return y
+
+
+def _take_head(x: torch.Tensor, w: torch.Tensor, stride: int) -> Optional[HeadResult]:
+    """The conv1 result ``x`` carries, if it was made for this very tensor and this very weight
+    (same object, unchanged since); anything else is dropped and the conv runs."""
+    rec = getattr(x, "_cml_head", None)
+    if rec is None:
+        return None
+    del x._cml_head
+    if (isinstance(rec, HeadResult) and rec.y() is x and rec.w is w and rec.wv == w._version
+            and stride == 1 and torch.is_grad_enabled()
+            and rec.z1n.shape == (x.shape[0], w.shape[0], x.shape[2], x.shape[3])
+            and rec.z1n.device == x.device):
+        return rec
+    return None
+
+
 def _stats_gram_affine(L, gram, cy, w, M, rmean, rvar, eps, momentum, gamma, beta):
     """``bn_stats_gram`` -> (mean, invstd, sc, bi): the affine from the finalize launch itself
     (bit-identical to ``_affine``) when PerfPolicy.bn_affine_kernel is on, else ``_affine``."""
@@ -496,7 +580,7 @@ class _RecomputeTailFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, z, g2, b2, mean2, invstd2, w, g3, b3, res, rmean3, rvar3, eps, momentum,
-                res_link, out_link):
+                res_link, out_link, head=None):
         sc, bi = _affine(g2, b2, mean2, invstd2)
         wc = w.contiguous()
         L = lib()
@@ -510,16 +594,27 @@ class _RecomputeTailFn(torch.autograd.Function):
         else:
             m3, i3 = L.conv1x1_bn_stats_only(z, wc, sc, bi, rmean3, rmean3, rvar3, eps, momentum)
             sc3, bi3 = _affine(g3, b3, m3, i3)
-        y, mask = L.conv1x1_bnres(z, wc, sc, bi, sc3, bi3, res)
+        hd = None
+        if head is None:
+            y, mask = L.conv1x1_bnres(z, wc, sc, bi, sc3, bi3, res)
+        else:   # + the successor's conv1 and bn1 statistics from the y tile on chip
+            hargs, aff = _head_args(head)
+            out = L.conv1x1_bnres_head(z, wc, sc, bi, sc3, bi3, res, *hargs)
+            y, mask = out[:2]
+            hd = _head_out(out, aff)
         ctx.gram = (gram, cy)
         ctx.save_for_backward(z, g2, b2, mean2, invstd2, w, sc, bi, mask, g3, m3, i3)
         ctx.res_link, ctx.out_link = res_link, out_link
         if out_link is not None:
             out_link.bn_ctx = None   # the consumer's conv1 epilogue owes this tail no sums
-        return y
+        if hd is None:
+            return y
+        ctx.mark_non_differentiable(*hd)
+        ctx.set_materialize_grads(False)   # no zero-filled grads for the head's outputs
+        return (y,) + hd
 
     @staticmethod
-    def backward(ctx, gy):
+    def backward(ctx, gy, *_head_grads):
         z, g2, b2, mean2, invstd2, w, sc, bi, mask, g3, m3, i3 = ctx.saved_tensors
         gy, _ = _take_out_link(ctx.out_link, gy)
         M = gy.numel() // gy.shape[1]
@@ -540,7 +635,7 @@ class _RecomputeTailFn(torch.autograd.Function):
         dw = dw.view_as(w) if need_dw else None
         dz, dg2, db2 = _cat_dgrad_bn2(L, gy, mask, z, sc, bi, w_cat, bias, g2, b2, mean2, invstd2)
         dres = _park_masked(gy, mask, ctx.res_link) if ctx.needs_input_grad[8] else None
-        return (dz, dg2, db2, None, None, dw, dg3, db3, dres) + (None,) * 6
+        return (dz, dg2, db2, None, None, dw, dg3, db3, dres) + (None,) * 7
 
 
 class _RecomputeDownTailFn(torch.autograd.Function):
@@ -558,7 +653,7 @@ class _RecomputeDownTailFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, z, g2, b2, mean2, invstd2, w3, g3, b3, rm3, rv3, x, wd, gd, bd, rmd, rvd,
-                eps, momentum, out_link):
+                eps, momentum, out_link, head=None):
         sc, bi = _affine(g2, b2, mean2, invstd2)
         L = lib()
         w3c, wdc = w3.contiguous(), wd.contiguous()
@@ -588,17 +683,28 @@ class _RecomputeDownTailFn(torch.autograd.Function):
             w_cat = scaled_cat(w3c.view(Co, P_), sc3, wdc.view(Co, Cin), scd)
         dev = z.device
         # x: the block input, a ReLU output, staged as is
-        y, mask = L.conv1x1_cat_bnres(z, x, sc, bi, None, None, w_cat,
-                                      _const(Co, 1.0, dev), bias)
+        hd = None
+        if head is None:
+            y, mask = L.conv1x1_cat_bnres(z, x, sc, bi, None, None, w_cat,
+                                          _const(Co, 1.0, dev), bias)
+        else:   # + the successor's conv1 and bn1 statistics from the y tile on chip
+            hargs, aff = _head_args(head)
+            out = L.conv1x1_cat_bnres_head(z, x, sc, bi, w_cat, _const(Co, 1.0, dev), bias, *hargs)
+            y, mask = out[:2]
+            hd = _head_out(out, aff)
         ctx.save_for_backward(z, g2, b2, mean2, invstd2, w3, sc, bi, mask, g3, m3, i3, x, wd, gd,
                               md, idd)
         ctx.out_link = out_link
         if out_link is not None:
             out_link.bn_ctx = None
-        return y
+        if hd is None:
+            return y
+        ctx.mark_non_differentiable(*hd)
+        ctx.set_materialize_grads(False)   # no zero-filled grads for the head's outputs
+        return (y,) + hd
 
     @staticmethod
-    def backward(ctx, gy):
+    def backward(ctx, gy, *_head_grads):
         (z, g2, b2, mean2, invstd2, w3, sc, bi, mask, g3, m3, i3, x, wd, gd, md,
          idd) = ctx.saved_tensors
         gy, _ = _take_out_link(ctx.out_link, gy)
@@ -628,7 +734,7 @@ class _RecomputeDownTailFn(torch.autograd.Function):
         if ctx.needs_input_grad[10]:
             dx = L.conv1x1_cat(gy, mask, x, None, None, w_catd, biasd)   # x staged as is
         return (dz, dg2, db2, None, None, dw3, dg3, db3, None, None, dx, dwd, dgd, dbd) + \
-            (None,) * 5
+            (None,) * 6
 
 
 class _Subsample2Fn(torch.autograd.Function):
@@ -720,14 +826,17 @@ def down_tail_recompute_ok(x: torch.Tensor, planes: int, down_conv) -> bool:
 
 
 def down_tail_recompute(z: torch.Tensor, bn_a, stats_a, conv, bn_b, x: torch.Tensor, down_conv,
-                        down_bn, out_link=None) -> torch.Tensor:
-    """y = relu(bn_b(conv(relu(bn_a(z)))) + down_bn(down_conv(x))) (see _RecomputeDownTailFn)."""
+                        down_bn, out_link=None, head: Optional[TailHead] = None) -> torch.Tensor:
+    """y = relu(bn_b(conv(relu(bn_a(z)))) + down_bn(down_conv(x))) (see _RecomputeDownTailFn).
+    ``head``: the successor's conv1 / bn1 to compute as well (``tail_head_spec``)."""
     mean, invstd = stats_a
-    return _RecomputeDownTailFn.apply(z, bn_a.weight, bn_a.bias, mean, invstd, conv.weight,
-                                      bn_b.weight, bn_b.bias, bn_b.running_mean,
-                                      bn_b.running_var, x, down_conv.weight, down_bn.weight,
-                                      down_bn.bias, down_bn.running_mean, down_bn.running_var,
-                                      bn_b.eps, bn_b.momentum, out_link)
+    wv = head.conv.weight._version if head is not None else 0
+    out = _RecomputeDownTailFn.apply(z, bn_a.weight, bn_a.bias, mean, invstd, conv.weight,
+                                     bn_b.weight, bn_b.bias, bn_b.running_mean,
+                                     bn_b.running_var, x, down_conv.weight, down_bn.weight,
+                                     down_bn.bias, down_bn.running_mean, down_bn.running_var,
+                                     bn_b.eps, bn_b.momentum, out_link, head)
+    return out if head is None else _give_head(out, head, wv)
 
 
 def recompute_tail_ok(planes: int) -> bool:
@@ -736,13 +845,17 @@ def recompute_tail_ok(planes: int) -> bool:
 
 
 def bnrelu_conv1x1_bn_res_recompute(z: torch.Tensor, bn_a, stats_a, conv, bn_b,
-                                    res: torch.Tensor, res_link=None,
-                                    out_link=None) -> torch.Tensor:
-    """``bnrelu_conv1x1_bn_res`` without a stored z3 (see _RecomputeTailFn)."""
+                                    res: torch.Tensor, res_link=None, out_link=None,
+                                    head: Optional[TailHead] = None) -> torch.Tensor:
+    """``bnrelu_conv1x1_bn_res`` without a stored z3 (see _RecomputeTailFn). ``head``: the
+    successor's conv1 / bn1 to compute as well (``tail_head_spec``)."""
     mean, invstd = stats_a
-    return _RecomputeTailFn.apply(z, bn_a.weight, bn_a.bias, mean, invstd, conv.weight,
-                                  bn_b.weight, bn_b.bias, res, bn_b.running_mean,
-                                  bn_b.running_var, bn_b.eps, bn_b.momentum, res_link, out_link)
+    wv = head.conv.weight._version if head is not None else 0
+    out = _RecomputeTailFn.apply(z, bn_a.weight, bn_a.bias, mean, invstd, conv.weight,
+                                 bn_b.weight, bn_b.bias, res, bn_b.running_mean,
+                                 bn_b.running_var, bn_b.eps, bn_b.momentum, res_link, out_link,
+                                 head)
+    return out if head is None else _give_head(out, head, wv)
 
 
 def res_tail_ok(planes: int) -> bool:
@@ -1093,7 +1206,7 @@ def conv1x1_bn_stats(x: torch.Tensor, conv, bn, stride: int = 1, dgrad_gemm: boo
     bottleneck conv1's ``ops.bn.DeferredBN1``."""
     return _Conv1x1BNStatsFn.apply(x, conv.weight, bn.running_mean, bn.running_var, stride,
                                    bn.eps, bn.momentum, dgrad_gemm, own_wgrad, link, _fin_aff(bn),
-                                   hand)
+                                   hand, _take_head(x, conv.weight, stride))
 
 
 def bnrelu_conv1x1_bn_stats(z: torch.Tensor, bn_a, stats_a, conv, bn_b, dgrad_gemm: bool = False,

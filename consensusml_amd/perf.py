@@ -72,6 +72,11 @@ class PerfPolicy:
                                           # persistent, one workgroup per CU over 64-pixel tiles,
                                           # and below a few tiles per CU the three launches win
                                           # (profiles/conv1_bwd/)
+    fused_tail_head: bool = True          # the next block's conv1 (+ bn1 statistics) inside a
+                                          # layer-1 recompute tail (tail_head.hip; p 64, p' 64 / 128)
+    fused_tail_head_min_pixels: int = 802816   # ... from this many pixels N H W on (batch 256 at
+                                          # 56 x 56, the smallest size measured:
+                                          # profiles/tail_head/); smaller sizes keep two launches
     # ---------------------------------------------------------------- 3x3 convolutions
     own_dgrad3x3: bool = True             # conv_gemm.hip data gradient
     conv3x3_bn_stats: bool = True         # conv_gemm.hip forward + BN statistics epilogue
@@ -158,6 +163,8 @@ class PerfPolicy:
             bn_affine_kernel=_env_bool("CML_BN_AFFINE_KERNEL", True),
             fused_conv1_bwd=_env_bool("CML_FUSED_CONV1_BWD", True),
             fused_conv1_bwd_min_pixels=_env_int("CML_FUSED_CONV1_BWD_MIN_PIXELS", 65536),
+            fused_tail_head=_env_bool("CML_FUSED_TAIL_HEAD", True),
+            fused_tail_head_min_pixels=_env_int("CML_FUSED_TAIL_HEAD_MIN_PIXELS", 802816),
             own_dgrad3x3=_env_bool("CML_DGRAD3X3", True),
             conv3x3_bn_stats=_env_bool("CML_CONV3X3_BN_STATS", True),
             bn1_dgrad_sums=_env_bool("CML_BN1_DGRAD_SUMS", True),

@@ -1277,6 +1277,96 @@ std::vector<Tensor> conv1x1_cat_bnres(const Tensor& x1, const Tensor& x2, const 
   return {y, mask};
 }
 
+// The layer-1 recompute tails with the next block's conv1 inside (tail_head.hip): conv1x1_bnres /
+// conv1x1_cat_bnres (x staged as is) plus z1n = conv1x1(y, w1n) and its training BN statistics as
+// conv1x1_bn_fwd(y, w1n, shift = rmean) gives them -> {y, mask, z1n, mean, invstd[, sc1, bi1]}.
+// wgs != 0: that many pixel ranges (tests: more ranges than tiles).
+bool tail_head_ok(int64_t M, int64_t p, int64_t Cout, int64_t p2) {
+  int S;
+  return cml::tail_head_plan(M, static_cast<int>(p), static_cast<int>(Cout), static_cast<int>(p2),
+                             &S);
+}
+
+namespace {
+std::vector<Tensor> tail_head(const char* what, const Tensor& z, const Tensor* x2, const Tensor& w,
+                              const Tensor& sc, const Tensor& bi, const Tensor& ep_sc,
+                              const Tensor& ep_bi, const Tensor* res, const Tensor& w1n,
+                              const Tensor& rmean, const Tensor& rvar, double eps, double momentum,
+                              const optional<Tensor>& gamma, const optional<Tensor>& beta,
+                              int64_t wgs) {
+  check_nhwc(z, "z");
+  TORCH_CHECK(z.dim() == 4, what, ": 4-D NHWC z");
+  const int64_t N = z.size(0), p = z.size(1), H = z.size(2), W = z.size(3), M = N * H * W;
+  const int64_t K = x2 ? 2 * p : p, Co = w.size(0);
+  check_dev(w, "w");
+  check_dev(w1n, "w1n");
+  TORCH_CHECK(w.scalar_type() == at::kBFloat16 && w.is_contiguous() && w.numel() == Co * K, what,
+              ": w must be contiguous bf16 [Cout, K]");
+  const int64_t p2 = w1n.size(0);
+  TORCH_CHECK(w1n.scalar_type() == at::kBFloat16 && w1n.numel() == p2 * Co &&
+                  (w1n.dim() == 2 || (w1n.dim() == 4 && w1n.size(1) == Co)) &&
+                  (w1n.is_contiguous() ||
+                   (w1n.dim() == 4 && w1n.is_contiguous(at::MemoryFormat::ChannelsLast))),
+              what, ": w1n must be bf16 [p', Cout(, 1, 1)]");
+  TORCH_CHECK(w.device() == z.device() && w1n.device() == z.device(), what, ": one device");
+  int S = 0;
+  TORCH_CHECK(wgs >= 0 && cml::tail_head_plan(M, static_cast<int>(p), static_cast<int>(Co),
+                                              static_cast<int>(p2), &S, static_cast<int>(wgs)),
+              what, ": no plan for this shape (tail_head_ok)");
+  for (const Tensor* t : {x2, res}) {
+    if (!t) continue;
+    check_nhwc(*t, "x / res");
+    TORCH_CHECK(t->dim() == 4 && t->size(0) == N && t->size(1) == (t == x2 ? p : Co) &&
+                    t->size(2) == H && t->size(3) == W && t->device() == z.device(),
+                what, ": x / res shape");
+  }
+  const c10::DeviceGuard guard(z.device());
+  auto f32 = z.options().dtype(at::kFloat);
+  Tensor y = at::empty({N, Co, H, W}, z.options().memory_format(at::MemoryFormat::ChannelsLast));
+  Tensor z1n = at::empty({N, p2, H, W}, z.options().memory_format(at::MemoryFormat::ChannelsLast));
+  Tensor mask = at::empty({M, Co / 8}, z.options().dtype(at::kByte));
+  Tensor mean = at::empty({p2}, f32), invstd = at::empty({p2}, f32);
+  Tensor part = at::empty({static_cast<int64_t>(S) * 2 * p2}, f32);
+  Tensor asc, abi;
+  cml::BnAffineOut ao{};
+  const cml::BnAffineOut* aff = aff_out(gamma, beta, p2, z, what, asc, abi, ao);
+  float* rm = opt_ptr<float>(rmean, at::kFloat, "running_mean", p2);
+  CML_CHECK_HIP(cml::launch_tail_head(
+      z.data_ptr(), x2 ? x2->data_ptr() : nullptr, w.data_ptr(),
+      opt_ptr<const float>(sc, at::kFloat, "sc", p), opt_ptr<const float>(bi, at::kFloat, "bi", p),
+      opt_ptr<const float>(ep_sc, at::kFloat, "ep_sc", Co),
+      opt_ptr<const float>(ep_bi, at::kFloat, "ep_bi", Co), res ? res->data_ptr() : nullptr,
+      y.data_ptr(), mask.data_ptr<uint8_t>(), w1n.data_ptr(), z1n.data_ptr(), rm,
+      part.data_ptr<float>(), S, mean.data_ptr<float>(), invstd.data_ptr<float>(), rm,
+      opt_ptr<float>(rvar, at::kFloat, "running_var", p2), static_cast<float>(eps),
+      static_cast<float>(momentum), aff, M, static_cast<int>(p), static_cast<int>(Co),
+      static_cast<int>(p2), cur_stream()));
+  if (aff) return {y, mask, z1n, mean, invstd, asc, abi};
+  return {y, mask, z1n, mean, invstd};
+}
+}  // namespace
+
+std::vector<Tensor> conv1x1_bnres_head(const Tensor& z, const Tensor& w3, const Tensor& sc,
+                                       const Tensor& bi, const Tensor& sc3, const Tensor& bi3,
+                                       const Tensor& res, const Tensor& w1n, const Tensor& rmean,
+                                       const Tensor& rvar, double eps, double momentum,
+                                       const optional<Tensor>& gamma,
+                                       const optional<Tensor>& beta, int64_t wgs) {
+  return tail_head("conv1x1_bnres_head", z, nullptr, w3, sc, bi, sc3, bi3, &res, w1n, rmean, rvar,
+                   eps, momentum, gamma, beta, wgs);
+}
+
+std::vector<Tensor> conv1x1_cat_bnres_head(const Tensor& z, const Tensor& x, const Tensor& sc,
+                                           const Tensor& bi, const Tensor& w_cat,
+                                           const Tensor& ep_sc, const Tensor& ep_bi,
+                                           const Tensor& w1n, const Tensor& rmean,
+                                           const Tensor& rvar, double eps, double momentum,
+                                           const optional<Tensor>& gamma,
+                                           const optional<Tensor>& beta, int64_t wgs) {
+  return tail_head("conv1x1_cat_bnres_head", z, &x, w_cat, sc, bi, ep_sc, ep_bi, nullptr, w1n,
+                   rmean, rvar, eps, momentum, gamma, beta, wgs);
+}
+
 // y = [(mask ? g : 0) | f2(x2)] w^T + bias (two sources concatenated along K): g [N, K1, H, W],
 // mask [M, K1 / 8], x2 [N, K2, H, W] NHWC bf16; f2 = max(x2 sc2 + bi2, 0) (fp32 [K2]) or x2 itself
 // (None); bias fp32 [Cout] or None; w [Cout, K1 + K2] contiguous bf16 -> y [N, Cout, H, W] NHWC.
@@ -2984,6 +3074,20 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("invstd"), py::arg("dgamma_out") = py::none(), py::arg("dbeta_out") = py::none(),
         "conv1x1_cat + the sums of the BN + ReLU backward its output feeds (+ optionally that "
         "BN's parameter gradients)");
+  m.def("tail_head_ok", &tail_head_ok, py::arg("M"), py::arg("p"), py::arg("Cout"), py::arg("p2"),
+        "whether tail_head.hip has a plan for this (pixels, planes, Cout, next planes)");
+  m.def("conv1x1_bnres_head", &conv1x1_bnres_head, py::arg("z"), py::arg("w3"), py::arg("sc"),
+        py::arg("bi"), py::arg("sc3"), py::arg("bi3"), py::arg("res"), py::arg("w1n"),
+        py::arg("rmean"), py::arg("rvar"), py::arg("eps"), py::arg("momentum"),
+        py::arg("gamma") = py::none(), py::arg("beta") = py::none(), py::arg("wgs") = 0,
+        "conv1x1_bnres + the next block's conv1 and its BN statistics "
+        "-> {y, mask, z1n, mean, invstd[, sc1, bi1]}");
+  m.def("conv1x1_cat_bnres_head", &conv1x1_cat_bnres_head, py::arg("z"), py::arg("x"),
+        py::arg("sc"), py::arg("bi"), py::arg("w_cat"), py::arg("ep_sc"), py::arg("ep_bi"),
+        py::arg("w1n"), py::arg("rmean"), py::arg("rvar"), py::arg("eps"), py::arg("momentum"),
+        py::arg("gamma") = py::none(), py::arg("beta") = py::none(), py::arg("wgs") = 0,
+        "conv1x1_cat_bnres (x staged as is) + the next block's conv1 and its BN statistics "
+        "-> {y, mask, z1n, mean, invstd[, sc1, bi1]}");
   m.def("bn_affine", &bn_affine, "BN affine (gamma invstd, beta - mean sc) of batch statistics");
   m.def("bn_bwd_apply", &bn_bwd_apply, "apply half of a BN + ReLU backward from its sums");
   m.def("split_search_sampled", &split_search_sampled,

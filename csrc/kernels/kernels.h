@@ -598,6 +598,23 @@ hipError_t launch_bn_stats_finalize(const float* part, int R, int BN, int N, int
                                    float* invstd, float* rmean, float* rvar, hipStream_t st,
                                    float* fold = nullptr, const BnAffineOut* aff = nullptr);
 
+// A layer-1 recompute tail with the next block's conv1 inside (tail_head.hip): y [M][256] and its
+// ReLU bit mask as launch_conv1x1_bnres (x2 null: z [M][64] with bn2's affine sc2 / bi2, w [256][64],
+// res [M][256]) or launch_conv1x1_cat_bnres (x2 [M][64] staged as is, w [256][128], res null)
+// write them, bit for bit; plus z1n [M][p2] = y w1n^T (w1n [p2][256] bf16, p2 in {64, 128}) and its
+// training BN statistics, as launch_conv1x1_bn_fwd on y gives them (shifted sums of the stored
+// bf16 values, finalize with running statistics and the optional affine). part: wgs x 2 x p2
+// floats with wgs from tail_head_plan (false: shape not supported; want != 0: that many pixel
+// ranges, empty ones included). Deterministic: one partial row per workgroup, no atomics.
+bool tail_head_plan(int64_t M, int p, int Cout, int p2, int* wgs, int want = 0);
+hipError_t launch_tail_head(const void* z, const void* x2, const void* w, const float* sc2,
+                            const float* bi2, const float* ep_sc, const float* ep_bi,
+                            const void* res, void* y, uint8_t* ymask, const void* w1n, void* z1n,
+                            const float* shift, float* part, int wgs, float* mean, float* invstd,
+                            float* rmean, float* rvar, float eps, float momentum,
+                            const BnAffineOut* aff, int64_t M, int p, int Cout, int p2,
+                            hipStream_t st);
+
 // Backward variants of the fused 1x1 conv (conv1x1.hip), stride 1, W given as [N][K] (for a data
 // gradient: the forward weight transposed).
 //   bnbwd: y = f(g) W^T with f = ca (mask ? g : 0) + cb z + cc per input channel (a BN + ReLU

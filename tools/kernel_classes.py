@@ -9,6 +9,7 @@ import sys
 CLASSES = [
     ("conv1 backward + bn1 apply, dX and dW in one pass (conv1_bwd.hip)",
      r"cml::.*conv1_bwd_kernel"),
+    ("recompute tail + the next block's conv1 (tail_head.hip)", r"cml::.*tail_head_kernel"),
     ("BatchNorm passes (bn_act.hip)", r"cml::.*bn_(apply|stats|bwd|finalize|apply2|bwd_apply2|bwd_reduce2)"),
     ("fused 1x1 conv + BN (conv1x1.hip, conv1x1g.hip)",
      r"cml::.*(conv1x1_bn|conv1x1_bnbwd|bn_bwd_coeffs|conv1x1g_|conv1x1q_)"),
