@@ -3207,6 +3207,22 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     const char* names[] = {"conv3x3p", "gemm2", "conv_gemm"};
     return py::make_tuple(std::string(names[r]), BM, BN);
   }, "(path, BM, BN) of the kernel conv_gemm launches for this shape: conv3x3p | gemm2 | conv_gemm");
+  m.def("bn_geometry", [](int64_t M, int64_t C) {
+    int nb = 0, grid = 0;
+    int64_t rpb = 0;
+    TORCH_CHECK(C >= 8 && C <= 2048 && cml::bn_geometry(M, static_cast<int>(C), &nb, &rpb, &grid),
+                "bn_geometry: shape not accepted by the BN launches");
+    return py::make_tuple(nb, rpb, grid);
+  }, py::arg("M"), py::arg("C"),
+        "(nb, rpb, apply_grid) of bn_act.hip's launches for x [M, C] in this process");
+  m.def("bn_settings", [] {
+    int nt, cap;
+    cml::bn_settings(&nt, &cap);
+    py::dict d;
+    d["bn_nt"] = nt;
+    d["bn_grid_cap"] = cap;
+    return d;
+  }, "the read-once BN switches (CML_BN_NT, CML_BN_GRID_CAP) as this process read them");
   m.def("gemm_nt_pick", &gemm_nt_pick, "EP_STORE tile choice of gemm_nt: 256, 128 or 0 (none)");
   m.attr("CMB_SORTED") = static_cast<int>(cml::CMB_SORTED);
   m.attr("CMB_WEIGHTED") = static_cast<int>(cml::CMB_WEIGHTED);

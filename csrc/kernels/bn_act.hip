@@ -58,10 +58,16 @@ __device__ __forceinline__ void ld8(const bf16* p, float (&o)[8]) {
     load_vec<bf16, 8>(p, o);
   }
 }
+int bn_nt_value() {
+  static const int v = [] {
+    const char* e = getenv("CML_BN_NT");
+    return e ? atoi(e) : 0;
+  }();
+  return v;
+}
 void bn_nt_init() {
   static const bool done = [] {
-    const char* e = getenv("CML_BN_NT");
-    const int v = e ? atoi(e) : 0;
+    const int v = bn_nt_value();
     if (v) (void)hipMemcpyToSymbol(HIP_SYMBOL(g_bn_nt), &v, sizeof(int));
     return true;
   }();
@@ -594,6 +600,20 @@ int apply_grid(int64_t M, int C) {
 size_t bn_workspace_bytes(int64_t M, int C) {
   const BNGeom g = geom(M, C);
   return static_cast<size_t>(g.nb) * 2 * C * sizeof(float);
+}
+
+bool bn_geometry(int64_t M, int C, int* nb, int64_t* rpb, int* grid) {
+  if (C < 8 || C % 8 != 0 || C / 8 > kBT || (kBT % (C / 8)) != 0 || M < 1) return false;
+  const BNGeom g = geom(M, C);
+  *nb = g.nb;
+  *rpb = g.rpb;
+  *grid = apply_grid(M, C);
+  return true;
+}
+
+void bn_settings(int* nt, int* grid_cap) {
+  *nt = bn_nt_value();
+  *grid_cap = apply_cap();
 }
 
 hipError_t launch_bn_fwd(const void* x, const void* res, void* y, void* mask, int64_t M, int C,

@@ -144,6 +144,11 @@ hipError_t launch_gossip_mix(int dtype, float* master, void* param_out, const vo
 // Backward recomputes the ReLU mask from x, writes dx (and dres = dz when res != null), dgamma /
 // dbeta (bf16) and the per-channel sums sdz / sdzx (fp32 [C]). ``work``: bn_workspace_bytes.
 size_t bn_workspace_bytes(int64_t M, int C);
+// Reports for tests (nothing here changes what is launched): the reduction passes' workgroups nb
+// and rows per workgroup rpb and the apply passes' grid for x[M, C] in this process (false: the
+// launches reject the shape), and the read-once switches CML_BN_NT / CML_BN_GRID_CAP as read.
+bool bn_geometry(int64_t M, int C, int* nb, int64_t* rpb, int* apply_grid);
+void bn_settings(int* nt, int* grid_cap);
 // mask (optional, only with res && relu): [M, C/8] bytes, one ReLU bit per element.
 hipError_t launch_bn_fwd(const void* x, const void* res, void* y, void* mask, int64_t M, int C,
                          const void* gamma, const void* beta, float* mean, float* invstd,
