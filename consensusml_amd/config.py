@@ -128,8 +128,30 @@ class OptimConfig:
                      unclipped aggregate. With ``worker_momentum`` the clipped quantity is the
                      aggregate of the momenta (about 1 / (1 - momentum) the gradient scale);
                      nothing is rescaled
+    name=lars        layer-wise adaptive rate scaling (You, Gitman, Ginsburg 2017) on the
+                     AGGREGATE, in the LARC form: the gradient of every adapted tensor is scaled
+                     by its trust ratio, then SGD-momentum runs unchanged. Per parameter tensor,
+                     over exactly its elements, with p the fp32 master and g the aggregate (the
+                     mean over workers or the rule's output): wn = ||p||, gn = ||g|| (fp64 sums);
+                     q = trust_coef * wn / (gn + weight_decay * wn + eps) when the tensor is
+                     adapted and wn > 0 and gn > 0, else q = 1; then per element g <- g +
+                     weight_decay * p, g <- q * g, and SGD's momentum / Nesterov / p <- p - lr * g.
+                     The step of an adapted tensor has length lr * trust_coef * wn whatever the
+                     aggregate's magnitude. A non-finite norm gives q = 0 for that tensor: it
+                     takes a ZERO gradient this step (counted in ``engine.lars_stats[t, 3]``), no
+                     state is poisoned. Like clip_norm it runs as three device stages (aggregate
+                     -> per-tensor norms -> update; sharded topology: ONE all-reduce of the fp64
+                     [T, 2] sums), so ``topology.early_update`` is off. ``engine.lars_stats``
+                     (fp64 [T, 4]) = [wn, gn, q, non-finite steps] per tensor. Not implemented
+                     together with ``clip_norm`` or ``worker_momentum``; one weight decay for all
+                     tensors
+    trust_coef       LARS trust coefficient (> 0)
+    lars_exclude_1d  LARS: tensors with fewer than 2 dimensions (biases, BatchNorm / LayerNorm
+                     affine) are not adapted (q = 1): they take the plain SGD step, weight decay
+                     included
+    eps              Adam's denominator term; LARS: the term added to the ratio's denominator
     """
-    name: str = "sgd"            # sgd | adam | adamw
+    name: str = "sgd"            # sgd | adam | adamw | lars
     lr: float = 0.1
     momentum: float = 0.9
     nesterov: bool = False
@@ -138,13 +160,23 @@ class OptimConfig:
     eps: float = 1e-8
     worker_momentum: bool = False
     clip_norm: float = 0.0
+    trust_coef: float = 0.001
+    lars_exclude_1d: bool = True
 
     def validate(self) -> None:
         c = self.clip_norm
         if isinstance(c, bool) or not isinstance(c, (int, float)) or not math.isfinite(c) or c < 0:
             raise ValueError(f"optim.clip_norm must be a finite number >= 0 (got {c!r})")
+        t = self.trust_coef
+        if isinstance(t, bool) or not isinstance(t, (int, float)) or not math.isfinite(t) or t <= 0:
+            raise ValueError(f"optim.trust_coef must be a finite number > 0 (got {t!r})")
+        if self.name == "lars" and c > 0:
+            raise ValueError("optim.name=lars with optim.clip_norm > 0 is not implemented")
         if not self.worker_momentum:
             return
+        if self.name == "lars":
+            raise ValueError("optim.worker_momentum is not implemented with optim.name=lars "
+                             "(it needs optim.name=sgd)")
         if self.name != "sgd":
             raise ValueError(f"optim.worker_momentum needs optim.name=sgd (got {self.name!r})")
         if self.momentum == 0:
@@ -160,7 +192,8 @@ class TopologyConfig:
 
     ``early_update`` (gossip, one worker per rank: each bucket's optimizer step runs during
     backward) is forced off while ``optim.clip_norm`` > 0: the update of the first bucket would
-    need the gradient norm over all of them. The engine logs the switch once.
+    need the gradient norm over all of them. The engine logs the switch once. The same holds for
+    ``optim.name=lars``, whose update waits for the per-tensor norms.
     """
     kind: str = "sharded"        # allreduce | allgather | sharded | gossip
     bucket_mb: float = 64.0      # bucket size in MB of gradient (bf16 on the wire)

@@ -94,8 +94,10 @@ def rule_combine(rule: str, n: int, f: int, trim: Optional[int] = None, *,
 
 @dataclass
 class OptArgs:
-    """Hyper-parameters of one fused optimizer step (SGD or Adam/AdamW)."""
-    kind: str = "sgd"            # none | sgd | adam (L2 weight decay) | adamw (decoupled)
+    """Hyper-parameters of one fused optimizer step (SGD or Adam/AdamW), or of the LARS step
+    (``lars_update``: SGD's fields; the trust coefficient and the ratio's eps go to ``lars_ratio``,
+    so this class keeps the fields the recorded engine traces list)."""
+    kind: str = "sgd"            # none | sgd | adam (L2 weight decay) | adamw (decoupled) | lars
     lr: float = 0.1
     momentum: float = 0.0
     weight_decay: float = 0.0
@@ -108,6 +110,8 @@ class OptArgs:
     gscale: float = 1.0
 
     def opt_id(self) -> int:
+        if self.kind == "lars":
+            raise ValueError("OptArgs(kind='lars') is the step of lars_update, not of agg_update")
         return {"none": 0, "sgd": 1, "adamw": 2, "adam": 3 if self.weight_decay else 2}[self.kind]
 
 
@@ -618,3 +622,150 @@ def clip_coef(norm2: torch.Tensor, max_norm: float, base: float, w_out: torch.Te
     st[0], st[1], st[3] = norm, coef, s.reshape(-1)[0]
     st[2] += bad
     return w_out
+
+
+# --------------------------------------------------------------------------- LARS
+LARS_STATS = ref.LARS_STATS   # fp64 per tensor: [wn, gn, q, steps with a non-finite norm]
+# Elements of one work item of the segmented norm pass. Measured over the project's two standard
+# sizes, as one tensor and cut like ResNet-50's tensor list, for C = 4096 .. 262144: 65536 is the
+# fastest or within the spread of the fastest in all four (profiles/lars/README.md)
+LARS_CHUNK = 65536
+
+
+class LarsPlan:
+    """Tables of one state vector for the LARS kernels (``lars_plan``). Tensor t (the caller's
+    order, ascending in the vector) holds elements [starts[t], starts[t] + numels[t]);
+    ``starts[T]`` is the vector length. ``items`` (int64 [I, 3] of (tensor, start, len)) cuts every
+    tensor into chunks of at most ``chunk`` elements, ``item_off`` (int64 [T + 1]) indexes them per
+    tensor. The device copies are made once per device."""
+
+    def __init__(self, starts: List[int], numels: List[int], chunk: int, items: torch.Tensor,
+                 item_off: torch.Tensor):
+        self.starts, self.numels, self.chunk = starts, numels, chunk
+        self.items, self.item_off = items, item_off
+        self.T = len(numels)
+        self.total = starts[-1]
+        self._dev = {}
+
+    def on(self, device) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+        """(items, item_off, starts, work) on ``device``; work: fp64 [2 I] partials."""
+        key = torch.device(device)
+        hit = self._dev.get(key)
+        if hit is None:
+            hit = (self.items.to(key), self.item_off.to(key),
+                   torch.tensor(self.starts, dtype=torch.int64, device=key),
+                   torch.empty(max(2 * self.items.shape[0], 1), dtype=torch.float64, device=key))
+            self._dev[key] = hit
+        return hit
+
+
+def lars_plan(starts, numels, chunk: int = 0, total: Optional[int] = None) -> LarsPlan:
+    """The work tables of the LARS kernels over a state vector whose tensor t occupies
+    [starts[t], starts[t] + numels[t]) (``numels[t]`` may be 0: a tensor with no element on this
+    rank). Starts ascend from 0, are multiples of 8 elements (so both rows load 16 B per lane and
+    a vector never straddles two tensors) and tensors do not overlap. ``chunk``: most elements of
+    a work item, a positive multiple of 8 (0: ``LARS_CHUNK``). ``total``: the vector length
+    (default: the end of the last tensor rounded up to 8)."""
+    starts = [int(s) for s in starts]
+    numels = [int(n) for n in numels]
+    chunk = int(chunk) or LARS_CHUNK
+    if len(starts) != len(numels) or not starts:
+        raise ValueError("lars_plan: starts and numels must be non-empty and of equal length")
+    if chunk <= 0 or chunk % 8:
+        raise ValueError(f"lars_plan: chunk must be a positive multiple of 8 (got {chunk})")
+    if starts[0] != 0:
+        raise ValueError(f"lars_plan: the first tensor must start at 0 (got {starts[0]})")
+    end = 0
+    for t, (s, n) in enumerate(zip(starts, numels)):
+        if s % 8:
+            raise ValueError(f"lars_plan: start {s} of tensor {t} is not a multiple of 8 elements")
+        if n < 0 or s < end:
+            raise ValueError(f"lars_plan: tensor {t} [{s}, +{n}) overlaps its predecessor or is "
+                             "negative")
+        end = max(end, s + n)
+    end8 = -(-end // 8) * 8
+    total = end8 if total is None else int(total)
+    if total < end:
+        raise ValueError(f"lars_plan: total {total} is shorter than the tensors ({end})")
+    if total % 8:
+        raise ValueError(f"lars_plan: total {total} is not a multiple of 8 elements")
+    items, item_off = [], [0]
+    for t, (s, n) in enumerate(zip(starts, numels)):
+        for a in range(0, n, chunk):
+            items.append((t, s + a, min(chunk, n - a)))
+        item_off.append(len(items))
+    it = torch.tensor(items, dtype=torch.int64).reshape(-1, 3)
+    return LarsPlan(starts + [total], numels, chunk, it, torch.tensor(item_off, dtype=torch.int64))
+
+
+def seg_sq_norm(master: torch.Tensor, g: torch.Tensor, scale: float, plan: LarsPlan,
+                out: Optional[torch.Tensor] = None, grid_cap: int = 0) -> torch.Tensor:
+    """out (fp64 [T, 2]) = per tensor (sum p^2, sum (float(x) * scale)^2) over exactly the tensor's
+    elements of the fp32 master and the co-indexed gradient row ``g`` (bf16 / fp32)
+    (``reference.seg_sq_norm``). GPU: one read-only pass, fp64 partials per work item summed in a
+    fixed order, no atomics: the same data gives the same bits."""
+    if out is None:
+        out = torch.zeros(plan.T, 2, dtype=torch.float64, device=master.device)
+    if master.is_cuda:
+        items, item_off, _, work = plan.on(master.device)
+        lib().seg_sq_norm(master, g, float(scale), items, item_off, plan.total, work, out,
+                          grid_cap)
+        return out
+    out.copy_(ref.seg_sq_norm(master, g, scale, plan.starts[:-1], plan.numels))
+    return out
+
+
+def lars_ratio(pairs: torch.Tensor, adapt: torch.Tensor, trust: float, weight_decay: float,
+               eps: float, q: torch.Tensor, stats: torch.Tensor,
+               reduced: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """q (fp32 [T]) = the trust ratios from ``pairs`` (fp64 [T, 2], ``seg_sq_norm``), or from
+    ``reduced`` when given (the pairs all-reduced over ranks); ``adapt`` (uint8 [T]): the tensors
+    LARS adapts. ``stats`` (fp64 [T, LARS_STATS]) = [wn, gn, q, += 1 when a norm is not finite
+    (then q = 0)] (``reference.lars_ratio``). Nothing is read back to the host on the GPU path."""
+    if not (trust > 0 and math.isfinite(trust)):
+        raise ValueError(f"lars_ratio: trust must be a finite number > 0 (got {trust})")
+    if pairs.is_cuda:
+        lib().lars_ratio(pairs, adapt, float(trust), float(weight_decay), float(eps), q, stats,
+                         reduced)
+        return q
+    qq, st, bad = ref.lars_ratio(reduced if reduced is not None else pairs, adapt, trust,
+                                 weight_decay, eps)
+    q.copy_(qq)
+    stats = stats.reshape(-1, LARS_STATS)
+    stats[:, :3] = st
+    stats[:, 3] += bad.double()
+    return q
+
+
+def lars_update(g: torch.Tensor, scale: float, plan: LarsPlan, q: torch.Tensor, opt: OptArgs,
+                master: torch.Tensor, s1: Optional[torch.Tensor] = None, segs=None,
+                grid_cap: int = 0) -> None:
+    """The LARS step in place over the state vector: ``reference.lars_update`` with the factors
+    ``q`` (``lars_ratio``) on the gradient row ``g`` times ``scale``, ``opt`` = OptArgs(kind=
+    "lars") for lr / momentum / weight_decay / nesterov / first. ``segs``: output segments
+    (param_out or None, state offset, length) -- the parameters rewritten from the master (bf16 /
+    fp32); None = no parameter output over the whole vector. GPU: 16 segments per launch."""
+    if opt.kind != "lars":
+        raise ValueError(f"lars_update takes OptArgs(kind='lars'), got {opt.kind!r}")
+    if segs is None:
+        segs = [(None, 0, plan.total)]
+    segs = [(p, int(o), int(n)) for p, o, n in segs]
+    if master.is_cuda:
+        _, _, starts, _ = plan.on(master.device)
+        lib().lars_update(g, float(scale), master, s1, q, starts, plan.starts,
+                          [p for p, _, _ in segs], [o for _, o, _ in segs],
+                          [n for _, _, n in segs], opt.lr, opt.momentum, opt.weight_decay,
+                          opt.nesterov, opt.first, grid_cap)
+        return
+    for _, o, n in segs:
+        if o % 8 or o < 0 or o + n > plan.total:
+            raise ValueError(f"lars_update: segment [{o}, +{n}) must start at a multiple of 8 "
+                             f"inside the state vector of {plan.total}")
+    p, b = ref.lars_update(master, g, s1, q, plan.starts, scale, opt.lr, opt.momentum,
+                           opt.weight_decay, opt.nesterov, opt.first)
+    for pout, o, n in segs:     # (the reference computes the whole vector; segments select)
+        master[o:o + n].copy_(p[o:o + n])
+        if opt.momentum:
+            s1[o:o + n].copy_(b[o:o + n])
+        if pout is not None:
+            pout[:n].copy_(p[o:o + n].to(pout.dtype))

@@ -504,5 +504,74 @@ def clip_coef(norm2: torch.Tensor, max_norm: float, base: float = 1.0):
     return w, norm, coef, int(not ok)
 
 
+# --------------------------------------------------------------------------- LARS
+
+LARS_STATS = 4   # per tensor: [wn, gn, q, count of steps with a non-finite norm] (fp64)
+
+
+def seg_sq_norm(master: torch.Tensor, g: torch.Tensor, scale: float, starts, numels
+                ) -> torch.Tensor:
+    """fp64 [T, 2]: per tensor t over exactly its elements [starts[t], starts[t] + numels[t]) of
+    the state vector, (sum p^2, sum (float(x) * scale)^2) with p the fp32 master and x the
+    co-indexed gradient row. The product is rounded to fp32 as ``sq_norm`` defines it, squares and
+    sums are fp64 (the definition of ``seg_sq_norm_partial``, csrc/kernels/lars.hip). Alignment
+    padding between tensors never enters a norm."""
+    sc = torch.tensor(scale, dtype=torch.float32)
+    p = master.detach().reshape(-1).cpu()
+    x = g.detach().reshape(-1).cpu()
+    out = torch.zeros(len(numels), 2, dtype=torch.float64)
+    for t, (s, n) in enumerate(zip(starts, numels)):
+        pw = p[s:s + n].double()
+        gv = (x[s:s + n].float() * sc).double()
+        out[t, 0] = (pw * pw).sum()
+        out[t, 1] = (gv * gv).sum()
+    return out
+
+
+def lars_ratio(pairs: torch.Tensor, adapt, trust: float, weight_decay: float, eps: float):
+    """(q fp32 [T], stats fp64 [T, 3] = (wn, gn, q), bad int64 [T]) of LARS from pairs[t] = (sw,
+    sg) = (sum p^2, sum g^2), all in fp64 (``lars_finalize``, csrc/kernels/lars.hip):
+
+      sw or sg not finite              q = 0 and bad = 1: the tensor takes a zero gradient
+      adapt[t], wn > 0 and gn > 0      q = fp32(trust * wn / (gn + weight_decay * wn + eps))
+      otherwise                        q = 1
+    with wn = sqrt(sw), gn = sqrt(sg) (a non-finite sum is reported as it is)."""
+    pr = pairs.detach().double().cpu().reshape(-1, 2)
+    T = pr.shape[0]
+    fin = torch.isfinite(pr) & (pr >= 0)
+    nrm = torch.where(fin, pr.clamp_min(0).sqrt(), pr)
+    wn, gn = nrm[:, 0], nrm[:, 1]
+    ok = fin.all(1)
+    ad = torch.as_tensor(adapt, dtype=torch.bool).reshape(T)
+    ratio = trust * wn / (gn + weight_decay * wn + eps)
+    q = torch.ones(T, dtype=torch.float64)
+    q = torch.where(ok & ad & (wn > 0) & (gn > 0), ratio, q)
+    q = torch.where(ok, q, torch.zeros_like(q)).float()
+    return q, torch.stack([wn, gn, q.double()], 1), (~ok).long()
+
+
+def lars_update(p: torch.Tensor, g: torch.Tensor, buf: Optional[torch.Tensor], q: torch.Tensor,
+                starts, scale: float, lr: float, momentum: float, weight_decay: float = 0.0,
+                nesterov: bool = False, first: bool = False
+                ) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """The LARS step over a whole state vector (returns new copies of master and buffer): per
+    element of tensor t, g = float(x) * scale; g += weight_decay * p; g = q[t] * g -- exactly 0
+    where q[t] == 0, so a NaN gradient poisons no state -- then ``sgd_update``'s momentum,
+    Nesterov and p - lr * g. ``starts``: T + 1 ascending starts, starts[T] = the vector length;
+    an element belongs to the last tensor whose start is not behind it, so padding takes the
+    preceding tensor's q (``lars_update``, csrc/kernels/lars.hip)."""
+    D = int(starts[-1])
+    spans = torch.as_tensor([starts[t + 1] - starts[t] for t in range(len(starts) - 1)])
+    spans[0] += starts[0]
+    qe = torch.repeat_interleave(q.detach().float().cpu(), spans)
+    p = p[:D].float()
+    gv = g[:D].float() * torch.tensor(scale, dtype=torch.float32)
+    if weight_decay:
+        gv = gv + weight_decay * p
+    gv = torch.where(qe == 0, torch.zeros_like(gv), qe * gv)
+    return sgd_update(p, gv, buf[:D] if buf is not None else None, lr, momentum, 0.0, nesterov,
+                      first)
+
+
 __all__ = [n for n in dir() if not n.startswith("_") and n not in ("math", "torch", "Optional",
                                                                      "Tuple", "annotations")]

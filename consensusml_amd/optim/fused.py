@@ -1,4 +1,4 @@
-"""Fused optimizers over flat buffers: ``FusedSGD``, ``FusedAdam``, ``FusedAdamW``.
+"""Fused optimizers over flat buffers: ``FusedSGD``, ``FusedAdam``, ``FusedAdamW``, ``FusedLARS``.
 
 Drop-in ``torch.optim.Optimizer`` subclasses for code that does not go through the consensus
 engine. At construction every parameter of a param group becomes a view into
@@ -283,7 +283,85 @@ class FusedAdam(FusedAdamW):
                          max_grad_norm=max_grad_norm)
 
 
+class FusedLARS(_FusedBase):
+    """LARS (You, Gitman, Ginsburg 2017) in the LARC form, as ``OptimConfig`` defines it: per
+    parameter tensor q = trust_coef * ||p|| / (||g|| + weight_decay * ||p|| + eps) (norms over
+    the fp32 master and the gradient times ``grad_scale``, fp64 sums on the device; q = 1 for a
+    tensor that is excluded or has a zero norm, q = 0 -- a zero gradient -- where a norm is not
+    finite), the gradient plus its weight-decay term is multiplied by q, and torch.optim.SGD's
+    momentum / Nesterov step runs on it. ``exclude_1d``: tensors with fewer than 2 dimensions
+    (biases, norm affine) take the plain SGD step. fp32 and bf16 parameters (the kernels read
+    fp32 / bf16 gradient rows; fp16 parameters raise TypeError). Three launches per flat buffer
+    (``csrc/kernels/lars.hip``): the segmented norms, the ratios, the update.
+
+    The state is ``momentum_buffer`` (+ ``master``), so a ``torch.optim.SGD`` state dict loads.
+    ``lars_stats``: per flat buffer an fp64 [T, 4] device tensor of [wn, gn, q, steps with a
+    non-finite norm], rows in that buffer's parameter order (``flat_buffers()[k].params``)."""
+    _kind = "lars"
+    _state_keys = ("momentum_buffer",)
+
+    def __init__(self, params, lr: float = 1e-3, momentum: float = 0.0,
+                 weight_decay: float = 0.0, nesterov: bool = False, trust_coef: float = 0.001,
+                 eps: float = 0.0, exclude_1d: bool = True, max_grad_norm: float = 0.0):
+        if nesterov and momentum <= 0:
+            raise ValueError("Nesterov momentum requires a momentum")
+        if not (isinstance(trust_coef, (int, float)) and 0 < trust_coef < float("inf")):
+            raise ValueError(f"trust_coef must be a finite number > 0 (got {trust_coef!r})")
+        if max_grad_norm:
+            raise ValueError("FusedLARS with max_grad_norm > 0 is not implemented")
+        super().__init__(params, dict(lr=lr, momentum=momentum, weight_decay=weight_decay,
+                                      nesterov=nesterov, trust_coef=trust_coef, eps=eps,
+                                      exclude_1d=exclude_1d))
+        self.lars_stats: List[torch.Tensor] = []
+        self._lars = []
+        for group, flats in zip(self.param_groups, self._flats):
+            for fl in flats:
+                if fl.grad.dtype == torch.float16:
+                    raise TypeError("FusedLARS takes fp32 / bf16 parameters")
+                dev, T = fl.grad.device, len(fl.params)
+                plan = K.lars_plan(fl.offsets, [p.numel() for p in fl.params], total=fl.total)
+                adapt = torch.tensor([not (group["exclude_1d"] and p.dim() < 2)
+                                      for p in fl.params], dtype=torch.uint8, device=dev)
+                bufs = (plan, adapt, torch.zeros(T, 2, dtype=torch.float64, device=dev),
+                        torch.ones(T, dtype=torch.float32, device=dev),
+                        torch.zeros(T, K.LARS_STATS, dtype=torch.float64, device=dev))
+                self._lars.append(bufs)
+                self.lars_stats.append(bufs[4])
+
+    def load_state_dict(self, state_dict) -> None:
+        super().load_state_dict(state_dict)
+        for group in self.param_groups:   # a torch.optim.SGD state dict carries no LARS keys
+            for k, v in self.defaults.items():
+                group.setdefault(k, v)
+
+    def _opt_args(self, group, step):
+        return OptArgs(kind="lars", lr=group["lr"], momentum=group["momentum"],
+                       weight_decay=group["weight_decay"], nesterov=group["nesterov"],
+                       first=step == 1)
+
+    @torch.no_grad()
+    def step(self, closure=None, grad_scale: float = 1.0):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        bufs = iter(self._lars)
+        for group, flats in zip(self.param_groups, self._flats):
+            group["step"] += 1
+            o = self._opt_args(group, group["step"])
+            for fl in flats:
+                fl.sync_foreign_grads()
+                plan, adapt, pairs, q, stats = next(bufs)
+                s1 = fl.states[0] if o.momentum else None
+                K.seg_sq_norm(fl.master, fl.grad, grad_scale, plan, out=pairs)
+                K.lars_ratio(pairs, adapt, group["trust_coef"], o.weight_decay, group["eps"], q,
+                             stats)
+                K.lars_update(fl.grad, grad_scale, plan, q, o, fl.master, s1,
+                              segs=[(fl.param if fl.lowp else None, 0, fl.total)])
+        return loss
+
+
 def build_optimizer(name: str, params, **kw) -> torch.optim.Optimizer:
-    """``OptimConfig.name`` -> fused optimizer (sgd | adam | adamw)."""
-    cls = {"sgd": FusedSGD, "adam": FusedAdam, "adamw": FusedAdamW}[name]
+    """``OptimConfig.name`` -> fused optimizer (sgd | adam | adamw | lars)."""
+    cls = {"sgd": FusedSGD, "adam": FusedAdam, "adamw": FusedAdamW, "lars": FusedLARS}[name]
     return cls(params, **kw)

@@ -40,6 +40,13 @@ is skipped: the norm is taken of that row times the step's gradient scale and th
 it with w_clip = scale * coefficient. The coefficient never reaches the host. With
 ``optim.worker_momentum`` the rows are momenta, so the clipped quantity is the aggregate of the
 momenta; centered clipping keeps the UNCLIPPED aggregate as its v0.
+
+LARS (optim.name = lars, defined in ``OptimConfig``) is the same three stages with a per-tensor
+norm in place of the global one: stage 1 as above (or skipped on the direct paths), then
+ops.kernels.seg_sq_norm over the master and the aggregate (fp64 [T, 2] sums; sharded, N > 1: ONE
+all-reduce of that vector), ops.kernels.lars_ratio (the DEVICE factors q and ``lars_stats``) and
+ops.kernels.lars_update, the SGD-momentum update that multiplies tensor t's gradient by q[t]. The
+sharded topology's parameter all-gathers follow the update.
 """
 from __future__ import annotations
 
@@ -169,7 +176,8 @@ class ConsensusEngine:
                 if idx.numel():
                     self._pad_cols[b.index] = idx.to(dev)
         self.s1 = (torch.zeros_like(self.master)
-                   if (oname != "sgd" or cfg.optim.momentum) and not self.worker_momentum else None)
+                   if (oname not in ("sgd", "lars") or cfg.optim.momentum)
+                   and not self.worker_momentum else None)
         self.s2 = torch.zeros_like(self.master) if oname in ("adam", "adamw") else None
         self.step_count = 0
 
@@ -208,8 +216,10 @@ class ConsensusEngine:
         self.clip_norm = float(cfg.optim.clip_norm)
         self.clip = self.clip_norm > 0
         self._clip_direct = self.topo == "allreduce" or (self.topo == "gossip" and self.V == 1)
+        # optim.name=lars: the same three stages with per-tensor norms (module docstring)
+        self.lars = oname == "lars"
         self.gout = None
-        if self.rule == "centered_clip" or (self.clip and not self._clip_direct):
+        if self.rule == "centered_clip" or ((self.clip or self.lars) and not self._clip_direct):
             self.gout = torch.zeros(self.state_len, dtype=torch.float32, device=dev)
         # [norm of the aggregate, clipping coefficient, steps whose norm was not finite (their
         # coefficient is 0: a zero gradient), squared norm] of the last step, fp64 on the device
@@ -221,6 +231,8 @@ class ConsensusEngine:
                            if self.clip and self.topo == "sharded" and self.group_active
                            and self.N > 1 else None)
         self._clip_work: Optional[torch.Tensor] = None
+        if self.lars:
+            self._setup_lars()
 
         # -------------------------------------------------- gradient capture + overlap hooks
         # Copy-on-ready: autograd produces fresh .grad tensors; when every parameter of a bucket
@@ -256,11 +268,16 @@ class ConsensusEngine:
         # produced that gradient), so updating it early is exact.
         self.early_update = (self.topo == "gossip" and self.V == 1 and dev.type == "cuda"
                              and cfg.fault.kind not in COLLUSION
-                             and cfg.topology.early_update and not self.clip)
+                             and cfg.topology.early_update and not self.clip
+                             and not self.lars)
         if self.clip and self.topo == "gossip" and self.V == 1 and cfg.topology.early_update:
             # the first bucket's update needs the norm over all of them
             _log.info("optim.clip_norm > 0: topology.early_update is off (the update waits for "
                       "the global gradient norm)")
+        if self.lars and self.topo == "gossip" and self.V == 1 and cfg.topology.early_update:
+            # a tensor's update needs its norms, and the stages run over the whole vector
+            _log.info("optim.name=lars: topology.early_update is off (the update waits for the "
+                      "per-tensor norms)")
         self._updated: set = set()
         self._opt_stream = torch.cuda.Stream(device=dev) if self.early_update else None
         # Sharded topology: the bf16 parameter all-gather of each bucket is not waited for at the
@@ -701,10 +718,10 @@ class ConsensusEngine:
     # ================================================================ optimizer args
     def _opt_args(self, gscale: float = 1.0) -> K.OptArgs:
         o = self.cfg.optim
-        kind = o.name if o.name in ("sgd", "adam", "adamw") else "adamw"
+        kind = o.name if o.name in ("sgd", "adam", "adamw", "lars") else "adamw"
         wd = o.weight_decay
         # 'adam' = torch.optim.Adam (L2 term in the gradient), 'adamw' = decoupled decay
-        mom = o.momentum if kind == "sgd" and not self.worker_momentum else 0.0
+        mom = o.momentum if kind in ("sgd", "lars") and not self.worker_momentum else 0.0
         return K.OptArgs(kind=kind, lr=o.lr, momentum=mom,
                          weight_decay=wd, nesterov=o.nesterov, first=self.step_count == 0,
                          beta1=o.betas[0], beta2=o.betas[1], eps=o.eps,
@@ -863,6 +880,56 @@ class ConsensusEngine:
         K.agg_update(row, combine="weighted", w=self.w_clip, n=1, D=fl.total, opt=self._opt_args(),
                      master=m, s1=s1, s2=s2, param_out=fl.flat_param)
 
+    # ================================================================ LARS
+    def _setup_lars(self) -> None:
+        """The tables of the vector the update runs over (rebuilt from the layout, so a
+        checkpoint carries nothing of them) and the per-tensor device buffers."""
+        fl, o, dev = self.flat, self.cfg.optim, self.device
+        shard = self.topo == "sharded" and self.group_active
+        ranges = fl.tensor_ranges(self.rank if shard else None)   # ascending in the vector
+        self._lars_plan = K.lars_plan([s for _, s, _ in ranges], [n for _, _, n in ranges],
+                                      total=self.state_len)
+        T = len(ranges)
+        order = torch.tensor([i for i, _, _ in ranges])
+        # row of the tables that holds parameter i (lars_stats is in flat.params order)
+        self._lars_row = torch.empty(T, dtype=torch.int64).scatter_(
+            0, order, torch.arange(T)).to(dev)
+        self._lars_adapt = torch.tensor(
+            [not (o.lars_exclude_1d and fl.params[i].dim() < 2) for i, _, _ in ranges],
+            dtype=torch.uint8, device=dev)
+        self._lars_pairs = torch.zeros(T, 2, dtype=torch.float64, device=dev)
+        self._lars_red = (torch.zeros(T, 2, dtype=torch.float64, device=dev)
+                          if shard and self.N > 1 else None)
+        self._lars_q = torch.ones(T, dtype=torch.float32, device=dev)
+        self._lars_stats = torch.zeros(T, K.LARS_STATS, dtype=torch.float64, device=dev)
+
+    @property
+    def lars_stats(self) -> Optional[torch.Tensor]:
+        """fp64 [T, 4] on the device, rows in ``flat.params`` order: [wn, gn, q, steps whose norm
+        was not finite] of the last step (None unless optim.name=lars)."""
+        return self._lars_stats[self._lars_row] if self.lars else None
+
+    def _lars_row_update(self, row: torch.Tensor, scale: float, segs) -> None:
+        """Stages 2 + 3 of LARS over ONE row co-indexed with the state vector (a gradient row
+        times ``scale``, or the materialised fp32 aggregate with scale 1): the per-tensor norms --
+        sharded, N > 1: ONE all-reduce of the fp64 [T, 2] sums, issued by every rank at this
+        point of the step, so every rank derives identical ratios -- then the update with the
+        device factors q. ``segs``: (parameters, state offset, length) the update rewrites."""
+        o = self.cfg.optim
+        K.seg_sq_norm(self.master, row, scale, self._lars_plan, out=self._lars_pairs)
+        red = self._lars_red
+        if red is not None:
+            red.copy_(self._lars_pairs)
+            dist.all_reduce(red)
+        K.lars_ratio(self._lars_pairs, self._lars_adapt, o.trust_coef, o.weight_decay, o.eps,
+                     self._lars_q, self._lars_stats, reduced=red)
+        K.lars_update(row, scale, self._lars_plan, self._lars_q, self._opt_args(), self.master,
+                      self.s1, segs=segs)
+
+    def _lars_full_update(self, row: torch.Tensor, scale: float) -> None:
+        fl = self.flat
+        self._lars_row_update(row, scale, [(fl.flat_param, 0, fl.total)])
+
     # ================================================================ topologies
     def _step_allreduce(self) -> None:
         fl = self.flat
@@ -872,6 +939,9 @@ class ConsensusEngine:
             fl.flat_grad[0].copy_(fl.flat_grad.float().sum(0).to(fl.dtype))
         if self.clip:       # direct path: every rank holds the same summed row, no collective
             self._clipped_row_update(fl.flat_grad[0], 1.0 / self.n)
+            return
+        if self.lars:
+            self._lars_full_update(fl.flat_grad[0], 1.0 / self.n)
             return
         opt = self._opt_args(gscale=1.0 / self.n)
         m, s1, s2 = self._state(0, fl.total)
@@ -911,7 +981,8 @@ class ConsensusEngine:
         if self.record_stats:
             self._record_stats(cols)
         opt = self._opt_args()
-        rule_opt = opt if not self.clip else K.OptArgs(kind="none")    # clipping: stage 1 only
+        staged = self.clip or self.lars     # clipping / LARS: the rule kernels are stage 1 only
+        rule_opt = opt if not staged else K.OptArgs(kind="none")
         # prefetch: earliest layers (highest bucket index) first, the next forward needs them first
         order = list(reversed(cols)) if self.param_prefetch else cols
         segs = [(b, X, length) + self._place(b) for b, X, length in order]
@@ -921,17 +992,17 @@ class ConsensusEngine:
                  and self.device.type == "cuda")
         if fused:
             self._aggregate_update_multi([s[1:] for s in segs], rule_opt,
-                                         gout=self.gout if self.clip else None)
+                                         gout=self.gout if staged else None)
         works = []
         for b, X, length, off, pout in segs:
             if not fused:
                 gout = self.gout[off:off + length] if self.gout is not None else None
                 # (the sharded stage 1 names no parameters; allgather's does, unused)
-                self._aggregate_update(X, length, off, None if sharded and self.clip else pout,
+                self._aggregate_update(X, length, off, None if sharded and staged else pout,
                                        rule_opt, gout)
                 if self.rule == "centered_clip":    # v0 <- the new, UNCLIPPED aggregate
                     (X[self.n, :length] if sharded else X[self.n]).copy_(gout.to(X.dtype))
-            if not self.clip:       # the parameters follow their update at once
+            if not staged:       # the parameters follow their update at once
                 self._gather_params(b, pout, works)
         if self.clip and sharded:
             # stage 2 over this rank's shards (N > 1: + one all-reduce of the fp64 scalar), then
@@ -945,6 +1016,14 @@ class ConsensusEngine:
                 self._gather_params(b, pout, works)
         elif self.clip:     # every rank holds the full aggregate: no collective
             self._clipped_row_update(self.gout, 1.0)
+        elif self.lars and sharded:
+            # stages 2 + 3 over this rank's shards; the parameter all-gathers follow the update
+            self._lars_row_update(self.gout, 1.0,
+                                  [(pout, off, length) for _, _, length, off, pout in segs])
+            for b, _, _, _, pout in segs:
+                self._gather_params(b, pout, works)
+        elif self.lars:     # every rank holds the full aggregate: no collective
+            self._lars_full_update(self.gout, 1.0)
         for w in works:
             w.wait()
 
@@ -1013,6 +1092,13 @@ class ConsensusEngine:
             K.agg_update(fl.flat_grad, combine="weighted", n=self.V,
                          opt=K.OptArgs(kind="none", gscale=1.0 / self.V), gout=self.gout)
             self._clipped_row_update(self.gout, 1.0)
+        elif self.lars and self.V == 1:
+            # every rank adapts its own local gradient; direct path: the row is the gradient
+            self._lars_full_update(fl.flat_grad[0], 1.0)
+        elif self.lars:
+            K.agg_update(fl.flat_grad, combine="weighted", n=self.V,
+                         opt=K.OptArgs(kind="none", gscale=1.0 / self.V), gout=self.gout)
+            self._lars_full_update(self.gout, 1.0)
         elif not self.early_update:
             opt = self._opt_args(gscale=1.0 / self.V)
             m, s1, s2 = self._state(0, fl.total)

@@ -14,7 +14,7 @@ a multiple of ``world * ALIGN`` so that its per-rank shard (``shard = len / worl
 from __future__ import annotations
 
 from dataclasses import dataclass
-from typing import Dict, List, Tuple
+from typing import Dict, List, Optional, Tuple
 
 import torch
 
@@ -167,6 +167,26 @@ class FlatModel:
     def gather_shard_vector(self, flat: torch.Tensor, rank: int) -> torch.Tensor:
         """Concatenate this rank's shard of every bucket (layout of the sharded optimizer state)."""
         return torch.cat([self.my_shard(flat, b, rank) for b in self.buckets])
+
+    def tensor_ranges(self, rank: Optional[int] = None) -> List[Tuple[int, int, int]]:
+        """(param index, start, len) of every parameter tensor, ascending in the vector an update
+        runs over: the whole flat vector (``rank`` None), or rank ``rank``'s shard vector of the
+        sharded topology (``gather_shard_vector``). Buckets hold whole tensors, so a tensor meets
+        a rank's shard of its bucket in at most one contiguous range; where they do not meet,
+        len is 0 and start is where the tensor would border the shard. Starts are multiples of 8
+        (tensor offsets are, shard boundaries are multiples of ALIGN)."""
+        out = []
+        for i in sorted(self.param_offset, key=lambda k: (self.param_offset[k], -k)):
+            o, n = self.param_offset[i], self.params[i].numel()
+            if rank is None:
+                out.append((i, o, n))
+                continue
+            b = self.buckets[self.bucket_of[i]]
+            lo = b.offset + rank * b.shard
+            a = min(max(o, lo), lo + b.shard)
+            e = min(max(o + n, lo), lo + b.shard)
+            out.append((i, b.shard_offset + a - lo, e - a))
+        return out
 
     def param_names(self) -> List[str]:
         names = {id(p): n for n, p in self.model.named_parameters()}

@@ -2164,6 +2164,160 @@ void clip_coef(const Tensor& norm2, double max_norm, double base, Tensor& w_out,
                                           cur_stream()));
 }
 
+// ---------------------------------------------------------------- LARS
+// a contiguous device table of `st` with at least min_numel elements on dev's device
+void check_table(const Tensor& t, at::ScalarType st, int64_t min_numel, const Tensor& dev,
+                 const char* name) {
+  check_dev(t, name);
+  TORCH_CHECK(t.device() == dev.device() && t.scalar_type() == st && t.is_contiguous() &&
+                  t.numel() >= min_numel,
+              "lars: ", name, " must be a contiguous ", st, " tensor of at least ", min_numel,
+              " elements on the state's device");
+}
+
+// the state vector's rows: fp32 master and the co-indexed gradient row (bf16 / fp32), both
+// contiguous, 16-B aligned and at least vec_len long
+int check_lars_rows(const Tensor& master, const Tensor& g, int64_t vec_len) {
+  check_dev(master, "master");
+  check_dev(g, "g");
+  TORCH_CHECK(vec_len >= 0, "lars: negative vector length");
+  TORCH_CHECK(master.scalar_type() == at::kFloat && master.is_contiguous() &&
+                  master.numel() >= vec_len,
+              "lars: master must be a contiguous fp32 tensor of at least ", vec_len, " elements");
+  TORCH_CHECK(g.device() == master.device() && g.is_contiguous() && g.numel() >= vec_len,
+              "lars: g must be a contiguous tensor of at least ", vec_len,
+              " elements on master's device");
+  TORCH_CHECK(((reinterpret_cast<uintptr_t>(master.data_ptr()) |
+                reinterpret_cast<uintptr_t>(g.data_ptr())) & 15) == 0,
+              "lars: master and g must be 16-B aligned");
+  return dtype_of(g);
+}
+
+// pairs[t] (fp64 [T, 2]) = (sum p^2, sum (fp32(g * scale))^2) over tensor t's elements. items:
+// device int64 [I, 3] of (tensor, start, len); item_off: device int64 [T + 1], tensor t's items
+// are [item_off[t], item_off[t + 1]); work: fp64, at least 2 I elements.
+void seg_sq_norm(const Tensor& master, const Tensor& g, double scale, const Tensor& items,
+                 const Tensor& item_off, int64_t vec_len, Tensor& work, Tensor& pairs,
+                 int64_t grid_cap) {
+  const int dt = check_lars_rows(master, g, vec_len);
+  TORCH_CHECK(grid_cap >= 0 && grid_cap <= (1 << 20), "seg_sq_norm: grid_cap out of range");
+  TORCH_CHECK(items.dim() == 2 && items.size(1) == 3, "seg_sq_norm: items must be [I, 3]");
+  const int64_t I = items.size(0);
+  const int64_t T = item_off.numel() - 1;
+  TORCH_CHECK(T >= 0 && T <= INT_MAX, "seg_sq_norm: item_off must hold T + 1 entries");
+  check_table(items, at::kLong, 3 * I, master, "items");
+  check_table(item_off, at::kLong, T + 1, master, "item_off");
+  check_table(work, at::kDouble, 2 * I, master, "work");
+  check_table(pairs, at::kDouble, 2 * T, master, "pairs");
+  const c10::DeviceGuard guard(master.device());
+  CML_CHECK_HIP(cml::launch_seg_sq_norm_partial(
+      dt, master.data_ptr<float>(), g.data_ptr(), static_cast<float>(scale),
+      items.data_ptr<int64_t>(), I, vec_len, work.data_ptr<double>(), static_cast<int>(grid_cap),
+      cur_stream()));
+  CML_CHECK_HIP(cml::launch_lars_finalize(work.data_ptr<double>(), item_off.data_ptr<int64_t>(), I,
+                                          static_cast<int>(T), pairs.data_ptr<double>(), nullptr,
+                                          nullptr, 0.0, 0.0, 0.0, nullptr, nullptr, cur_stream()));
+}
+
+// q[t] (fp32) and stats[t] (fp64 [4]: wn, gn, q, non-finite count) from pairs[t] = (sum p^2, sum
+// g^2), or from reduced[t] when given (the pairs all-reduced over ranks); adapt: uint8 [T]
+void lars_ratio(const Tensor& pairs, const Tensor& adapt, double trust, double wd, double eps,
+                Tensor& q, Tensor& stats, const optional<Tensor>& reduced) {
+  check_dev(pairs, "pairs");
+  const int64_t T = adapt.numel();
+  TORCH_CHECK(T <= INT_MAX, "lars_ratio: too many tensors");
+  check_table(pairs, at::kDouble, 2 * T, pairs, "pairs");
+  check_table(adapt, at::kByte, T, pairs, "adapt");
+  check_table(q, at::kFloat, T, pairs, "q");
+  check_table(stats, at::kDouble, cml::kLarsStats * T, pairs, "stats");
+  const double* red = opt_ptr<const double>(reduced, at::kDouble, "reduced", 2 * T);
+  if (red) TORCH_CHECK(reduced->device() == pairs.device(), "lars_ratio: reduced on pairs' device");
+  TORCH_CHECK(trust > 0.0 && wd >= 0.0 && eps >= 0.0,
+              "lars_ratio: trust must be positive, weight decay and eps not negative");
+  const c10::DeviceGuard guard(pairs.device());
+  CML_CHECK_HIP(cml::launch_lars_finalize(nullptr, nullptr, 0, static_cast<int>(T),
+                                          const_cast<double*>(pairs.data_ptr<double>()), red,
+                                          adapt.data_ptr<uint8_t>(), trust, wd, eps,
+                                          q.data_ptr<float>(), stats.data_ptr<double>(),
+                                          cur_stream()));
+}
+
+// The LARS update over output segments (param_out or None, state offset, length), at most 16 per
+// launch. starts_host: the T + 1 values of the device table `starts`, checked here: ascending from
+// 0, all multiples of 8 (a 16-B vector never straddles two tensors), starts[T] = the vector length.
+void lars_update(const Tensor& g, double scale, Tensor& master, const optional<Tensor>& s1,
+                 const Tensor& q, const Tensor& starts, const std::vector<int64_t>& starts_host,
+                 const std::vector<optional<Tensor>>& pouts, const std::vector<int64_t>& offs,
+                 const std::vector<int64_t>& lens, double lr, double momentum, double weight_decay,
+                 bool nesterov, bool first, int64_t grid_cap) {
+  TORCH_CHECK(starts_host.size() >= 2, "lars_update: starts must hold T + 1 >= 2 entries");
+  const int64_t T = static_cast<int64_t>(starts_host.size()) - 1;
+  TORCH_CHECK(T <= INT_MAX, "lars_update: too many tensors");
+  TORCH_CHECK(starts_host[0] == 0, "lars_update: the first tensor must start at 0");
+  for (int64_t t = 0; t <= T; ++t) {
+    TORCH_CHECK(starts_host[t] % 8 == 0, "lars_update: tensor start ", starts_host[t],
+                " is not a multiple of 8 elements");
+    TORCH_CHECK(t == 0 || starts_host[t] >= starts_host[t - 1],
+                "lars_update: tensor starts must ascend");
+  }
+  const int64_t vec_len = starts_host[T];
+  const int dt = check_lars_rows(master, g, vec_len);
+  TORCH_CHECK(grid_cap >= 0 && grid_cap <= (1 << 20), "lars_update: grid_cap out of range");
+  check_table(q, at::kFloat, T, master, "q");
+  check_table(starts, at::kLong, T + 1, master, "starts");
+  float* s1p = opt_ptr<float>(s1, at::kFloat, "s1", vec_len);
+  TORCH_CHECK(momentum == 0.0 || s1p != nullptr, "lars_update: momentum needs s1");
+  if (s1p) TORCH_CHECK(s1->device() == master.device() &&
+                           (reinterpret_cast<uintptr_t>(s1p) & 15) == 0,
+                       "lars_update: s1 on master's device, 16-B aligned");
+  const size_t ns = pouts.size();
+  TORCH_CHECK(ns >= 1 && offs.size() == ns && lens.size() == ns,
+              "lars_update: matching pouts / offs / lens");
+  const bool has_out = pouts[0].has_value() && pouts[0]->defined();
+  bool pf32 = false;
+  std::vector<cml::LarsSeg> segs(ns);
+  for (size_t i = 0; i < ns; ++i) {
+    TORCH_CHECK(offs[i] >= 0 && lens[i] >= 0 && offs[i] % 8 == 0 && offs[i] <= vec_len &&
+                    lens[i] <= vec_len - offs[i],
+                "lars_update: segment ", i, " [", offs[i], ", +", lens[i],
+                ") must start at a multiple of 8 inside the state vector of ", vec_len);
+    const bool has = pouts[i].has_value() && pouts[i]->defined();
+    TORCH_CHECK(has == has_out, "lars_update: every segment or none has a param_out");
+    void* p = nullptr;
+    if (has) {
+      const Tensor& P = *pouts[i];
+      check_dev(P, "param_out");
+      const bool f32 = P.scalar_type() == at::kFloat;
+      TORCH_CHECK(f32 || P.scalar_type() == at::kBFloat16, "lars_update: param_out bf16 or fp32");
+      TORCH_CHECK(i == 0 || f32 == pf32, "lars_update: param_outs of one dtype");
+      pf32 = f32;
+      TORCH_CHECK(P.device() == master.device() && P.is_contiguous() && P.numel() >= lens[i],
+                  "lars_update: param_out ", i, " must be contiguous with at least ", lens[i],
+                  " elements on master's device");
+      p = P.data_ptr();
+      TORCH_CHECK((reinterpret_cast<uintptr_t>(p) & 15) == 0,
+                  "lars_update: param_out must be 16-B aligned");
+    }
+    segs[i] = cml::LarsSeg{p, offs[i], lens[i]};
+  }
+  cml::LarsUpd u{};
+  u.lr = static_cast<float>(lr);
+  u.momentum = static_cast<float>(momentum);
+  u.weight_decay = static_cast<float>(weight_decay);
+  u.nesterov = nesterov;
+  u.first = first;
+  u.param_f32 = pf32;
+  const c10::DeviceGuard guard(master.device());
+  for (size_t a = 0; a < ns; a += cml::kLarsMaxSegs) {
+    const int n = static_cast<int>(std::min(ns, a + cml::kLarsMaxSegs) - a);
+    CML_CHECK_HIP(cml::launch_lars_update(dt, g.data_ptr(), static_cast<float>(scale),
+                                          master.data_ptr<float>(), s1p, q.data_ptr<float>(),
+                                          starts.data_ptr<int64_t>(), static_cast<int>(T),
+                                          segs.data() + a, n, u, static_cast<int>(grid_cap),
+                                          cur_stream()));
+  }
+}
+
 // ---------------------------------------------------------------- transformer ops
 void check_bf16c(const Tensor& t, const char* name) {
   check_dev(t, name);
@@ -3000,6 +3154,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("clip_coef", &clip_coef, "global-norm clipping coefficient as a device weight + stats",
         py::arg("norm2"), py::arg("max_norm"), py::arg("base"), py::arg("w_out"), py::arg("stats"),
         py::arg("reduced") = py::none());
+  m.def("seg_sq_norm", &seg_sq_norm,
+        "per-tensor (sum p^2, sum g^2) of a state vector, in fp64 over a table of work items",
+        py::arg("master"), py::arg("g"), py::arg("scale"), py::arg("items"), py::arg("item_off"),
+        py::arg("vec_len"), py::arg("work"), py::arg("pairs"), py::arg("grid_cap") = 0);
+  m.def("lars_ratio", &lars_ratio, "LARS trust ratios as device factors + per-tensor stats",
+        py::arg("pairs"), py::arg("adapt"), py::arg("trust"), py::arg("wd"), py::arg("eps"),
+        py::arg("q"), py::arg("stats"), py::arg("reduced") = py::none());
+  m.def("lars_update", &lars_update, "SGD-momentum update with a per-tensor gradient factor",
+        py::arg("g"), py::arg("scale"), py::arg("master"), py::arg("s1"), py::arg("q"),
+        py::arg("starts"), py::arg("starts_host"), py::arg("pouts"), py::arg("offs"),
+        py::arg("lens"), py::arg("lr"), py::arg("momentum"), py::arg("weight_decay"),
+        py::arg("nesterov"), py::arg("first"), py::arg("grid_cap") = 0);
   m.def("bn_fwd", &bn_fwd, "fused NHWC BatchNorm(+res)(+ReLU) forward");
   m.def("bn_bwd", &bn_bwd, "fused NHWC BatchNorm(+res)(+ReLU) backward");
   m.def("bn_fwd2", &bn_fwd2, "relu(BN(x1) + BN(x2)) forward (downsample-block tail)");

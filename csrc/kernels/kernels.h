@@ -288,6 +288,53 @@ hipError_t launch_clip_finalize(const double* partials, int npart, double* norm2
                                 const double* reduced, double max_norm, float base, float* w_out,
                                 double* stats, hipStream_t stream);
 
+// LARS: layer-wise trust ratios on the aggregate (lars.hip, optim.name=lars). One state vector of
+// vec_len elements holds every parameter tensor at a start that is a multiple of 8 elements: the
+// fp32 master, the momentum buffer and the co-indexed gradient row g (bf16 / fp32, times scale).
+// seg_sq_norm_partial: items = device int64 [nitems, 3] of (tensor, start, len), a tensor's
+// range [start, start + numel) cut into chunks (starts multiples of 8; the last item of a tensor
+// ends at its exact numel). Item i writes work[2 i] = sum p^2 and work[2 i + 1] = sum (fp32(g *
+// scale))^2 over its elements, accumulated in fp64 in a fixed order: every slot written on every
+// launch, no atomics. An item outside [0, vec_len) reads nothing and writes zeros. grid_cap: most
+// workgroups (they stride over the items); <= 0 = the default.
+int seg_sq_norm_grid(int64_t nitems, int grid_cap);
+hipError_t launch_seg_sq_norm_partial(int dtype, const float* master, const void* g, float scale,
+                                      const int64_t* items, int64_t nitems, int64_t vec_len,
+                                      double* work, int grid_cap, hipStream_t stream);
+// lars_finalize (one wave per tensor). work != nullptr: pairs[t] = the sum, in item order, of the
+// pairs of items [item_off[t], item_off[t + 1]). q != nullptr: with (sw, sg) = reduced ? reduced[t]
+// : pairs[t] (reduced: the pairs all-reduced over ranks), wn = sqrt(sw), gn = sqrt(sg):
+//   sw or sg not finite             q[t] = 0 (that tensor takes a zero gradient) and stats[t][3] += 1
+//   adapt[t] and wn > 0 and gn > 0  q[t] = float(trust * wn / (gn + wd * wn + eps)), in fp64
+//   else                            q[t] = 1
+// stats[t] = (wn, gn, q[t], count of non-finite steps), kLarsStats fp64 per tensor.
+constexpr int kLarsStats = 4;
+hipError_t launch_lars_finalize(const double* work, const int64_t* item_off, int64_t nitems, int T,
+                                double* pairs, const double* reduced, const uint8_t* adapt,
+                                double trust, double wd, double eps, float* q, double* stats,
+                                hipStream_t stream);
+// lars_update: per element of tensor t, g = fp32(g * scale); g = fma(wd, p, g) when wd != 0; g =
+// q[t] * g (exactly 0 where q[t] == 0); then the momentum buffer, Nesterov and p = fma(-lr, g, p)
+// of OPT_SGD (agg_update.hip), `first` included. starts: device int64 [T + 1], ascending, all
+// multiples of 8, starts[T] = vec_len; an element belongs to the last tensor whose start is not
+// behind it (padding takes the preceding tensor's q). Up to kLarsMaxSegs output segments in one
+// launch: state elements [off, off + len) -> param_out[0, len) (bf16, fp32 when param_f32, or
+// nullptr for all of them); off a multiple of 8. grid_cap: most workgroups over all segments.
+constexpr int kLarsMaxSegs = 16;
+struct LarsSeg {
+  void* param_out;
+  int64_t off;
+  int64_t len;
+};
+struct LarsUpd {
+  float lr, momentum, weight_decay;
+  int nesterov, first;
+  int param_f32;
+};
+hipError_t launch_lars_update(int dtype, const void* g, float scale, float* master, float* s1,
+                              const float* q, const int64_t* starts, int T, const LarsSeg* segs,
+                              int nseg, const LarsUpd& u, int grid_cap, hipStream_t stream);
+
 // ---- transformer ops (transformer.hip); bf16 activations, fp32 statistics.
 // Cross-entropy over contiguous bf16 logits [R, V] (16-B aligned base): forward writes the
 // per-row logsumexp and loss (0 for ignored rows); backward writes
