@@ -3389,6 +3389,84 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     d["bn_grid_cap"] = cap;
     return d;
   }, "the read-once BN switches (CML_BN_NT, CML_BN_GRID_CAP) as this process read them");
+  m.def("wgrad_settings", [] {
+    int dma, xf, ns128, wide;
+    cml::wgrad_settings(&dma, &xf, &ns128, &wide);
+    py::dict d;
+    d["wgrad_dma"] = dma;
+    d["wgrad_dma_xf"] = xf;
+    d["wgrad_dma_ns128"] = ns128;
+    d["fold_wide_min"] = wide;
+    d["wgrad3x3_direct"] = cml::wgrad3x3_direct_setting();
+    return d;
+  }, "the read-once weight-gradient switches (CML_WGRAD_DMA, CML_WGRAD_DMA_XF, "
+     "CML_WGRAD_DMA_NS128, CML_FOLD_WIDE_MIN, CML_WGRAD3X3_DIRECT) as this process read them");
+  m.def("wgrad_route", [](const std::string& kind, const py::args& a) {
+    const char* folds[] = {"none", "narrow", "wide"};
+    auto arg = [&](size_t i) { return a[i].cast<int64_t>(); };
+    auto small = [&](size_t i, const char* what) {
+      const int64_t v = arg(i);
+      TORCH_CHECK(v >= 0 && v < (1ll << 30), "wgrad_route: ", what, " out of range");
+      return static_cast<int>(v);
+    };
+    py::dict d;
+    if (kind == "1x1") {
+      TORCH_CHECK(a.size() >= 6 && a.size() <= 8,
+                  "wgrad_route('1x1', P, Co, Ci, pro, dmode, colsum[, same[, bf16]])");
+      cml::Wgrad1x1Route r;
+      cml::wgrad1x1_route(arg(0), small(1, "Co"), small(2, "Ci"), a[3].cast<bool>(),
+                          small(4, "dmode"), a[5].cast<bool>(),
+                          a.size() > 6 && a[6].cast<bool>(), a.size() > 7 && a[7].cast<bool>(), &r);
+      const char* paths[] = {"gram", "dma", "staged"};
+      d["ok"] = r.ok;
+      if (!r.ok) return d;
+      d["path"] = std::string(paths[r.path]);
+      d["splits"] = r.splits;
+      d["cps"] = r.cps;
+      if (r.path == cml::WG_PATH_GRAM) return d;   // (gram1x1.hip's own tile and fold)
+      d["TM"] = r.TM;
+      d["TN"] = r.TN;
+      d["KC"] = r.KC;
+      d["direct"] = r.direct;
+      d["fold"] = std::string(folds[r.fold]);
+    } else if (kind == "s2") {
+      TORCH_CHECK(a.size() == 6, "wgrad_route('s2', N, H, W, Co, Ci, taps)");
+      cml::WgradS2Route r;
+      cml::wgrad3x3s2_route(small(0, "N"), small(1, "H"), small(2, "W"), small(3, "Co"),
+                            small(4, "Ci"), small(5, "taps"), &r);
+      // (the binding's own limits, as wgrad3x3s2_ok applies them)
+      const bool ok = r.ok && wgrad3x3s2_ok(arg(0), arg(1), arg(2), arg(3), arg(4), arg(5));
+      d["ok"] = ok;
+      if (!ok) return d;
+      d["TM"] = r.TM;
+      d["TN"] = r.TN;
+      d["stages"] = r.stages;
+      d["splits"] = r.splits;
+      d["cps"] = r.cps;
+      d["fold"] = std::string(folds[r.fold]);
+    } else if (kind == "3x3") {
+      TORCH_CHECK(a.size() == 5, "wgrad_route('3x3', B, H, W, Co, Ci)");
+      cml::Wgrad3x3Route r;
+      d["ok"] = cml::wgrad3x3_route(small(0, "B"), small(1, "H"), small(2, "W"), small(3, "Co"),
+                                    small(4, "Ci"), &r);
+      if (!r.ok) return d;
+      d["R"] = r.R;
+      d["G"] = r.G;
+      d["npx"] = r.npx;
+      d["nch"] = r.nch;
+      d["splits"] = r.splits;
+      d["cps"] = r.cps;
+      d["tci"] = r.tci;
+      d["dy_rows"] = r.dy_rows;
+      d["grid"] = r.grid;
+      d["fold"] = std::string(folds[r.fold]);
+    } else {
+      TORCH_CHECK(false, "wgrad_route: kind is '1x1', 's2' or '3x3'");
+    }
+    return d;
+  }, "the kernel, tile and split plan a weight-gradient launch takes for this shape in this "
+     "process: ('1x1', P, Co, Ci, pro, dmode, colsum[, same[, bf16]]) | ('s2', N, H, W, Co, Ci, "
+     "taps) | ('3x3', B, H, W, Co, Ci)");
   m.def("gemm_nt_pick", &gemm_nt_pick, "EP_STORE tile choice of gemm_nt: 256, 128 or 0 (none)");
   m.attr("CMB_SORTED") = static_cast<int>(cml::CMB_SORTED);
   m.attr("CMB_WEIGHTED") = static_cast<int>(cml::CMB_WEIGHTED);

@@ -558,6 +558,35 @@ hipError_t launch_wgrad3x3_direct(const void* dy, const void* x, const void* zer
                                   void* dw, bool dw_bf16, int B, int H, int W, int Co, int Ci,
                                   hipStream_t st);
 
+// Read-only reports of the weight-gradient launches, computed by the host code the launches use
+// (bindings: wgrad_settings, wgrad_route). The read-once switches as this process read them:
+// CML_WGRAD_DMA, CML_WGRAD_DMA_XF (0 / 1), CML_WGRAD_DMA_NS128, CML_FOLD_WIDE_MIN and
+// CML_WGRAD3X3_DIRECT (the integers read).
+void wgrad_settings(int* dma, int* dma_xf, int* dma_ns128, int* fold_wide_min);
+int wgrad3x3_direct_setting();
+enum { WG_FOLD_NONE = 0, WG_FOLD_NARROW = 1, WG_FOLD_WIDE = 2 };
+enum { WG_PATH_GRAM = 0, WG_PATH_DMA = 1, WG_PATH_STAGED = 2 };
+int wgrad_fold_kind(int S);   // the fold kernel of S splits (narrow or wide)
+// launch_wgrad1x1_ex's route. same: dy and x are one storage and a dmode-3 prologue uses the x
+// prologue's own constants (what gram1x1_route asks of the pointers). ok false: the launch
+// refuses the call (channel counts, P, column sums in a tile without them).
+struct Wgrad1x1Route {
+  bool ok, direct;
+  int path, TM, TN, KC, splits, cps, fold;
+};
+void wgrad1x1_route(int64_t P, int Co, int Ci, bool pro, int dmode, bool cs, bool same,
+                    bool dw_bf16, Wgrad1x1Route* r);
+struct WgradS2Route {
+  bool ok;
+  int TM, TN, stages, splits, cps, fold;
+};
+void wgrad3x3s2_route(int N, int H, int W, int Co, int Ci, int taps, WgradS2Route* r);
+struct Wgrad3x3Route {
+  bool ok;
+  int R, G, npx, nch, splits, cps, tci, dy_rows, grid, fold;
+};
+bool wgrad3x3_route(int B, int H, int W, int Co, int Ci, Wgrad3x3Route* r);
+
 // Fused 1x1 convolution forward (conv1x1.hip): y[M][N] = f(x)[src(m)][K] W[N][K]^T on NHWC bf16,
 // f = identity or max(x * pro_sc + pro_bi, 0) per input channel (pro_sc != null), src(m) = m
 // (stride 1) or the stride-2 pixel of an [*, H, W] input. With part / mean non-null also the

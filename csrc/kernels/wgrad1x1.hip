@@ -721,8 +721,7 @@ int fold_wide_min() {
 
 // out[0:n] = sum over S rows of part [S][n] (n % 4 == 0), fixed order, bf16 or fp32 out.
 void fold_splits(const float* part, int S, int64_t n, void* out, bool out_bf16, hipStream_t st) {
-  const int wmin = fold_wide_min();
-  if (wmin > 0 && S >= wmin) {
+  if (wgrad_fold_kind(S) == WG_FOLD_WIDE) {
     const int64_t b = (n + 63) / 64;
     if (out_bf16) wgrad_fold_wide_kernel<true><<<static_cast<unsigned>(b), 256, 0, st>>>(part, S, n, out);
     else wgrad_fold_wide_kernel<false><<<static_cast<unsigned>(b), 256, 0, st>>>(part, S, n, out);
@@ -740,8 +739,7 @@ void fold_dw_cs(const float* part, int64_t n, void* dw, bool dw_bf16, const floa
     fold_splits(part, S, n, dw, dw_bf16, st);
     return;
   }
-  const int wmin = fold_wide_min();
-  const bool wide = wmin > 0 && S >= wmin;
+  const bool wide = wgrad_fold_kind(S) == WG_FOLD_WIDE;
   const int64_t b1 = wide ? (n + 63) / 64 : (n / 4 + 255) / 256;
   const int64_t b2 = wide ? (ncs + 63) / 64 : (ncs / 4 + 255) / 256;
 #define CML_FP(W, B)                                                                            \
@@ -821,12 +819,16 @@ int chunk_of(int, int) { return 64; }
 namespace {
 // LDS-DMA kernel tile for a plain (no prologue / column sums) weight gradient, or false
 // (CML_WGRAD_DMA=0 disables it: A/B)
-bool dma_tile(int64_t P, int Co, int Ci, int* TM, int* TN) {
+bool dma_enabled() {
   static const bool on = [] {
     const char* e = getenv("CML_WGRAD_DMA");
     return !(e && e[0] == '0');
   }();
-  if (!on || P < kDmaKC || P % kDmaKC || P >= (1ll << 31)) return false;
+  return on;
+}
+
+bool dma_tile(int64_t P, int Co, int Ci, int* TM, int* TN) {
+  if (!dma_enabled() || P < kDmaKC || P % kDmaKC || P >= (1ll << 31)) return false;
   if (Co % 256 == 0 && Ci % 256 == 0) { *TM = 256; *TN = 256; }
   else if (Co % 128 == 0 && Ci % 256 == 0) { *TM = 128; *TN = 256; }
   else if (Co % 256 == 0 && Ci % 128 == 0) { *TM = 256; *TN = 128; }
@@ -867,44 +869,64 @@ hipError_t launch_dma(DmaArgs a, int64_t P, int S, int cps, hipStream_t st) {
   return hipSuccess;
 }
 
+// pipeline stages: the 256 x 256 tile, the 128 x 256 / 256 x 128 tiles
+constexpr int kNS256 = 4, kNS128x = 6;
+
+// the stride-2 128 x 128 tile: 8 stages (1 workgroup / CU) or 4 (2 workgroups / CU):
+// CML_WGRAD_DMA_NS128 (A/B)
+int dma_ns128() {
+  static const int ns = [] {
+    const char* e = getenv("CML_WGRAD_DMA_NS128");
+    return e ? atoi(e) : 4;
+  }();
+  return ns;
+}
+
+// stages of the tile launch_dma_tile / launch_dma_xf take (0: no such tile)
+int dma_stages(int TM, int TN, bool s2) {
+  if (TM == 256 && TN == 256) return kNS256;
+  if ((TM == 128 && TN == 256) || (TM == 256 && TN == 128)) return kNS128x;
+  if (TM == 128 && TN == 128 && s2) return dma_ns128() == 8 ? 8 : 4;
+  return 0;
+}
+
 template <bool PRO, bool DPM>
 hipError_t launch_dma_xf(int TM, int TN, const DmaArgs& a, int64_t P, int S, int cps,
                          hipStream_t st) {
-  if (TM == 256 && TN == 256) return launch_dma<256, 256, 4, 128, false, PRO, DPM>(a, P, S, cps, st);
-  if (TM == 256 && TN == 128) return launch_dma<256, 128, 6, 128, false, PRO, DPM>(a, P, S, cps, st);
+  if (TM == 256 && TN == 256) return launch_dma<256, 256, kNS256, 128, false, PRO, DPM>(a, P, S, cps, st);
+  if (TM == 256 && TN == 128) return launch_dma<256, 128, kNS128x, 128, false, PRO, DPM>(a, P, S, cps, st);
   if constexpr (!DPM)
-    if (TM == 128 && TN == 256) return launch_dma<128, 256, 6, 128, false, PRO, DPM>(a, P, S, cps, st);
+    if (TM == 128 && TN == 256) return launch_dma<128, 256, kNS128x, 128, false, PRO, DPM>(a, P, S, cps, st);
   return hipErrorInvalidValue;
 }
 
 hipError_t launch_dma_tile(int TM, int TN, bool s2, const DmaArgs& a, int64_t P, int S, int cps,
                            hipStream_t st) {
-  if (TM == 256 && TN == 256) return s2 ? launch_dma<256, 256, 4, 128, true>(a, P, S, cps, st)
-                                        : launch_dma<256, 256, 4, 128, false>(a, P, S, cps, st);
-  if (TM == 128 && TN == 256) return s2 ? launch_dma<128, 256, 6, 128, true>(a, P, S, cps, st)
-                                        : launch_dma<128, 256, 6, 128, false>(a, P, S, cps, st);
-  if (TM == 256 && TN == 128) return s2 ? launch_dma<256, 128, 6, 128, true>(a, P, S, cps, st)
-                                        : launch_dma<256, 128, 6, 128, false>(a, P, S, cps, st);
-  if (TM == 128 && TN == 128 && s2) {
-    // 8 stages (1 workgroup / CU) or 4 (2 workgroups / CU): CML_WGRAD_DMA_NS128 (A/B)
-    static const int ns = [] {
-      const char* e = getenv("CML_WGRAD_DMA_NS128");
-      return e ? atoi(e) : 4;
-    }();
-    return ns == 8 ? launch_dma<128, 128, 8, 64, true>(a, P, S, cps, st)
-                   : launch_dma<128, 128, 4, 64, true>(a, P, S, cps, st);
-  }
+  if (TM == 256 && TN == 256) return s2 ? launch_dma<256, 256, kNS256, 128, true>(a, P, S, cps, st)
+                                        : launch_dma<256, 256, kNS256, 128, false>(a, P, S, cps, st);
+  if (TM == 128 && TN == 256) return s2 ? launch_dma<128, 256, kNS128x, 128, true>(a, P, S, cps, st)
+                                        : launch_dma<128, 256, kNS128x, 128, false>(a, P, S, cps, st);
+  if (TM == 256 && TN == 128) return s2 ? launch_dma<256, 128, kNS128x, 128, true>(a, P, S, cps, st)
+                                        : launch_dma<256, 128, kNS128x, 128, false>(a, P, S, cps, st);
+  if (TM == 128 && TN == 128 && s2)
+    return dma_stages(128, 128, true) == 8 ? launch_dma<128, 128, 8, 64, true>(a, P, S, cps, st)
+                                           : launch_dma<128, 128, 4, 64, true>(a, P, S, cps, st);
   return hipErrorInvalidValue;
 }
 
 // DMA eligibility of a wgrad1x1 call: plain; x prologue (PRO); DP_MASK dy prologue (TM 256),
 // with its column sums. CML_WGRAD_DMA_XF=0 keeps the prologue variants on the register-staged
 // kernel (A/B).
-bool dma_ok(int64_t P, int Co, int Ci, bool pro, int dmode, bool cs, int* TM, int* TN) {
+bool dma_xf_enabled() {
   static const bool xf = [] {
     const char* e = getenv("CML_WGRAD_DMA_XF");
     return !(e && e[0] == '0');
   }();
+  return xf;
+}
+
+bool dma_ok(int64_t P, int Co, int Ci, bool pro, int dmode, bool cs, int* TM, int* TN) {
+  const bool xf = dma_xf_enabled();
   if (dmode != DP_NONE && dmode != DP_MASK) return false;
   if (cs && dmode != DP_MASK) return false;
   if ((pro || dmode != DP_NONE) && !xf) return false;
@@ -963,6 +985,77 @@ void staged_plan(int64_t P, int Co, int Ci, int* splits, int* cps, bool pro) {
   *splits = (nchunk + c - 1) / c;
 }
 
+// the fold kernel of S splits; fold_splits and fold_dw_cs launch by it
+int wgrad_fold_kind(int S) {
+  const int wmin = fold_wide_min();
+  return wmin > 0 && S >= wmin ? WG_FOLD_WIDE : WG_FOLD_NARROW;
+}
+
+namespace {
+// Kernel, tile, chunk and split plan of a wgrad1x1_general call (pro: x prologue, dmode: dy
+// prologue, cs: column sums); wgrad1x1_general launches what this says and wgrad1x1_route reports
+// it. ok false: the call is refused.
+void general_route(int64_t P, int Co, int Ci, bool pro, int dmode, bool cs, Wgrad1x1Route* r) {
+  *r = Wgrad1x1Route{};
+  if (dmode < DP_NONE || dmode > DP_BNRELU) return;
+  // (the column sums have no 1024-thread tile either: it takes the prologue tiles)
+  const bool anypro = pro || dmode != DP_NONE || cs;
+  {
+    int tm, tn;
+    pick_tile(Co, Ci, &tm, &tn, anypro);
+    if (cs && tm * tn > 32768) return;   // no column sums in that tile
+  }
+  if (!(Co == 64 && Ci == 64) && (Ci == 64 ? Co % 256 != 0 : (Co % 128 || Ci % 128))) return;
+  if (P < 1 || P >= (1ll << 31)) return;
+  r->ok = true;
+  if (dma_ok(P, Co, Ci, pro, dmode, cs, &r->TM, &r->TN)) {
+    dma_plan(P, Co, Ci, r->TM, r->TN, &r->splits, &r->cps);
+    r->path = WG_PATH_DMA;
+    r->KC = kDmaKC;
+    r->direct = r->splits == 1 && !cs;
+  } else {
+    staged_plan(P, Co, Ci, &r->splits, &r->cps, anypro);
+    pick_tile(Co, Ci, &r->TM, &r->TN, anypro);
+    r->path = WG_PATH_STAGED;
+    r->KC = chunk_of(r->TM, r->TN);
+  }
+  r->fold = r->direct ? WG_FOLD_NONE : wgrad_fold_kind(r->splits);
+}
+}  // namespace
+
+void wgrad1x1_route(int64_t P, int Co, int Ci, bool pro, int dmode, bool cs, bool same,
+                    bool dw_bf16, Wgrad1x1Route* r) {
+  // (gram1x1_route only compares the pointers: one stand-in address for "the same storage")
+  static const float tag = 0.f;
+  const float* sc = pro ? &tag : nullptr;
+  if (same && gram1x1_route(&tag, &tag, Co, Ci, sc, sc, dmode, dmode == DP_BNRELU ? sc : nullptr,
+                            dmode == DP_BNRELU ? sc : nullptr, dw_bf16)) {
+    *r = Wgrad1x1Route{};
+    r->ok = P >= 1;
+    r->path = WG_PATH_GRAM;   // (tile, chunk and fold are gram1x1.hip's own: not reported)
+    gram1x1_plan(P, Co, &r->splits, &r->cps);
+    return;
+  }
+  general_route(P, Co, Ci, pro, dmode, cs, r);
+}
+
+void wgrad3x3s2_route(int N, int H, int W, int Co, int Ci, int taps, WgradS2Route* r) {
+  *r = WgradS2Route{};
+  if ((taps != 9 && taps != 1) || !s2_tile(N, H, W, Co, Ci, &r->TM, &r->TN)) return;
+  r->ok = true;
+  dma_plan(static_cast<int64_t>(N) * (H / 2) * (W / 2), Co, taps * Ci, r->TM, r->TN, &r->splits,
+           &r->cps);
+  r->stages = dma_stages(r->TM, r->TN, true);
+  r->fold = wgrad_fold_kind(r->splits);
+}
+
+void wgrad_settings(int* dma, int* dma_xf, int* ns128, int* fold_wide) {
+  *dma = dma_enabled() ? 1 : 0;
+  *dma_xf = dma_xf_enabled() ? 1 : 0;
+  *ns128 = dma_ns128();
+  *fold_wide = fold_wide_min();
+}
+
 // every launch_wgrad1x1_ex call but the Gram products; launch_wgrad1x1 takes it directly, its
 // callers size `part` from wgrad1x1_plan alone
 hipError_t wgrad1x1_general(const void* dy, const void* x, float* part, void* dw, bool dw_bf16,
@@ -1001,28 +1094,19 @@ hipError_t wgrad1x1_general(const void* dy, const void* x, float* part, void* dw
   if (dmode == DP_FULL && (!dz_z || !dz_mask || !dz_a || !dz_b || !dz_c)) return hipErrorInvalidValue;
   if (dmode == DP_MASK && (!dz_mask || !dz_a || !dz_c)) return hipErrorInvalidValue;
   if (dmode == DP_BNRELU && (!dz_a || !dz_b)) return hipErrorInvalidValue;
-  if (dmode < DP_NONE || dmode > DP_BNRELU || ((cs_part == nullptr) != (cs == nullptr)))
-    return hipErrorInvalidValue;
-  {
-    int tm, tn;
-    pick_tile(Co, Ci, &tm, &tn, pro_sc != nullptr || dmode != DP_NONE || cs != nullptr);
-    if (cs && tm * tn > 32768) return hipErrorInvalidValue;   // no column sums in that tile
-  }
-  DPro dp{reinterpret_cast<const uint16_t*>(dz_z), dz_mask, dz_a, dz_b, dz_c};
-  if (!(Co == 64 && Ci == 64) && (Ci == 64 ? Co % 256 != 0 : (Co % 128 || Ci % 128)))
-    return hipErrorInvalidValue;
-  if (P < 1 || P >= (1ll << 31)) return hipErrorInvalidValue;
+  if ((cs_part == nullptr) != (cs == nullptr)) return hipErrorInvalidValue;
   if ((pro_sc == nullptr) != (pro_bi == nullptr)) return hipErrorInvalidValue;
-  int S, cps, TM, TN;
-  // (the column sums have no 1024-thread tile either: it takes the prologue tiles)
-  const bool anypro = pro_sc != nullptr || dmode != DP_NONE || cs != nullptr;
-  if (dma_ok(P, Co, Ci, pro_sc != nullptr, dmode, cs != nullptr, &TM, &TN)) {
+  Wgrad1x1Route rt;
+  general_route(P, Co, Ci, pro_sc != nullptr, dmode, cs != nullptr, &rt);
+  if (!rt.ok) return hipErrorInvalidValue;
+  DPro dp{reinterpret_cast<const uint16_t*>(dz_z), dz_mask, dz_a, dz_b, dz_c};
+  const int S = rt.splits, cps = rt.cps, TM = rt.TM, TN = rt.TN;
+  if (rt.path == WG_PATH_DMA) {
     // (the caller sized `part` from this plan: no fallback to the staged kernel's splits)
     if ((reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(x)) % 16)
       return hipErrorInvalidValue;
-    dma_plan(P, Co, Ci, TM, TN, &S, &cps);
     // one split, no column sums: the kernel writes dW itself (wgrad1x1_direct; part may be null)
-    const bool direct = S == 1 && cs == nullptr;
+    const bool direct = rt.direct;
     if (!direct && part == nullptr) return hipErrorInvalidValue;
     DmaArgs da{};
     da.dy = reinterpret_cast<const uint16_t*>(dy);
@@ -1050,9 +1134,7 @@ hipError_t wgrad1x1_general(const void* dy, const void* x, float* part, void* dw
     return hipGetLastError();
   }
   if (part == nullptr) return hipErrorInvalidValue;
-  staged_plan(P, Co, Ci, &S, &cps, anypro);
-  pick_tile(Co, Ci, &TM, &TN, anypro);
-  const int KC = chunk_of(TM, TN);
+  const int KC = rt.KC;
   const int tiles_n = Ci / TN;
   const dim3 grid((Co / TM) * tiles_n, S);
   const auto* dyp = reinterpret_cast<const uint16_t*>(dy);
@@ -1086,22 +1168,24 @@ hipError_t wgrad1x1_general(const void* dy, const void* x, float* part, void* dw
 }
 
 bool wgrad3x3s2_plan(int N, int H, int W, int Co, int Ci, int* splits, int taps) {
-  int TM, TN, cps;
-  if ((taps != 9 && taps != 1) || !s2_tile(N, H, W, Co, Ci, &TM, &TN)) return false;
-  dma_plan(static_cast<int64_t>(N) * (H / 2) * (W / 2), Co, taps * Ci, TM, TN, splits, &cps);
+  WgradS2Route r;
+  wgrad3x3s2_route(N, H, W, Co, Ci, taps, &r);
+  if (!r.ok) return false;
+  *splits = r.splits;
   return true;
 }
 
 hipError_t launch_wgrad3x3s2(const void* dy, const void* x, const void* zero, float* part,
                              void* dw, bool dw_bf16, int N, int H, int W, int Co, int Ci,
                              hipStream_t st, int taps) {
-  int TM, TN, S, cps;
-  if ((taps != 9 && taps != 1) || !s2_tile(N, H, W, Co, Ci, &TM, &TN)) return hipErrorInvalidValue;
+  WgradS2Route r;
+  wgrad3x3s2_route(N, H, W, Co, Ci, taps, &r);
+  if (!r.ok) return hipErrorInvalidValue;
   if ((reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(x) |
        reinterpret_cast<uintptr_t>(zero)) % 16)
     return hipErrorInvalidValue;
   const int64_t P = static_cast<int64_t>(N) * (H / 2) * (W / 2);
-  dma_plan(P, Co, taps * Ci, TM, TN, &S, &cps);
+  const int TM = r.TM, TN = r.TN, S = r.splits, cps = r.cps;
   DmaArgs da{};
   da.dy = reinterpret_cast<const uint16_t*>(dy);
   da.x = reinterpret_cast<const uint16_t*>(x);

@@ -230,11 +230,10 @@ int direct_enabled() {
   return v;
 }
 
-}  // namespace
-
-bool wgrad3x3_direct_plan(int B, int H, int W, int Co, int Ci, int* splits, int* tci) {
-  if (!direct_enabled() || B < 1 || H < 1 || W < 1 || Co % 64 || !(Ci == 64 || Ci % 128 == 0))
-    return false;
+// Chunk geometry of a B x H x W batch: R rows of one image per chunk (G == 1) or G whole images
+// (R == H), and the rows of the padded dy image a chunk holds in LDS. The plan, the launch and
+// wgrad3x3_route all take it from here. False: no row count within a chunk divides H.
+bool chunk_geometry(int B, int H, int W, int* R_, int* G_, int* dy_rows) {
   int R, G = 1;
   if (H * W <= kKP) {
     R = H;
@@ -249,7 +248,45 @@ bool wgrad3x3_direct_plan(int B, int H, int W, int Co, int Ci, int* splits, int*
   const int k = kKP - 1, HW = H * W;
   const int maxrow = k + 2 * (k / W) + (G > 1 ? (k / HW) * (2 * W + 4) : 0) + 2 * (W + 2) + 2;
   const int PB = (G == 1 ? R + 2 : H + 2) * (W + 2);
-  const int dyr = std::max(G * PB, maxrow + 1);
+  *R_ = R;
+  *G_ = G;
+  *dy_rows = std::max(G * PB, maxrow + 1);
+  return true;
+}
+
+// The launch's shape arguments for the plan's S splits and ci tile T (pointers left null). False:
+// the geometry does not fit the per-wave DMA plan or LDS.
+bool launch_args(int B, int H, int W, int Co, int Ci, int S, int T, W3Args* out, int* dy_rows) {
+  W3Args a{};
+  a.H = H;
+  a.W = W;
+  a.Co = Co;
+  a.Ci = Ci;
+  int dyr;
+  if (!chunk_geometry(B, H, W, &a.R, &a.G, &dyr)) return false;
+  a.npx = a.G * a.R * W;
+  a.nch = a.G == 1 ? B * (H / a.R) : B / a.G;
+  a.cps = (a.nch + S - 1) / S;
+  a.tiles_ci = Ci / T;
+  a.tiles = (Co / 64) * a.tiles_ci;
+  a.rx = (kKP * (T * 2 + 64) + 1023) / 1024 * 1024;
+  a.rd = (dyr * kRBD + 1023) / 1024 * 1024;
+  if ((a.rx >> 10) > kNW * kMaxIX || (a.rd >> 10) > kNW * kMaxID) return false;
+  if (2 * static_cast<size_t>(a.rx + a.rd) > 160 * 1024) return false;
+  *out = a;
+  *dy_rows = dyr;
+  return true;
+}
+
+}  // namespace
+
+int wgrad3x3_direct_setting() { return direct_enabled(); }
+
+bool wgrad3x3_direct_plan(int B, int H, int W, int Co, int Ci, int* splits, int* tci) {
+  if (!direct_enabled() || B < 1 || H < 1 || W < 1 || Co % 64 || !(Ci == 64 || Ci % 128 == 0))
+    return false;
+  int R, G, dyr;
+  if (!chunk_geometry(B, H, W, &R, &G, &dyr)) return false;
   if (dyr > kMaxDyRows) return false;
   const int T = Ci % 128 == 0 ? 128 : 64;
   const int64_t nch = G == 1 ? static_cast<int64_t>(B) * (H / R) : B / G;
@@ -263,44 +300,40 @@ bool wgrad3x3_direct_plan(int B, int H, int W, int Co, int Ci, int* splits, int*
   return true;
 }
 
+bool wgrad3x3_route(int B, int H, int W, int Co, int Ci, Wgrad3x3Route* r) {
+  *r = Wgrad3x3Route{};
+  int S, T, dyr;
+  W3Args a{};
+  if (!wgrad3x3_direct_plan(B, H, W, Co, Ci, &S, &T) ||
+      !launch_args(B, H, W, Co, Ci, S, T, &a, &dyr))
+    return false;
+  r->ok = true;
+  r->R = a.R;
+  r->G = a.G;
+  r->npx = a.npx;
+  r->nch = a.nch;
+  r->splits = S;
+  r->cps = a.cps;
+  r->tci = T;
+  r->dy_rows = dyr;
+  r->grid = a.tiles * S;
+  r->fold = wgrad_fold_kind(S);
+  return true;
+}
+
 hipError_t launch_wgrad3x3_direct(const void* dy, const void* x, const void* zero, float* part,
                                   void* dw, bool dw_bf16, int B, int H, int W, int Co, int Ci,
                                   hipStream_t st) {
-  int S, T;
-  if (!wgrad3x3_direct_plan(B, H, W, Co, Ci, &S, &T)) return hipErrorInvalidValue;
+  int S, T, dyr;
   W3Args a{};
+  if (!wgrad3x3_direct_plan(B, H, W, Co, Ci, &S, &T) ||
+      !launch_args(B, H, W, Co, Ci, S, T, &a, &dyr))
+    return hipErrorInvalidValue;
   a.dy = reinterpret_cast<const uint16_t*>(dy);
   a.x = reinterpret_cast<const uint16_t*>(x);
   a.zero = reinterpret_cast<const uint16_t*>(zero);
   a.part = part;
-  a.H = H;
-  a.W = W;
-  a.Co = Co;
-  a.Ci = Ci;
-  const int HW = H * W;
-  if (HW <= kKP) {
-    a.R = H;
-    a.G = 1;
-    for (int g = kKP / HW; g >= 1; --g)
-      if (B % g == 0) { a.G = g; break; }
-  } else {
-    a.G = 1;
-    for (int r = kKP / W; r >= 1; --r)
-      if (H % r == 0) { a.R = r; break; }
-  }
-  a.npx = a.G * a.R * W;
-  a.nch = a.G == 1 ? B * (H / a.R) : B / a.G;
-  a.cps = (a.nch + S - 1) / S;
-  a.tiles_ci = Ci / T;
-  a.tiles = (Co / 64) * a.tiles_ci;
-  const int k = kKP - 1;
-  const int maxrow = k + 2 * (k / W) + (a.G > 1 ? (k / HW) * (2 * W + 4) : 0) + 2 * (W + 2) + 2;
-  const int dyr = std::max(a.G * (a.G == 1 ? a.R + 2 : H + 2) * (W + 2), maxrow + 1);
-  a.rx = (kKP * (T * 2 + 64) + 1023) / 1024 * 1024;
-  a.rd = (dyr * kRBD + 1023) / 1024 * 1024;
-  if ((a.rx >> 10) > kNW * kMaxIX || (a.rd >> 10) > kNW * kMaxID) return hipErrorInvalidValue;
   const size_t lds = 2 * static_cast<size_t>(a.rx + a.rd);
-  if (lds > 160 * 1024) return hipErrorInvalidValue;
   const int grid = a.tiles * S;
   auto kern = T == 128 ? &wgrad3x3_kernel<128> : &wgrad3x3_kernel<64>;
   (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern),

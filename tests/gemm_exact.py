@@ -432,22 +432,24 @@ def check_route(name):
     assert got == tuple(kw["route"]), f"route {got}, expected {tuple(kw['route'])}"
 
 
-def run_child(expect, names, routes_only=False):
+def run_child(expect, names, routes_only=False, script=None, env_of=None, defaults=None):
     """Run `names` in a fresh process whose environment sets exactly `expect`'s variables, one
     JSON line per case; assert the settings it read and that every case passed. routes_only: the
-    child checks the settings and the conv cases' routes and touches no GPU."""
-    env = {k: v for k, v in os.environ.items() if k not in ENV_OF.values()}
+    child checks the settings and the conv cases' routes and touches no GPU. script / env_of /
+    defaults: another oracle's child mode with its own read-once settings (wgrad_oracle.py)."""
+    env_of = ENV_OF if env_of is None else env_of
+    env = {k: v for k, v in os.environ.items() if k not in env_of.values()}
     env["PYTHONPATH"] = ROOT
     for k, v in expect.items():
-        env[ENV_OF[k]] = str(v)
-    r = subprocess.run([sys.executable, os.path.abspath(__file__),
+        env[env_of[k]] = str(v)
+    r = subprocess.run([sys.executable, os.path.abspath(script or __file__),
                         json.dumps({"expect": expect, "cases": list(names),
                                     "routes_only": routes_only})],
                        env=env, capture_output=True, text=True, timeout=300)
     print(r.stdout[-6000:])
     assert r.returncode == 0, f"child exit {r.returncode}: {r.stderr[-3000:]}"
     res = [json.loads(ln) for ln in r.stdout.splitlines() if ln.startswith("{")]
-    want = dict(DEFAULTS, **expect)
+    want = dict(DEFAULTS if defaults is None else defaults, **expect)
     assert [x["name"] for x in res] == list(names), "the child did not run every case"
     for x in res:
         assert x["settings"] == want, (x["name"], x["settings"], want)
