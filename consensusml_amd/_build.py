@@ -29,6 +29,12 @@ ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 CXX = os.environ.get("CXX", "g++")
 EXT_SUFFIX = sysconfig.get_config_var("EXT_SUFFIX") or ".so"
+# extra hipcc flags of single kernel sources (csrc/kernels/*.hip are all compiled; a new file
+# needs no entry). flash_attn64.hip: scalar fp32 VALU only, no packed fp32 pairs in its softmax
+# rescale and store scaling
+SRC_FLAGS = {
+    "flash_attn64.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+}
 
 
 def _torch_paths():
@@ -80,7 +86,8 @@ def build_kernels(force: bool = False, verbose: bool = False) -> str:
         obj = os.path.join(BUILD, os.path.basename(src) + ".o")
         objs.append(obj)
         if force or _newer(obj, [src] + hdrs):
-            jobs.append([HIPCC, f"--offload-arch={ARCH}", *common, "-I", CSRC, "-c", src, "-o", obj])
+            jobs.append([HIPCC, f"--offload-arch={ARCH}", *common,
+                         *SRC_FLAGS.get(os.path.basename(src), []), "-I", CSRC, "-c", src, "-o", obj])
     bsrc = os.path.join(CSRC, "bindings.cpp")
     bobj = os.path.join(BUILD, "bindings.cpp.o")
     objs.append(bobj)

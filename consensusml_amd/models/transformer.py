@@ -1,6 +1,7 @@
 """BERT-base and Llama-3 transformer families (N12).
 
-Attention runs own MFMA kernels: BERT's short sequences ``csrc/kernels/attention.hip``, Llama's
+Attention runs own MFMA kernels: BERT's short sequences ``csrc/kernels/attention.hip`` (past
+S = 128 the head-dim-64 flash kernels of ``csrc/kernels/flash_attn64.hip``), Llama's
 causal GQA attention (head dim 128) ``csrc/kernels/flash_attn.hip`` forward and backward. The
 GEMMs are gemm.hip or hipBLASLt. Everything between them runs the hand-written HIP kernels of
 ``csrc/kernels/transformer.hip`` (``ops.transformer``) on bf16 GPU tensors:

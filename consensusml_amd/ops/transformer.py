@@ -373,16 +373,47 @@ def _attn_ok(qkv: torch.Tensor, H: int, hd: int) -> bool:
 # PerfPolicy.attn_kernel: short-sequence MFMA attention for BERT-shaped problems (off: SDPA)
 
 
-def fused_qkv_attention(qkv: torch.Tensor, H: int, hd: int) -> torch.Tensor:
-    """Non-causal multi-head attention straight from the fused projection ``qkv [B, S, 3 H hd]``
-    to ``[B, S, H hd]`` (the output projection's input layout). S <= 128, hd = 64 bf16 GPU
-    tensors run csrc/kernels/attention.hip (one workgroup per (batch, head), MFMA, exact
-    softmax); anything else splits the heads and runs SDPA."""
+class _Flash64Fn(torch.autograd.Function):
+    """Flash attention for head dim 64 on csrc/kernels/flash_attn64.hip, fused layouts on both
+    sides: qkv [B, S, 3 H 64] -> o [B, S, H 64]; the backward's two kernels write every element of
+    dqkv themselves."""
+
+    @staticmethod
+    def forward(ctx, qkv, H, causal, scale):
+        o, lse = lib().flash64_fwd(qkv, H, causal, scale)
+        ctx.save_for_backward(qkv, o, lse)
+        ctx.cfg = (H, causal, scale)
+        return o
+
+    @staticmethod
+    def backward(ctx, do):
+        qkv, o, lse = ctx.saved_tensors
+        H, causal, scale = ctx.cfg
+        return lib().flash64_bwd(qkv, o, do, lse, H, causal, scale), None, None, None
+
+
+def _flash64_ok(qkv: torch.Tensor, hd: int, causal: bool) -> bool:
+    # non-causal S <= 128 stays with the short kernel, or with SDPA where that one refuses
+    # (S % 32 != 0): the flash kernel was not measured against SDPA there
+    return (hd == 64 and _P().flash_attn64 and _gpu_bf16(qkv) and (causal or qkv.shape[1] > 128)
+            and qkv.is_contiguous() and qkv.data_ptr() % 16 == 0)
+
+
+def fused_qkv_attention(qkv: torch.Tensor, H: int, hd: int, causal: bool = False) -> torch.Tensor:
+    """Multi-head attention (full, or causal with ``causal=True``) straight from the fused
+    projection ``qkv [B, S, 3 H hd]`` to ``[B, S, H hd]`` (the output projection's input layout).
+    hd = 64 bf16 GPU tensors: non-causal S <= 128 (S % 32 == 0) runs csrc/kernels/attention.hip
+    (one workgroup per (batch, head), exact softmax); S > 128, and causal attention at any S, run
+    the flash kernels of csrc/kernels/flash_attn64.hip. Anything else splits the heads and runs
+    SDPA."""
     B, S, _ = qkv.shape
-    if _attn_ok(qkv, H, hd):
+    if not causal and _attn_ok(qkv, H, hd):
         return _AttnFn.apply(qkv, H, 1.0 / math.sqrt(hd))
+    if _flash64_ok(qkv, hd, causal):
+        return _Flash64Fn.apply(qkv, H, bool(causal), 1.0 / math.sqrt(hd))
     q, k, v = qkv_split(qkv, H, H, hd)
-    return F.scaled_dot_product_attention(q, k, v).transpose(1, 2).reshape(B, S, H * hd)
+    return F.scaled_dot_product_attention(q, k, v, is_causal=bool(causal)).transpose(1, 2).reshape(
+        B, S, H * hd)
 
 
 # ============================================================================ flash attention

@@ -111,6 +111,10 @@ class PerfPolicy:
     attn_kernel: bool = True              # MFMA attention for short sequences (BERT)
     flash_attn: bool = True               # flash_attn.hip for head-dim-128 (GQA, causal) attention
                                           # (Llama); False: SDPA (AOTriton kernels on ROCm torch)
+    flash_attn64: bool = True             # flash_attn64.hip for head-dim-64 attention from the
+                                          # fused QKV layout past S = 128 (BERT at 256 / 384 / 512)
+                                          # and causal at any S; False: head split + SDPA
+                                          # (profiles/flash64/README.md)
     multi_copy: bool = True               # multi-tensor HIP copy for gradient capture
     batched_workers: bool = True          # virtual workers as one batched fwd/bwd (BERT)
     own_gemm: bool = True                 # gemm.hip for transformer linears with >= 128 tiles
@@ -184,6 +188,7 @@ class PerfPolicy:
             batch_wlayouts=_env_bool("CML_BATCH_WLAYOUTS", True),
             attn_kernel=_env_bool("CML_ATTN_KERNEL", True),
             flash_attn=_env_bool("CML_FLASH_ATTN", True),
+            flash_attn64=_env_bool("CML_FLASH_ATTN64", True),
             multi_copy=_env_bool("CML_MULTI_COPY", True),
             batched_workers=_env_bool("CML_BATCHED_WORKERS", True),
             own_gemm=_env_bool("CML_OWN_GEMM", True),

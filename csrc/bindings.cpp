@@ -2636,6 +2636,58 @@ std::vector<Tensor> flash_bwd(const Tensor& q, const Tensor& k, const Tensor& v,
   return {dq, dk, dv};
 }
 
+// Flash attention, head dim 64, fused layouts (csrc/kernels/flash_attn64.hip): qkv [B, S, 3 H 64]
+// bf16 contiguous -> (o [B, S, H 64], lse fp32 [B, H, S], log2 domain)
+void check_flash64_qkv(const Tensor& qkv, int64_t H) {
+  check_bf16c(qkv, "qkv");
+  TORCH_CHECK(H >= 1 && qkv.dim() == 3 && qkv.size(2) == 3 * H * 64 && qkv.size(0) >= 1 &&
+                  qkv.size(1) >= 1, "flash64: qkv must be [B, S, 3 H 64]");
+  TORCH_CHECK((reinterpret_cast<uintptr_t>(qkv.data_ptr()) & 15) == 0, "flash64: 16-B aligned qkv");
+}
+
+std::vector<Tensor> flash64_fwd(const Tensor& qkv, int64_t H, bool causal, double scale,
+                                double rescale_thr, int64_t nq) {
+  check_flash64_qkv(qkv, H);
+  TORCH_CHECK(nq >= 0 && nq <= 2, "flash64_fwd: nq must be 0 (auto), 1 or 2");
+  const int64_t B = qkv.size(0), S = qkv.size(1);
+  const c10::DeviceGuard guard(qkv.device());
+  Tensor o = at::empty({B, S, H * 64}, qkv.options());
+  Tensor lse = at::empty({B, H, S}, qkv.options().dtype(at::kFloat));
+  CML_CHECK_HIP(cml::launch_flash64_fwd(qkv.data_ptr(), o.data_ptr(), lse.data_ptr<float>(),
+                                        static_cast<int>(B), static_cast<int>(H),
+                                        static_cast<int>(S), static_cast<float>(scale), causal,
+                                        cur_stream(), static_cast<float>(rescale_thr),
+                                        static_cast<int>(nq)));
+  return {o, lse};
+}
+
+Tensor flash64_bwd(const Tensor& qkv, const Tensor& o, const Tensor& dout_in, const Tensor& lse,
+                   int64_t H, bool causal, double scale) {
+  check_flash64_qkv(qkv, H);
+  const int64_t B = qkv.size(0), S = qkv.size(1);
+  Tensor dout = dout_in.contiguous();
+  check_bf16c(o, "o");
+  check_bf16c(dout, "dout");
+  TORCH_CHECK(o.sizes() == dout.sizes() && o.dim() == 3 && o.size(0) == B && o.size(1) == S &&
+                  o.size(2) == H * 64, "flash64_bwd: o / dout must be [B, S, H 64]");
+  TORCH_CHECK((reinterpret_cast<uintptr_t>(o.data_ptr()) & 15) == 0 &&
+                  (reinterpret_cast<uintptr_t>(dout.data_ptr()) & 15) == 0,
+              "flash64_bwd: 16-B aligned o / dout");
+  TORCH_CHECK(lse.is_cuda() && lse.scalar_type() == at::kFloat && lse.is_contiguous() &&
+                  lse.numel() == B * H * S && lse.get_device() == qkv.get_device() &&
+                  o.get_device() == qkv.get_device() && dout.get_device() == qkv.get_device(),
+              "flash64_bwd: lse fp32 [B, H, S], all tensors on one device");
+  const c10::DeviceGuard guard(qkv.device());
+  Tensor dqkv = at::empty_like(qkv);
+  Tensor dsum = at::empty({B, H, S}, lse.options());
+  CML_CHECK_HIP(cml::launch_flash64_bwd(qkv.data_ptr(), o.data_ptr(), dout.data_ptr(),
+                                        lse.data_ptr<float>(), dsum.data_ptr<float>(),
+                                        dqkv.data_ptr(), static_cast<int>(B), static_cast<int>(H),
+                                        static_cast<int>(S), static_cast<float>(scale), causal,
+                                        cur_stream()));
+  return dqkv;
+}
+
 Tensor swiglu_fwd(const Tensor& h) {
   check_bf16c(h, "h");
   const int64_t F2 = h.size(-1);
@@ -3327,6 +3379,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("q"), py::arg("k"), py::arg("v"), py::arg("causal"), py::arg("scale"),
         py::arg("rescale_thr") = 8.0);
   m.def("flash_bwd", &flash_bwd, "flash attention backward (dq, per-query-head dk / dv)");
+  m.def("flash64_fwd", &flash64_fwd, "flash attention forward, head dim 64, fused qkv in",
+        py::arg("qkv"), py::arg("H"), py::arg("causal"), py::arg("scale"),
+        py::arg("rescale_thr") = 8.0, py::arg("nq") = 0);
+  m.def("flash64_bwd", &flash64_bwd, "flash attention backward, head dim 64, fused dqkv out");
   m.def("swiglu_fwd", &swiglu_fwd, "silu(a) * b over [a | b]");
   m.def("swiglu_bwd", &swiglu_bwd, "SwiGLU backward");
   m.def("attn_fwd", &attn_fwd, "short-sequence MFMA attention forward (fused qkv in)");

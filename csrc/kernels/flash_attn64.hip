@@ -1,0 +1,602 @@
+// Flash attention for head dim 64 straight from the fused QKV projection (BERT-base / GPT-2-small
+// shapes past the short kernel's S <= 128), MHA, full and causal, forward and backward on
+// v_mfma_f32_32x32x16_bf16, gfx950 / CDNA4.
+//
+// Layouts (those of attention.hip, so no split / transpose / gather copies exist on either side):
+//   qkv  [B, S, 3, H, 64]   row stride ld = 3 H 64; q / k / v of head h at column (j H + h) 64
+//   o, do [B, S, H * 64]
+//   lse  [B, H, S] fp32     log2 domain: m + log2(l) of the scores times scale * log2(e)
+//   dsum [B, H, S] fp32     D = rowsum(dO * O), written by the dQ kernel
+//   dqkv [B, S, 3, H, 64]   q section by the dQ kernel, k / v sections by the dK / dV kernel: every
+//                           element written exactly once (no zero-fill, no atomics, no group sum)
+//
+// MFMA 32x32x16 bf16: lane l (r = l & 31, h = l >> 5) holds A[r][8h + j], B[8h + j][r]
+// (j = 0..7) and C[(i & 3) + 8 (i >> 2) + 4h][r] (i = 0..15). As in flash_attn.hip every product
+// sums over the previous accumulator's ROW index, so accumulators are fed back as B operands with
+// no lane movement and the other operand comes from ds_read_b64_tr_b16 on the row images.
+//
+// What head dim 64 changes against flash_attn.hip:
+//   * rows are 128 B: a 16 KB image holds 128 rows. A staged tile is 128 keys (forward, dQ) or 128
+//     queries (dK / dV), consumed as two / four independent sub-tiles between ONE pair of barriers
+//     (half the barriers per key of the hd-128 kernel)
+//   * 4 k-steps per S^T tile, 2 output accumulators per 32 queries: Q is 16 VGPRs, O 32
+//   * the swizzle is attention.hip's sw64 (chunk c of row r at 16 (c ^ f((r >> 1) & 7))): LDS-DMA
+//     writes lane-linear (8 rows x 128 B per wave instruction), so f goes on each lane's SOURCE
+//     chunk; a row's 8 chunks stay inside its one 128-B line, so the global side stays coalesced
+//   * dK / dV: the lane's K AND V rows sit in registers (16 VGPRs each), so there is no resident V
+//     image: 66 KB of LDS and two workgroups per CU instead of 130 KB and one
+//
+// Forward (f64_fwd_kernel<CAUSAL, NQ>): 4 waves, a wave owns NQ x 32 queries.
+//   S^T = K Q^T, online softmax in the log2 domain with the deferred rescale (threshold = launch
+//   argument), O^T += V^T P^T. NQ = 2: every K row fragment and every V^T fragment read from LDS
+//   feeds two MFMAs, 256 queries per staged tile (248-250 VGPRs). NQ = 1: 128 queries per
+//   workgroup, twice the workgroups (139 VGPRs). Neither wins everywhere: NQ = 1 at BERT's
+//   8192-token steps (0.0226 vs 0.0266 ms at 16 x 12 x 512), NQ = 2 once the grid fills the chip
+//   several times over (0.076 vs 0.090 ms at 64 x 12 x 512); f64_nq() picks per launch.
+// dQ (f64_dq_kernel): 4 waves x 32 queries; D in the prologue; dS^T = P^T (dP^T - D),
+//   dQ^T += K^T dS^T. Q, dO fragments (32 VGPRs) + 4 score tiles (64) + dQ (32): a 64-query wave
+//   would need ~290 VGPRs and lose the second workgroup per CU, so it was not built.
+// dK / dV (f64_dkdv_kernel): 4 waves x 32 keys, Q / dO tiles of 128 queries + their lse / D staged.
+// LDS / occupancy: forward and dQ 2 x (K image + V image) = 64 KB; dK / dV 2 x (Q image + dO image
+//   + lse [128] + D [128]) = 66 KB; two workgroups (8 waves) per CU each.
+// Staging: 16-B global_load_lds from the fused rows into two buffers, one barrier per tile, the DMA
+// of tile t + 1 issued after the barrier of tile t. Work order: XCD-contiguous (batch, head)
+// ranges, heaviest causal blocks first; causal sub-tiles fully masked for a wave are skipped
+// wave-uniformly (barrier count uniform).
+#include <math.h>
+
+#include "common.h"
+#include "kernels.h"
+
+namespace cml {
+namespace {
+
+typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef short v4i16 __attribute__((ext_vector_type(4)));
+typedef __attribute__((address_space(3))) v4i16 lds_v4i16;
+typedef __attribute__((address_space(3))) void lds_void;
+typedef __attribute__((address_space(1))) void g_void;
+
+constexpr int kD = 64;                  // head dim
+constexpr int kBK = 128;                // rows per staged tile
+constexpr int kImg = kBK * 128;         // one [128][64] bf16 image: 16 KB
+constexpr int kThreads = 256;
+constexpr int kFwdSmem = 4 * kImg;              // 2 x (K, V)
+constexpr int kKVBuf = 2 * kImg + 1024;         // Q image, dO image, lse [128], D [128]
+constexpr int kKVSmem = 2 * kKVBuf;
+
+struct F64Args {
+  const uint16_t* qkv;    // [B, S, 3, H, 64]
+  const uint16_t* o;      // [B, S, H, 64]
+  const uint16_t* dout;   // [B, S, H, 64]
+  uint16_t* out;          // forward: o; backward: dqkv
+  float* lse;             // [B, H, S]
+  float* dsum;            // [B, H, S]
+  int B, H, S;
+  float c;                // scale * log2(e)
+  float scale;
+  float thr;              // forward: deferred-rescale threshold (log2 units)
+};
+
+__device__ __forceinline__ f32x16 mfma(bf16x8_t a, bf16x8_t b, f32x16 c) {
+  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
+}
+__device__ __forceinline__ f32x16 zero16() {
+  f32x16 z;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) z[i] = 0.f;
+  return z;
+}
+// accumulator row of register i for lane half h
+__device__ __forceinline__ int acc_row(int i, int h) { return (i & 3) + 8 * (i >> 2) + 4 * h; }
+__device__ __forceinline__ int swz_f(int row) {
+  const int k = (row >> 1) & 7;
+  return ((k & 1) << 2) | (k >> 1);
+}
+// byte offset of 16-B chunk ch / of element col of row `row` in a [rows][128 B] image
+__device__ __forceinline__ int sw(int row, int ch) { return row * 128 + 16 * (ch ^ swz_f(row)); }
+__device__ __forceinline__ int swe(int row, int col) { return sw(row, col >> 3) + 2 * (col & 7); }
+__device__ __forceinline__ bf16x8_t rowfrag(const char* img, int row, int ch) {
+  return *reinterpret_cast<const bf16x8_t*>(img + sw(row, ch));
+}
+__device__ __forceinline__ uint2 tr_rd(const char* p) {
+  return __builtin_bit_cast(uint2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4i16*)(p)));
+}
+// transposed operand of an image X [rows = k][64 cols = m]: elements 0-3 = X[ka + q][m],
+// 4-7 = X[kb + q][m] (q = 0..3), m = m0 + (lane & 31)
+__device__ __forceinline__ bf16x8_t trfrag(const char* img, int ka, int kb, int m0, int lane) {
+  const int q = (lane >> 2) & 3, col = m0 + 16 * ((lane >> 4) & 1) + 4 * (lane & 3);
+  const uint2 lo = tr_rd(img + swe(ka + q, col)), hi = tr_rd(img + swe(kb + q, col));
+  return __builtin_bit_cast(bf16x8_t, make_uint4(lo.x, lo.y, hi.x, hi.y));
+}
+// registers 8u..8u+7 of an accumulator as a bf16 operand fragment
+__device__ __forceinline__ bf16x8_t acc_frag(const f32x16& x, int u) {
+  const int o = 8 * u;
+  return __builtin_bit_cast(bf16x8_t, make_uint4(pk_bf16(x[o], x[o + 1]), pk_bf16(x[o + 2], x[o + 3]),
+                                                 pk_bf16(x[o + 4], x[o + 5]),
+                                                 pk_bf16(x[o + 6], x[o + 7])));
+}
+__device__ __forceinline__ float fexp2(float x) { return __builtin_amdgcn_exp2f(x); }
+
+// One row of 64 outputs times sc as bf16: o[dt][4g..4g+3] = elements 32 dt + 8 g + 4 h + 0..3 of
+// the lane's row (lanes r and r + 32 hold one row). permlane32_swap pairs groups g, g + 1 so each
+// lane stores 16 contiguous bytes. Every lane must execute it: `ok` only gates the stores.
+__device__ __forceinline__ void store_row(uint16_t* row, const f32x16 (&o)[2], float sc, int h,
+                                          bool ok) {
+#pragma unroll
+  for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+    for (int g = 0; g < 4; g += 2) {
+      uint32_t a0 = pk_bf16(o[dt][4 * g] * sc, o[dt][4 * g + 1] * sc);
+      uint32_t a1 = pk_bf16(o[dt][4 * g + 2] * sc, o[dt][4 * g + 3] * sc);
+      uint32_t b0 = pk_bf16(o[dt][4 * g + 4] * sc, o[dt][4 * g + 5] * sc);
+      uint32_t b1 = pk_bf16(o[dt][4 * g + 6] * sc, o[dt][4 * g + 7] * sc);
+      const auto x = __builtin_amdgcn_permlane32_swap(a0, b0, false, false);
+      const auto y = __builtin_amdgcn_permlane32_swap(a1, b1, false, false);
+      a0 = x[0]; b0 = x[1];
+      a1 = y[0]; b1 = y[1];
+      if (ok) *reinterpret_cast<uint4*>(row + 32 * dt + 8 * g + 8 * h) = make_uint4(a0, a1, b0, b1);
+    }
+}
+
+// rows [row0, row0 + 128) of a [S][ld] bf16 tensor's 64 columns at g (rows past S clamped to
+// S - 1) into an image: 16 LDS-DMA wave-instructions of 8 rows x 128 B, wave w issues w, w + 4, ..
+__device__ __forceinline__ void stage(const uint16_t* g, int64_t ld, int row0, int S, char* img,
+                                      int w, int lane) {
+#pragma unroll
+  for (int s = 0; s < kBK / 8 / 4; ++s) {
+    const int i = w + 4 * s;
+    const int row = 8 * i + (lane >> 3);
+    const int ch = (lane & 7) ^ swz_f(row);
+    int gr = row0 + row;
+    gr = gr < S ? gr : S - 1;
+    __builtin_amdgcn_global_load_lds((g_void*)(g + gr * ld + 8 * ch), (lds_void*)(img + 1024 * i),
+                                     16, 0, 0);
+  }
+}
+
+// workgroup id -> (row block, batch * head): ids sharing an XCD (id % 8) take a contiguous head
+// range; blocks in decreasing (heavy_last) or increasing order of causal work
+__device__ __forceinline__ void work_item(int nblk, int BH, bool heavy_last, int& blk, int& bh) {
+  const int id = blockIdx.x;
+  int slot, hb;
+  if ((BH & 7) == 0) {
+    const int hp = BH >> 3;
+    slot = (id >> 3) / hp;
+    hb = (id & 7) * hp + (id >> 3) % hp;
+  } else {
+    slot = id / BH;
+    hb = id % BH;
+  }
+  blk = heavy_last ? nblk - 1 - slot : slot;
+  bh = hb;
+}
+
+// ------------------------------------------------------------------------------------- forward
+template <bool CAUSAL, int NQ>
+__global__ __launch_bounds__(kThreads, 2) void f64_fwd_kernel(F64Args a) {
+  constexpr int BQ = 128 * NQ;
+  extern __shared__ __attribute__((aligned(16))) char smem[];   // 2 x (K image, V image)
+  const int lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
+  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int S = a.S, H = a.H;
+  int qb, bh;
+  work_item((S + BQ - 1) / BQ, a.B * H, CAUSAL, qb, bh);
+  const int b = bh / H, hh = bh - b * H;
+  const int64_t ld = 3LL * H * kD;
+  const uint16_t* base = a.qkv + static_cast<int64_t>(b) * S * ld;
+  const uint16_t* kg = base + (H + hh) * kD;
+  const uint16_t* vg = base + (2 * H + hh) * kD;
+  const int q0 = qb * BQ, qmin = q0 + 32 * NQ * w;
+  const int kend = CAUSAL ? min(S, q0 + BQ) : S;
+  const int nt = (kend + kBK - 1) / kBK;
+
+  stage(kg, ld, 0, S, smem, w, lane);
+  stage(vg, ld, 0, S, smem + kImg, w, lane);
+  bf16x8_t qf[NQ][4];   // B operand of S^T = K Q^T: Q[qrow][16 ks + 8 h + j]
+#pragma unroll
+  for (int n = 0; n < NQ; ++n) {
+    const uint16_t* qp = base + min(qmin + 32 * n + r, S - 1) * ld + hh * kD + 8 * h;
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) qf[n][ks] = *reinterpret_cast<const bf16x8_t*>(qp + 16 * ks);
+  }
+  f32x16 o[NQ][2];
+  float m[NQ], l[NQ];
+#pragma unroll
+  for (int n = 0; n < NQ; ++n) {
+    o[n][0] = zero16();
+    o[n][1] = zero16();
+    m[n] = -INFINITY;
+    l[n] = 0.f;
+  }
+  for (int t = 0; t < nt; ++t) {
+    const char* kimg = smem + (t & 1) * 2 * kImg;
+    const char* vimg = kimg + kImg;
+    // tile t landed (this wave's DMAs: a barrier does not wait for global_load_lds), then every
+    // wave's; every wave is done with tile t - 1's buffer
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (t + 1 < nt) {
+      char* nb = smem + ((t + 1) & 1) * 2 * kImg;
+      stage(kg, ld, (t + 1) * kBK, S, nb, w, lane);
+      stage(vg, ld, (t + 1) * kBK, S, nb + kImg, w, lane);
+    }
+#pragma unroll
+    for (int hf = 0; hf < 2; ++hf) {
+      const int k0 = t * kBK + 64 * hf;
+      // no key of the half is visible to any query of the wave (never the first half: key 0 is)
+      if (k0 >= S || (CAUSAL && k0 > qmin + 32 * NQ - 1)) continue;
+      // S^T: s[n][0] = keys k0 + 0..31, s[n][1] = keys k0 + 32..63 (rows), query of the lane
+      f32x16 s[NQ][2];
+#pragma unroll
+      for (int n = 0; n < NQ; ++n) s[n][0] = s[n][1] = zero16();
+#pragma unroll
+      for (int ks = 0; ks < 4; ++ks) {
+        const bf16x8_t ka = rowfrag(kimg, 64 * hf + r, 2 * ks + h);
+        const bf16x8_t kb = rowfrag(kimg, 64 * hf + 32 + r, 2 * ks + h);
+#pragma unroll
+        for (int n = 0; n < NQ; ++n) {
+          s[n][0] = mfma(ka, qf[n][ks], s[n][0]);
+          s[n][1] = mfma(kb, qf[n][ks], s[n][1]);
+        }
+      }
+#pragma unroll
+      for (int n = 0; n < NQ; ++n) {
+        const int qlo = qmin + 32 * n, qrow = qlo + r;
+        if (CAUSAL ? (k0 + 63 > qlo) : (k0 + 64 > S)) {
+#pragma unroll
+          for (int i = 0; i < 16; ++i) {
+            const int key = k0 + acc_row(i, h);
+            if ((CAUSAL && key > qrow) || key >= S) s[n][0][i] = -INFINITY;
+            if ((CAUSAL && key + 32 > qrow) || key + 32 >= S) s[n][1][i] = -INFINITY;
+          }
+        }
+        float mt = -INFINITY;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) mt = fmaxf(mt, fmaxf(s[n][0][i], s[n][1][i]));
+        mt = fmaxf(mt, __shfl_xor(mt, 32, 64)) * a.c;
+        // deferred rescale: the running max moves (and O, l are rescaled) only when some row's
+        // tile max exceeds it by more than thr, so exponentiated scores stay <= 2^thr; the first
+        // half always sets m (finite from then on: key 0 is visible to every query). A half that
+        // is fully masked for this 32-query group has mt = -inf and changes nothing.
+        if (__any(mt > m[n] + a.thr)) {
+          const float mn = fmaxf(m[n], mt);
+          const float alpha = fexp2(m[n] - mn);
+          m[n] = mn;
+          l[n] *= alpha;
+#pragma unroll
+          for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+            for (int i = 0; i < 16; ++i) o[n][dt][i] *= alpha;
+        }
+        float ls = 0.f;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+          s[n][0][i] = fexp2(fmaf(s[n][0][i], a.c, -m[n]));
+          s[n][1][i] = fexp2(fmaf(s[n][1][i], a.c, -m[n]));
+          ls += s[n][0][i] + s[n][1][i];
+        }
+        l[n] += ls;
+      }
+      // O^T += V^T P^T over the 64 keys (4 k-steps of 16); each V^T fragment feeds NQ MFMAs
+#pragma unroll
+      for (int u = 0; u < 2; ++u) {
+        const int ka = 64 * hf + 16 * u + 4 * h;
+        bf16x8_t pf[NQ][2];
+#pragma unroll
+        for (int n = 0; n < NQ; ++n) {
+          pf[n][0] = acc_frag(s[n][0], u);
+          pf[n][1] = acc_frag(s[n][1], u);
+        }
+#pragma unroll
+        for (int dt = 0; dt < 2; ++dt) {
+          const bf16x8_t v0 = trfrag(vimg, ka, ka + 8, 32 * dt, lane);
+          const bf16x8_t v1 = trfrag(vimg, 32 + ka, 40 + ka, 32 * dt, lane);
+#pragma unroll
+          for (int n = 0; n < NQ; ++n) {
+            o[n][dt] = mfma(v0, pf[n][0], o[n][dt]);
+            o[n][dt] = mfma(v1, pf[n][1], o[n][dt]);
+          }
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int n = 0; n < NQ; ++n) {
+    const int qrow = qmin + 32 * n + r;
+    const float lt = l[n] + __shfl_xor(l[n], 32, 64);
+    store_row(a.out + ((static_cast<int64_t>(b) * S + min(qrow, S - 1)) * H + hh) * kD, o[n],
+              1.f / lt, h, qrow < S);
+    if (h == 0 && qrow < S) a.lse[static_cast<int64_t>(bh) * S + qrow] = m[n] + __log2f(lt);
+  }
+}
+
+// ------------------------------------------------------------------------------ backward: dQ
+template <bool CAUSAL>
+__global__ __launch_bounds__(kThreads, 2) void f64_dq_kernel(F64Args a) {
+  constexpr int BQ = 128;
+  extern __shared__ __attribute__((aligned(16))) char smem[];   // 2 x (K image, V image)
+  const int lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
+  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int S = a.S, H = a.H;
+  int qb, bh;
+  work_item((S + BQ - 1) / BQ, a.B * H, CAUSAL, qb, bh);
+  const int b = bh / H, hh = bh - b * H;
+  const int64_t ld = 3LL * H * kD;
+  const uint16_t* base = a.qkv + static_cast<int64_t>(b) * S * ld;
+  const uint16_t* kg = base + (H + hh) * kD;
+  const uint16_t* vg = base + (2 * H + hh) * kD;
+  const int q0 = qb * BQ, qmin = q0 + 32 * w, qrow = qmin + r;
+  const int qc = min(qrow, S - 1);
+  const int kend = CAUSAL ? min(S, q0 + BQ) : S;
+  const int nt = (kend + kBK - 1) / kBK;
+
+  stage(kg, ld, 0, S, smem, w, lane);
+  stage(vg, ld, 0, S, smem + kImg, w, lane);
+  bf16x8_t qf[4], df[4];
+  float dsum;
+  {
+    const uint16_t* qp = base + qc * ld + hh * kD + 8 * h;
+    const int64_t orow = ((static_cast<int64_t>(b) * S + qc) * H + hh) * kD + 8 * h;
+    const uint16_t* dp = a.dout + orow;
+    const uint16_t* op = a.o + orow;
+    float part = 0.f;
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) {
+      qf[ks] = *reinterpret_cast<const bf16x8_t*>(qp + 16 * ks);
+      const uint4 dv = *reinterpret_cast<const uint4*>(dp + 16 * ks);
+      const uint4 ov = *reinterpret_cast<const uint4*>(op + 16 * ks);
+      df[ks] = __builtin_bit_cast(bf16x8_t, dv);
+      const uint32_t d4[4] = {dv.x, dv.y, dv.z, dv.w}, o4[4] = {ov.x, ov.y, ov.z, ov.w};
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        part = fmaf(__uint_as_float(d4[e] << 16), __uint_as_float(o4[e] << 16), part);
+        part = fmaf(__uint_as_float(d4[e] & 0xffff0000u), __uint_as_float(o4[e] & 0xffff0000u), part);
+      }
+    }
+    dsum = part + __shfl_xor(part, 32, 64);
+    if (h == 0 && qrow < S) a.dsum[static_cast<int64_t>(bh) * S + qrow] = dsum;
+  }
+  const float lse = a.lse[static_cast<int64_t>(bh) * S + qc];
+  f32x16 dq[2] = {zero16(), zero16()};
+  for (int t = 0; t < nt; ++t) {
+    const char* kimg = smem + (t & 1) * 2 * kImg;
+    const char* vimg = kimg + kImg;
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // tile t landed (see f64_fwd_kernel)
+    __syncthreads();
+    if (t + 1 < nt) {
+      char* nb = smem + ((t + 1) & 1) * 2 * kImg;
+      stage(kg, ld, (t + 1) * kBK, S, nb, w, lane);
+      stage(vg, ld, (t + 1) * kBK, S, nb + kImg, w, lane);
+    }
+#pragma unroll
+    for (int hf = 0; hf < 2; ++hf) {
+      const int k0 = t * kBK + 64 * hf;
+      if (k0 >= S || (CAUSAL && k0 > qmin + 31)) continue;
+      f32x16 s0 = zero16(), s1 = zero16(), p0 = zero16(), p1 = zero16();
+#pragma unroll
+      for (int ks = 0; ks < 4; ++ks) {
+        s0 = mfma(rowfrag(kimg, 64 * hf + r, 2 * ks + h), qf[ks], s0);
+        s1 = mfma(rowfrag(kimg, 64 * hf + 32 + r, 2 * ks + h), qf[ks], s1);
+        p0 = mfma(rowfrag(vimg, 64 * hf + r, 2 * ks + h), df[ks], p0);
+        p1 = mfma(rowfrag(vimg, 64 * hf + 32 + r, 2 * ks + h), df[ks], p1);
+      }
+      const bool edge = CAUSAL ? (k0 + 63 > qmin) : (k0 + 64 > S);
+#pragma unroll
+      for (int i = 0; i < 16; ++i) {
+        float e0 = fexp2(fmaf(s0[i], a.c, -lse)), e1 = fexp2(fmaf(s1[i], a.c, -lse));
+        if (edge) {
+          const int key = k0 + acc_row(i, h);
+          if ((CAUSAL && key > qrow) || key >= S) e0 = 0.f;
+          if ((CAUSAL && key + 32 > qrow) || key + 32 >= S) e1 = 0.f;
+        }
+        s0[i] = e0 * (p0[i] - dsum);   // dS^T
+        s1[i] = e1 * (p1[i] - dsum);
+      }
+      // dQ^T += K^T dS^T (K^T by transposed reads of the K rows)
+#pragma unroll
+      for (int u = 0; u < 2; ++u) {
+        const bf16x8_t d0 = acc_frag(s0, u), d1 = acc_frag(s1, u);
+        const int ka = 64 * hf + 16 * u + 4 * h;
+#pragma unroll
+        for (int dt = 0; dt < 2; ++dt) {
+          dq[dt] = mfma(trfrag(kimg, ka, ka + 8, 32 * dt, lane), d0, dq[dt]);
+          dq[dt] = mfma(trfrag(kimg, 32 + ka, 40 + ka, 32 * dt, lane), d1, dq[dt]);
+        }
+      }
+    }
+  }
+  store_row(a.out + (static_cast<int64_t>(b) * S + qc) * ld + hh * kD, dq, a.scale, h, qrow < S);
+}
+
+// --------------------------------------------------------------------------- backward: dK, dV
+// 4 waves x 32 keys; the lane's K and V rows in registers (B operands of S = Q K^T and
+// dP = dO V^T), Q / dO tiles of 128 queries with their lse / D in LDS.
+template <bool CAUSAL>
+__global__ __launch_bounds__(kThreads, 2) void f64_dkdv_kernel(F64Args a) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
+  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int S = a.S, H = a.H;
+  int kb, bh;
+  work_item((S + kBK - 1) / kBK, a.B * H, false, kb, bh);
+  const int b = bh / H, hh = bh - b * H;
+  const int64_t ld = 3LL * H * kD, ld_o = static_cast<int64_t>(H) * kD;
+  const uint16_t* base = a.qkv + static_cast<int64_t>(b) * S * ld;
+  const uint16_t* qg = base + hh * kD;
+  const uint16_t* dog = a.dout + static_cast<int64_t>(b) * S * ld_o + hh * kD;
+  const float* lseg = a.lse + static_cast<int64_t>(bh) * S;
+  const float* dsg = a.dsum + static_cast<int64_t>(bh) * S;
+  const int kb0 = kb * kBK, kmin = kb0 + 32 * w, key = kmin + r;
+  const int kc = min(key, S - 1);
+  const int qstart = CAUSAL ? kb0 : 0;
+  const int nt = (S - qstart + kBK - 1) / kBK;
+
+  auto stage_all = [&](int t, char* buf) {
+    const int row0 = qstart + t * kBK;
+    stage(qg, ld, row0, S, buf, w, lane);
+    stage(dog, ld_o, row0, S, buf + kImg, w, lane);
+    // lse (waves 0, 1) / D (waves 2, 3) of the tile's 128 queries: one 4-B DMA per lane
+    const float* src = (w < 2 ? lseg : dsg) + min(row0 + 64 * (w & 1) + lane, S - 1);
+    __builtin_amdgcn_global_load_lds((g_void*)src, (lds_void*)(buf + 2 * kImg + 256 * w), 4, 0, 0);
+  };
+  stage_all(0, smem);
+  bf16x8_t kf[4], vf[4];   // B operands K^T / V^T [d][key] = this lane's key rows
+  {
+    const uint16_t* kp = base + kc * ld + (H + hh) * kD + 8 * h;
+    const uint16_t* vp = kp + H * kD;
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) {
+      kf[ks] = *reinterpret_cast<const bf16x8_t*>(kp + 16 * ks);
+      vf[ks] = *reinterpret_cast<const bf16x8_t*>(vp + 16 * ks);
+    }
+  }
+  f32x16 dk[2] = {zero16(), zero16()};
+  f32x16 dv[2] = {zero16(), zero16()};
+  for (int t = 0; t < nt; ++t) {
+    const char* qimg = smem + (t & 1) * kKVBuf;
+    const char* dimg = qimg + kImg;
+    const float* lsel = reinterpret_cast<const float*>(qimg + 2 * kImg);
+    const float* dsl = lsel + 128;
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // tile t landed (see f64_fwd_kernel)
+    __syncthreads();
+    if (t + 1 < nt) stage_all(t + 1, smem + ((t + 1) & 1) * kKVBuf);
+    const int q0 = qstart + t * kBK;
+#pragma unroll 1
+    for (int qs = 0; qs < 4; ++qs) {
+      const int qq0 = q0 + 32 * qs;
+      // no query of the sub-tile sees a key of the wave: past S, or (causal) all before them
+      if (qq0 >= S || (CAUSAL && qq0 + 31 < kmin)) continue;
+      f32x16 s = zero16(), dp = zero16();
+#pragma unroll
+      for (int ks = 0; ks < 4; ++ks) {
+        s = mfma(rowfrag(qimg, 32 * qs + r, 2 * ks + h), kf[ks], s);
+        dp = mfma(rowfrag(dimg, 32 * qs + r, 2 * ks + h), vf[ks], dp);
+      }
+      // s[i] = S[query qq0 + acc_row(i, h)][key]; registers 4g..4g+3: 4 consecutive queries
+      const bool edge = (CAUSAL && qq0 < kmin + 31) || qq0 + 32 > S;
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const int ql = 32 * qs + 8 * g + 4 * h;
+        const float4 L = *reinterpret_cast<const float4*>(lsel + ql);
+        const float4 Dd = *reinterpret_cast<const float4*>(dsl + ql);
+        const float Lv[4] = {L.x, L.y, L.z, L.w}, Dv[4] = {Dd.x, Dd.y, Dd.z, Dd.w};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const int i = 4 * g + e;
+          float p = fexp2(fmaf(s[i], a.c, -Lv[e]));
+          if (edge) {
+            const int qi = qq0 + 8 * g + 4 * h + e;
+            if ((CAUSAL && qi < key) || qi >= S) p = 0.f;
+          }
+          s[i] = p;
+          dp[i] = p * (dp[i] - Dv[e]);
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < 2; ++u) {
+        const bf16x8_t pb = acc_frag(s, u), sb = acc_frag(dp, u);
+        const int ka = 32 * qs + 16 * u + 4 * h;
+#pragma unroll
+        for (int dt = 0; dt < 2; ++dt) {
+          dv[dt] = mfma(trfrag(dimg, ka, ka + 8, 32 * dt, lane), pb, dv[dt]);
+          dk[dt] = mfma(trfrag(qimg, ka, ka + 8, 32 * dt, lane), sb, dk[dt]);
+        }
+      }
+    }
+  }
+  uint16_t* row = a.out + (static_cast<int64_t>(b) * S + kc) * ld + (H + hh) * kD;
+  store_row(row, dk, a.scale, h, key < S);
+  store_row(row + H * kD, dv, 1.f, h, key < S);
+}
+
+typedef void (*F64Kernel)(F64Args);
+
+hipError_t launch_f64(F64Kernel kern, const F64Args& a, int smem, int rows, hipStream_t st) {
+  // dynamic LDS at / above the default limit: set once per kernel
+  static const void* done[16] = {};
+  const void* f = reinterpret_cast<const void*>(kern);
+  bool set = false;
+  for (const void* d : done) set = set || d == f;
+  if (!set) {
+    hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
+    if (e != hipSuccess) return e;
+    for (const void*& d : done)
+      if (d == nullptr) {
+        d = f;
+        break;
+      }
+  }
+  const int nblk = (a.S + rows - 1) / rows;
+  const dim3 grid(static_cast<unsigned>(nblk * a.B * a.H));
+  kern<<<grid, kThreads, smem, st>>>(a);
+  return hipGetLastError();
+}
+
+// 32-query groups per forward wave: 2 when its grid still gives every CU >= 3 workgroups (causal:
+// >= 4) and S wastes no half block of 256 queries, else 1. Measured at 12 heads (256 CUs,
+// profiles/flash64/README.md): at 1.5-2 workgroups per CU NQ = 1 is 12-17 % faster; at 3 NQ = 2
+// is 8-13 % faster (causal: 3 % slower); at 4.5-6 NQ = 2 is 7-15 % faster (causal at 4.5: level);
+// S = 384 (a third of NQ = 2's query rows would be padding) stays 4-7 % slower at every size.
+int f64_nq(int B, int H, int S, bool causal) {
+  static const int cus = [] {
+    int dev = 0, n = 0;
+    if (hipGetDevice(&dev) != hipSuccess ||
+        hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
+      n = 256;
+    return n;
+  }();
+  const int64_t nb2 = (S + 255) / 256;
+  return nb2 * B * H >= (causal ? 4LL : 3LL) * cus && 2 * nb2 == (S + 127) / 128 ? 2 : 1;
+}
+
+bool f64_shape_ok(int B, int H, int S) {
+  return B >= 1 && H >= 1 && S >= 1 &&
+         static_cast<int64_t>((S + kBK - 1) / kBK) * B * H < (1LL << 31);
+}
+
+}  // namespace
+
+hipError_t launch_flash64_fwd(const void* qkv, void* o, float* lse, int B, int H, int S,
+                              float scale, bool causal, hipStream_t st, float rescale_thr,
+                              int nq) {
+  if (!f64_shape_ok(B, H, S) || nq < 0 || nq > 2) return hipErrorInvalidValue;
+  F64Args a{};
+  a.qkv = static_cast<const uint16_t*>(qkv);
+  a.out = static_cast<uint16_t*>(o);
+  a.lse = lse;
+  a.B = B; a.H = H; a.S = S;
+  a.scale = scale;
+  a.c = scale * 1.4426950408889634f;
+  a.thr = rescale_thr < 0.f ? 0.f : rescale_thr;
+  if ((nq ? nq : f64_nq(B, H, S, causal)) == 2)
+    return causal ? launch_f64(f64_fwd_kernel<true, 2>, a, kFwdSmem, 256, st)
+                  : launch_f64(f64_fwd_kernel<false, 2>, a, kFwdSmem, 256, st);
+  return causal ? launch_f64(f64_fwd_kernel<true, 1>, a, kFwdSmem, 128, st)
+                : launch_f64(f64_fwd_kernel<false, 1>, a, kFwdSmem, 128, st);
+}
+
+hipError_t launch_flash64_bwd(const void* qkv, const void* o, const void* dout, const float* lse,
+                              float* dsum, void* dqkv, int B, int H, int S, float scale,
+                              bool causal, hipStream_t st) {
+  if (!f64_shape_ok(B, H, S)) return hipErrorInvalidValue;
+  F64Args a{};
+  a.qkv = static_cast<const uint16_t*>(qkv);
+  a.o = static_cast<const uint16_t*>(o);
+  a.dout = static_cast<const uint16_t*>(dout);
+  a.out = static_cast<uint16_t*>(dqkv);
+  a.lse = const_cast<float*>(lse);
+  a.dsum = dsum;
+  a.B = B; a.H = H; a.S = S;
+  a.scale = scale;
+  a.c = scale * 1.4426950408889634f;
+  // dQ first: it also writes D = rowsum(dO * O), which the dK / dV kernel reads
+  hipError_t e = causal ? launch_f64(f64_dq_kernel<true>, a, kFwdSmem, 128, st)
+                        : launch_f64(f64_dq_kernel<false>, a, kFwdSmem, 128, st);
+  if (e != hipSuccess) return e;
+  return causal ? launch_f64(f64_dkdv_kernel<true>, a, kKVSmem, kBK, st)
+                : launch_f64(f64_dkdv_kernel<false>, a, kKVSmem, kBK, st);
+}
+
+}  // namespace cml

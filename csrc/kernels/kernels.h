@@ -399,6 +399,17 @@ hipError_t launch_flash_bwd(const void* q, const void* k, const void* v, const v
                             const void* dout, const float* lse, float* dsum, void* dq, void* dk,
                             void* dv, int B, int H, int KV, int S, float scale, bool causal,
                             hipStream_t stream);
+// Flash attention, head dim 64, MHA, causal or full, any S >= 1, in the fused layouts of
+// launch_attn_fwd / bwd: qkv [B, S, 3, H, 64] -> o [B, S, H * 64], lse fp32 [B, H, S] (log2
+// domain). Backward: dqkv [B, S, 3, H, 64], every element written once; dsum [B, H, S] fp32
+// scratch. csrc/kernels/flash_attn64.hip. rescale_thr as in launch_flash_fwd; nq: 32-query groups
+// per forward wave (1 | 2; 0 = chosen from the grid size).
+hipError_t launch_flash64_fwd(const void* qkv, void* o, float* lse, int B, int H, int S,
+                              float scale, bool causal, hipStream_t stream,
+                              float rescale_thr = 8.f, int nq = 0);
+hipError_t launch_flash64_bwd(const void* qkv, const void* o, const void* dout, const float* lse,
+                              float* dsum, void* dqkv, int B, int H, int S, float scale,
+                              bool causal, hipStream_t stream);
 // SwiGLU over h = [a | b] ([M, 2F]): y = silu(a) * b; backward writes dh [M, 2F].
 hipError_t launch_swiglu_fwd(const void* h, void* y, int64_t M, int F, hipStream_t stream);
 hipError_t launch_swiglu_bwd(const void* dy, const void* h, void* dh, int64_t M, int F,
