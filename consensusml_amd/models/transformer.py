@@ -1,7 +1,8 @@
 """BERT-base and Llama-3 transformer families (N12).
 
 Attention runs own MFMA kernels: BERT's short sequences ``csrc/kernels/attention.hip`` (past
-S = 128 the head-dim-64 flash kernels of ``csrc/kernels/flash_attn64.hip``), Llama's
+S = 128 the head-dim-64 flash kernels of ``csrc/kernels/flash_attn64.hip``; a batch padded to S
+with a length per sequence, ``BertMLM(ids, lens)``, runs their length variants at every S), Llama's
 causal GQA attention (head dim 128) ``csrc/kernels/flash_attn.hip`` forward and backward. The
 GEMMs are gemm.hip or hipBLASLt. Everything between them runs the hand-written HIP kernels of
 ``csrc/kernels/transformer.hip`` (``ops.transformer``) on bf16 GPU tensors:
@@ -26,6 +27,7 @@ Random-init weights (no checkpoints offline).
 from __future__ import annotations
 
 from dataclasses import dataclass
+from typing import Optional
 
 import torch
 import torch.nn as nn
@@ -59,12 +61,13 @@ class BertLayer(nn.Module):
         self.fc2 = Linear(c.ffn, c.d)
         self.ln2 = LayerNorm(c.d, eps=1e-12)
 
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
+    def forward(self, x: torch.Tensor, lens: Optional[torch.Tensor] = None) -> torch.Tensor:
         B, S, D = x.shape
         # x feeds both the QKV GEMM and the residual add of ln1 (likewise fc1 / ln2): the norm's
         # backward parks x's residual gradient on a link and the GEMM's data gradient absorbs it
         l1, l2 = ResidualLink(), ResidualLink()
-        a = fused_qkv_attention(self.qkv(x, l1), self.h, D // self.h)
+        # lens: only attention mixes tokens; the norms, the FFN and the residuals are per token
+        a = fused_qkv_attention(self.qkv(x, l1), self.h, D // self.h, lens=lens)
         _, x = add_norm(x, self.o(a), self.ln1.weight, self.ln1.bias, self.ln1.eps, l1)  # post-LN
         _, x = add_norm(x, ffn_gelu(x, self.fc1, self.fc2, l2), self.ln2.weight, self.ln2.bias,
                         self.ln2.eps, l2)
@@ -89,10 +92,10 @@ class BertMLM(nn.Module):
                 if isinstance(m, nn.Linear) and m.bias is not None:
                     nn.init.zeros_(m.bias)
 
-    def forward(self, ids: torch.Tensor) -> torch.Tensor:
+    def forward(self, ids: torch.Tensor, lens: Optional[torch.Tensor] = None) -> torch.Tensor:
         x = self.ln(bert_embed(ids, self.tok.weight, self.pos.weight, self.typ.weight))
         for l in self.layers:
-            x = l(x)
+            x = l(x, lens)
         x = self.head_ln(linear_gelu(x, self.head))
         return linear(x, self.tok.weight, self.bias, logits=True)
 

@@ -376,20 +376,21 @@ def _attn_ok(qkv: torch.Tensor, H: int, hd: int) -> bool:
 class _Flash64Fn(torch.autograd.Function):
     """Flash attention for head dim 64 on csrc/kernels/flash_attn64.hip, fused layouts on both
     sides: qkv [B, S, 3 H 64] -> o [B, S, H 64]; the backward's two kernels write every element of
-    dqkv themselves."""
+    dqkv themselves. ``lens`` (int32 [B] on the device, or None) selects the kernels' length
+    variants: rows past a sequence's length are never read and come back zero in o, lse and dqkv."""
 
     @staticmethod
-    def forward(ctx, qkv, H, causal, scale):
-        o, lse = lib().flash64_fwd(qkv, H, causal, scale)
-        ctx.save_for_backward(qkv, o, lse)
+    def forward(ctx, qkv, H, causal, scale, lens=None):
+        o, lse = lib().flash64_fwd(qkv, H, causal, scale, lens=lens)
+        ctx.save_for_backward(qkv, o, lse, lens)
         ctx.cfg = (H, causal, scale)
         return o
 
     @staticmethod
     def backward(ctx, do):
-        qkv, o, lse = ctx.saved_tensors
+        qkv, o, lse, lens = ctx.saved_tensors
         H, causal, scale = ctx.cfg
-        return lib().flash64_bwd(qkv, o, do, lse, H, causal, scale), None, None, None
+        return lib().flash64_bwd(qkv, o, do, lse, H, causal, scale, lens=lens), None, None, None, None
 
 
 def _flash64_ok(qkv: torch.Tensor, hd: int, causal: bool) -> bool:
@@ -399,18 +400,49 @@ def _flash64_ok(qkv: torch.Tensor, hd: int, causal: bool) -> bool:
             and qkv.is_contiguous() and qkv.data_ptr() % 16 == 0)
 
 
-def fused_qkv_attention(qkv: torch.Tensor, H: int, hd: int, causal: bool = False) -> torch.Tensor:
+def _lens_attention(qkv: torch.Tensor, H: int, hd: int, causal: bool,
+                    lens: torch.Tensor) -> torch.Tensor:
+    """``fused_qkv_attention`` with lengths as qkv_split + SDPA under a key-padding mask (combined
+    with the causal mask: SDPA takes ``is_causal`` or ``attn_mask``, not both), the output times
+    the row-validity mask. Padded rows of qkv are zeroed first (no gradient, no NaN from them)."""
+    B, S, _ = qkv.shape
+    pos = torch.arange(S, device=qkv.device)
+    valid = pos[None] < lens.to(qkv.device).long().clamp(1, S)[:, None]          # [B, S]
+    q, k, v = qkv_split(qkv.masked_fill(~valid[:, :, None], 0), H, H, hd)
+    mask = valid[:, None, None, :]                                               # keys
+    if causal:
+        mask = mask & (pos[None, :] <= pos[:, None])
+    o = F.scaled_dot_product_attention(q, k, v, attn_mask=mask)
+    return o.transpose(1, 2).reshape(B, S, H * hd).masked_fill(~valid[:, :, None], 0)
+
+
+def fused_qkv_attention(qkv: torch.Tensor, H: int, hd: int, causal: bool = False,
+                        lens: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Multi-head attention (full, or causal with ``causal=True``) straight from the fused
     projection ``qkv [B, S, 3 H hd]`` to ``[B, S, H hd]`` (the output projection's input layout).
     hd = 64 bf16 GPU tensors: non-causal S <= 128 (S % 32 == 0) runs csrc/kernels/attention.hip
     (one workgroup per (batch, head), exact softmax); S > 128, and causal attention at any S, run
     the flash kernels of csrc/kernels/flash_attn64.hip. Anything else splits the heads and runs
-    SDPA."""
+    SDPA.
+
+    ``lens`` (int32 ``[B]`` on qkv's device, ``1 <= lens[b] <= S``, clamped into that range): a
+    batch padded to S. Sequence b is rows ``[0, lens[b])``: a valid query attends to keys
+    ``[0, lens[b])`` (causal: ``[0, min(q + 1, lens[b]))``); the output and the gradient of qkv
+    are exactly zero on padded rows, and nothing depends on what qkv or the output gradient hold
+    there (NaN included). hd = 64 bf16 GPU tensors run the length variants of the flash kernels
+    at every S (key tiles and query blocks past a length cost no work; lens is never read on the
+    host); anything else splits the heads and runs SDPA under a key-padding mask."""
     B, S, _ = qkv.shape
+    if lens is not None:
+        if (hd == 64 and _P().flash_attn64 and _gpu_bf16(qkv) and qkv.is_contiguous()
+                and qkv.data_ptr() % 16 == 0):
+            return _Flash64Fn.apply(qkv, H, bool(causal), 1.0 / math.sqrt(hd),
+                                    lens.to(device=qkv.device, dtype=torch.int32).contiguous())
+        return _lens_attention(qkv, H, hd, bool(causal), lens)
     if not causal and _attn_ok(qkv, H, hd):
         return _AttnFn.apply(qkv, H, 1.0 / math.sqrt(hd))
     if _flash64_ok(qkv, hd, causal):
-        return _Flash64Fn.apply(qkv, H, bool(causal), 1.0 / math.sqrt(hd))
+        return _Flash64Fn.apply(qkv, H, bool(causal), 1.0 / math.sqrt(hd), None)
     q, k, v = qkv_split(qkv, H, H, hd)
     return F.scaled_dot_product_attention(q, k, v, is_causal=bool(causal)).transpose(1, 2).reshape(
         B, S, H * hd)

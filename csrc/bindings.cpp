@@ -2645,9 +2645,20 @@ void check_flash64_qkv(const Tensor& qkv, int64_t H) {
   TORCH_CHECK((reinterpret_cast<uintptr_t>(qkv.data_ptr()) & 15) == 0, "flash64: 16-B aligned qkv");
 }
 
+// lens: int32 [B] on qkv's device, rows of each sequence (the kernels clamp it into [1, S]; it is
+// never read on the host); none: every sequence is S rows
+const int* flash64_lens(const optional<Tensor>& lens, const Tensor& qkv) {
+  if (!lens.has_value()) return nullptr;
+  TORCH_CHECK(lens->scalar_type() == at::kInt && lens->dim() == 1 && lens->size(0) == qkv.size(0) &&
+                  lens->is_contiguous() && lens->device() == qkv.device(),
+              "flash64: lens must be int32 [B], contiguous, on qkv's device");
+  return lens->data_ptr<int>();
+}
+
 std::vector<Tensor> flash64_fwd(const Tensor& qkv, int64_t H, bool causal, double scale,
-                                double rescale_thr, int64_t nq) {
+                                double rescale_thr, int64_t nq, const optional<Tensor>& lens) {
   check_flash64_qkv(qkv, H);
+  const int* lp = flash64_lens(lens, qkv);
   TORCH_CHECK(nq >= 0 && nq <= 2, "flash64_fwd: nq must be 0 (auto), 1 or 2");
   const int64_t B = qkv.size(0), S = qkv.size(1);
   const c10::DeviceGuard guard(qkv.device());
@@ -2657,13 +2668,14 @@ std::vector<Tensor> flash64_fwd(const Tensor& qkv, int64_t H, bool causal, doubl
                                         static_cast<int>(B), static_cast<int>(H),
                                         static_cast<int>(S), static_cast<float>(scale), causal,
                                         cur_stream(), static_cast<float>(rescale_thr),
-                                        static_cast<int>(nq)));
+                                        static_cast<int>(nq), lp));
   return {o, lse};
 }
 
 Tensor flash64_bwd(const Tensor& qkv, const Tensor& o, const Tensor& dout_in, const Tensor& lse,
-                   int64_t H, bool causal, double scale) {
+                   int64_t H, bool causal, double scale, const optional<Tensor>& lens) {
   check_flash64_qkv(qkv, H);
+  const int* lp = flash64_lens(lens, qkv);
   const int64_t B = qkv.size(0), S = qkv.size(1);
   Tensor dout = dout_in.contiguous();
   check_bf16c(o, "o");
@@ -2684,7 +2696,7 @@ Tensor flash64_bwd(const Tensor& qkv, const Tensor& o, const Tensor& dout_in, co
                                         lse.data_ptr<float>(), dsum.data_ptr<float>(),
                                         dqkv.data_ptr(), static_cast<int>(B), static_cast<int>(H),
                                         static_cast<int>(S), static_cast<float>(scale), causal,
-                                        cur_stream()));
+                                        cur_stream(), lp));
   return dqkv;
 }
 
@@ -3381,8 +3393,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("flash_bwd", &flash_bwd, "flash attention backward (dq, per-query-head dk / dv)");
   m.def("flash64_fwd", &flash64_fwd, "flash attention forward, head dim 64, fused qkv in",
         py::arg("qkv"), py::arg("H"), py::arg("causal"), py::arg("scale"),
-        py::arg("rescale_thr") = 8.0, py::arg("nq") = 0);
-  m.def("flash64_bwd", &flash64_bwd, "flash attention backward, head dim 64, fused dqkv out");
+        py::arg("rescale_thr") = 8.0, py::arg("nq") = 0, py::arg("lens") = py::none());
+  m.def("flash64_bwd", &flash64_bwd, "flash attention backward, head dim 64, fused dqkv out",
+        py::arg("qkv"), py::arg("o"), py::arg("dout"), py::arg("lse"), py::arg("H"),
+        py::arg("causal"), py::arg("scale"), py::arg("lens") = py::none());
   m.def("swiglu_fwd", &swiglu_fwd, "silu(a) * b over [a | b]");
   m.def("swiglu_bwd", &swiglu_bwd, "SwiGLU backward");
   m.def("attn_fwd", &attn_fwd, "short-sequence MFMA attention forward (fused qkv in)");

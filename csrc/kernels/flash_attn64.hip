@@ -43,6 +43,31 @@
 // of tile t + 1 issued after the barrier of tile t. Work order: XCD-contiguous (batch, head)
 // ranges, heaviest causal blocks first; causal sub-tiles fully masked for a wave are skipped
 // wave-uniformly (barrier count uniform).
+//
+// Lengths (the VL instantiations, launched when `lens` is given; the others are the same code with
+// L = S folded in: same registers, same bits). Sequence b is rows [0, L), L = lens[b] clamped into
+// [1, S] by a scalar load per workgroup; the row stride of every tensor stays S.
+//   * no padded row is ever read: every row clamp -- the staging DMA, the lse / D DMA, the
+//     register loads of Q, dO, O, K, V rows -- is to L - 1, not S - 1. A masked key has p = 0, but
+//     0 * NaN inside the P V or dO^T P MFMA is NaN, so masking the scores alone is not enough
+//   * loop bounds come from L: kend / nt (forward, dQ) and the query-tile count (dK / dV), so tiles
+//     wholly past L are never staged and the t + 1 < nt prefetch follows; the sub-tile skips and
+//     the edge masks compare against L. Causal forward / dQ fold both masks into one bound per
+//     row, the last visible key min(row, L - 1) (this is what keeps <causal, 2, VL> at 246 VGPRs;
+//     with two compares per score it spilled 39)
+//   * a block wholly past L (query block in forward / dQ, key block in dK / dV) stores its zeros
+//     (and lse = 0 / D = 0) and returns before the first DMA and barrier: the whole workgroup
+//     takes the exit. In a partial block a wave wholly past L runs the barriers and its share of
+//     the staging but no MFMA: its visible-row bound (kvis / qvis) is 0, which the existing
+//     wave-uniform skip then tests (as a separate flag in the skip the full NQ = 2 form spilled
+//     34 VGPRs; as a bound it is 252, no scratch). Padded rows of a partial block are stored as
+//     +0 bits by store_row (lse, D: 0.f), so dqkv is still written exactly once by the kernels
+//   * the forward's first half-tile still sets the running max: L >= 1, so key 0 is visible to
+//     every query of a wave that computes at all
+//   * grid, f64_nq and work_item are those of S: the launch needs no host knowledge of lens. Dead
+//     blocks keep their place in the order (a different order was not tried)
+// VGPRs with lengths: forward 141 / 140 (NQ 1 causal / full), 246 / 252 (NQ 2), dQ 176 / 174,
+// dK / dV 207 / 207; no scratch, LDS as above, two workgroups per CU.
 #include <math.h>
 
 #include "common.h"
@@ -77,6 +102,7 @@ struct F64Args {
   float c;                // scale * log2(e)
   float scale;
   float thr;              // forward: deferred-rescale threshold (log2 units)
+  const int* lens;        // [B] rows of each sequence (VL kernels only; clamped into [1, S])
 };
 
 __device__ __forceinline__ f32x16 mfma(bf16x8_t a, bf16x8_t b, f32x16 c) {
@@ -121,9 +147,11 @@ __device__ __forceinline__ float fexp2(float x) { return __builtin_amdgcn_exp2f(
 
 // One row of 64 outputs times sc as bf16: o[dt][4g..4g+3] = elements 32 dt + 8 g + 4 h + 0..3 of
 // the lane's row (lanes r and r + 32 hold one row). permlane32_swap pairs groups g, g + 1 so each
-// lane stores 16 contiguous bytes. Every lane must execute it: `ok` only gates the stores.
+// lane stores 16 contiguous bytes. Every lane must execute it: `ok` only gates the stores. `zero`
+// (a padded row of a length-variant kernel; lanes r and r + 32 agree on it) stores +0 bits
+// whatever the accumulators hold.
 __device__ __forceinline__ void store_row(uint16_t* row, const f32x16 (&o)[2], float sc, int h,
-                                          bool ok) {
+                                          bool ok, bool zero = false) {
 #pragma unroll
   for (int dt = 0; dt < 2; ++dt)
 #pragma unroll
@@ -136,12 +164,15 @@ __device__ __forceinline__ void store_row(uint16_t* row, const f32x16 (&o)[2], f
       const auto y = __builtin_amdgcn_permlane32_swap(a1, b1, false, false);
       a0 = x[0]; b0 = x[1];
       a1 = y[0]; b1 = y[1];
-      if (ok) *reinterpret_cast<uint4*>(row + 32 * dt + 8 * g + 8 * h) = make_uint4(a0, a1, b0, b1);
+      if (ok)
+        *reinterpret_cast<uint4*>(row + 32 * dt + 8 * g + 8 * h) =
+            zero ? make_uint4(0u, 0u, 0u, 0u) : make_uint4(a0, a1, b0, b1);
     }
 }
 
 // rows [row0, row0 + 128) of a [S][ld] bf16 tensor's 64 columns at g (rows past S clamped to
-// S - 1) into an image: 16 LDS-DMA wave-instructions of 8 rows x 128 B, wave w issues w, w + 4, ..
+// S - 1; the length-variant kernels pass the sequence's length as S, so no padded row is ever
+// read) into an image: 16 LDS-DMA wave-instructions of 8 rows x 128 B, wave w issues w, w + 4, ..
 __device__ __forceinline__ void stage(const uint16_t* g, int64_t ld, int row0, int S, char* img,
                                       int w, int lane) {
 #pragma unroll
@@ -173,8 +204,28 @@ __device__ __forceinline__ void work_item(int nblk, int BH, bool heavy_last, int
   bh = hb;
 }
 
+// rows of sequence b: S, or (VL) lens[b] clamped into [1, S] -- workgroup-uniform, a scalar load
+template <bool VL>
+__device__ __forceinline__ int seq_len(const F64Args& a, int b) {
+  if constexpr (VL) return min(max(a.lens[b], 1), a.S);
+  return a.S;
+}
+// A block wholly past its sequence's length: +0 into the 64 columns at p of rows [row0, row0 +
+// rows) below S (16 B per lane and pass, a row's 128 B contiguous) and 0.f into f[row0 ..] (lse
+// or D; nullptr: none). The whole workgroup calls it and returns, before any DMA or barrier.
+__device__ __forceinline__ void zero_block(uint16_t* p, int64_t ld, int row0, int rows, int S,
+                                           float* f) {
+  for (int i = threadIdx.x; i < 8 * rows; i += kThreads) {
+    const int row = row0 + (i >> 3);
+    if (row < S) *reinterpret_cast<uint4*>(p + row * ld + 8 * (i & 7)) = make_uint4(0u, 0u, 0u, 0u);
+  }
+  if (f != nullptr)
+    for (int i = threadIdx.x; i < rows; i += kThreads)
+      if (row0 + i < S) f[row0 + i] = 0.f;
+}
+
 // ------------------------------------------------------------------------------------- forward
-template <bool CAUSAL, int NQ>
+template <bool CAUSAL, int NQ, bool VL>
 __global__ __launch_bounds__(kThreads, 2) void f64_fwd_kernel(F64Args a) {
   constexpr int BQ = 128 * NQ;
   extern __shared__ __attribute__((aligned(16))) char smem[];   // 2 x (K image, V image)
@@ -189,15 +240,23 @@ __global__ __launch_bounds__(kThreads, 2) void f64_fwd_kernel(F64Args a) {
   const uint16_t* kg = base + (H + hh) * kD;
   const uint16_t* vg = base + (2 * H + hh) * kD;
   const int q0 = qb * BQ, qmin = q0 + 32 * NQ * w;
-  const int kend = CAUSAL ? min(S, q0 + BQ) : S;
+  const int L = seq_len<VL>(a, b);   // keys and valid queries: rows [0, L)
+  if (VL && q0 >= L) {
+    zero_block(a.out + static_cast<int64_t>(b) * S * H * kD + hh * kD, static_cast<int64_t>(H) * kD,
+               q0, BQ, S, a.lse + static_cast<int64_t>(bh) * S);
+    return;
+  }
+  // keys visible to the wave: none for a partial block's wave of padded queries (no MFMA)
+  const int kvis = VL && qmin >= L ? 0 : L;
+  const int kend = CAUSAL ? min(L, q0 + BQ) : L;
   const int nt = (kend + kBK - 1) / kBK;
 
-  stage(kg, ld, 0, S, smem, w, lane);
-  stage(vg, ld, 0, S, smem + kImg, w, lane);
+  stage(kg, ld, 0, L, smem, w, lane);
+  stage(vg, ld, 0, L, smem + kImg, w, lane);
   bf16x8_t qf[NQ][4];   // B operand of S^T = K Q^T: Q[qrow][16 ks + 8 h + j]
 #pragma unroll
   for (int n = 0; n < NQ; ++n) {
-    const uint16_t* qp = base + min(qmin + 32 * n + r, S - 1) * ld + hh * kD + 8 * h;
+    const uint16_t* qp = base + min(qmin + 32 * n + r, L - 1) * ld + hh * kD + 8 * h;
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) qf[n][ks] = *reinterpret_cast<const bf16x8_t*>(qp + 16 * ks);
   }
@@ -219,14 +278,15 @@ __global__ __launch_bounds__(kThreads, 2) void f64_fwd_kernel(F64Args a) {
     __syncthreads();
     if (t + 1 < nt) {
       char* nb = smem + ((t + 1) & 1) * 2 * kImg;
-      stage(kg, ld, (t + 1) * kBK, S, nb, w, lane);
-      stage(vg, ld, (t + 1) * kBK, S, nb + kImg, w, lane);
+      stage(kg, ld, (t + 1) * kBK, L, nb, w, lane);
+      stage(vg, ld, (t + 1) * kBK, L, nb + kImg, w, lane);
     }
 #pragma unroll
     for (int hf = 0; hf < 2; ++hf) {
       const int k0 = t * kBK + 64 * hf;
-      // no key of the half is visible to any query of the wave (never the first half: key 0 is)
-      if (k0 >= S || (CAUSAL && k0 > qmin + 32 * NQ - 1)) continue;
+      // no key of the half is visible to any query of the wave (never the first half: key 0 is,
+      // unless the whole wave is padding, kvis = 0)
+      if (k0 >= kvis || (CAUSAL && k0 > qmin + 32 * NQ - 1)) continue;
       // S^T: s[n][0] = keys k0 + 0..31, s[n][1] = keys k0 + 32..63 (rows), query of the lane
       f32x16 s[NQ][2];
 #pragma unroll
@@ -243,13 +303,17 @@ __global__ __launch_bounds__(kThreads, 2) void f64_fwd_kernel(F64Args a) {
       }
 #pragma unroll
       for (int n = 0; n < NQ; ++n) {
-        const int qlo = qmin + 32 * n, qrow = qlo + r;
-        if (CAUSAL ? (k0 + 63 > qlo) : (k0 + 64 > S)) {
+        // causal with lengths: the last visible key of a row is min(row, L - 1) -- one bound for
+        // both masks; a padded query row sees keys [0, L) like row L - 1, whose Q it holds
+        const int qlo = (CAUSAL && VL) ? min(qmin + 32 * n, L - 1) : qmin + 32 * n;
+        const int qrow = (CAUSAL && VL) ? min(qmin + 32 * n + r, L - 1) : qmin + 32 * n + r;
+        if (CAUSAL ? (k0 + 63 > qlo) : (k0 + 64 > L)) {
 #pragma unroll
           for (int i = 0; i < 16; ++i) {
             const int key = k0 + acc_row(i, h);
-            if ((CAUSAL && key > qrow) || key >= S) s[n][0][i] = -INFINITY;
-            if ((CAUSAL && key + 32 > qrow) || key + 32 >= S) s[n][1][i] = -INFINITY;
+            constexpr bool kOne = CAUSAL && VL;   // qrow < L already
+            if ((CAUSAL && key > qrow) || (!kOne && key >= L)) s[n][0][i] = -INFINITY;
+            if ((CAUSAL && key + 32 > qrow) || (!kOne && key + 32 >= L)) s[n][1][i] = -INFINITY;
           }
         }
         float mt = -INFINITY;
@@ -258,8 +322,9 @@ __global__ __launch_bounds__(kThreads, 2) void f64_fwd_kernel(F64Args a) {
         mt = fmaxf(mt, __shfl_xor(mt, 32, 64)) * a.c;
         // deferred rescale: the running max moves (and O, l are rescaled) only when some row's
         // tile max exceeds it by more than thr, so exponentiated scores stay <= 2^thr; the first
-        // half always sets m (finite from then on: key 0 is visible to every query). A half that
-        // is fully masked for this 32-query group has mt = -inf and changes nothing.
+        // half always sets m (finite from then on: key 0 is visible to every query -- with
+        // lengths too, since L >= 1 after the clamp and a wave that gets here has qmin < L). A
+        // half that is fully masked for this 32-query group has mt = -inf and changes nothing.
         if (__any(mt > m[n] + a.thr)) {
           const float mn = fmaxf(m[n], mt);
           const float alpha = fexp2(m[n] - mn);
@@ -306,14 +371,18 @@ __global__ __launch_bounds__(kThreads, 2) void f64_fwd_kernel(F64Args a) {
   for (int n = 0; n < NQ; ++n) {
     const int qrow = qmin + 32 * n + r;
     const float lt = l[n] + __shfl_xor(l[n], 32, 64);
+    // rows [L, S) of a partial block: +0 and lse = 0 (a dead wave's l is 0: its 1 / lt is never
+    // stored)
+    const bool pad = VL && qrow >= L;
     store_row(a.out + ((static_cast<int64_t>(b) * S + min(qrow, S - 1)) * H + hh) * kD, o[n],
-              1.f / lt, h, qrow < S);
-    if (h == 0 && qrow < S) a.lse[static_cast<int64_t>(bh) * S + qrow] = m[n] + __log2f(lt);
+              1.f / lt, h, qrow < S, pad);
+    if (h == 0 && qrow < S)
+      a.lse[static_cast<int64_t>(bh) * S + qrow] = pad ? 0.f : m[n] + __log2f(lt);
   }
 }
 
 // ------------------------------------------------------------------------------ backward: dQ
-template <bool CAUSAL>
+template <bool CAUSAL, bool VL>
 __global__ __launch_bounds__(kThreads, 2) void f64_dq_kernel(F64Args a) {
   constexpr int BQ = 128;
   extern __shared__ __attribute__((aligned(16))) char smem[];   // 2 x (K image, V image)
@@ -328,12 +397,20 @@ __global__ __launch_bounds__(kThreads, 2) void f64_dq_kernel(F64Args a) {
   const uint16_t* kg = base + (H + hh) * kD;
   const uint16_t* vg = base + (2 * H + hh) * kD;
   const int q0 = qb * BQ, qmin = q0 + 32 * w, qrow = qmin + r;
-  const int qc = min(qrow, S - 1);
-  const int kend = CAUSAL ? min(S, q0 + BQ) : S;
+  const int L = seq_len<VL>(a, b);
+  if (VL && q0 >= L) {
+    zero_block(a.out + static_cast<int64_t>(b) * S * ld + hh * kD, ld, q0, BQ, S,
+               a.dsum + static_cast<int64_t>(bh) * S);
+    return;
+  }
+  const int kvis = VL && qmin >= L ? 0 : L;   // as in the forward
+  const bool pad = VL && qrow >= L;
+  const int qc = min(qrow, L - 1);   // the row whose Q, dO, O and lse the lane holds
+  const int kend = CAUSAL ? min(L, q0 + BQ) : L;
   const int nt = (kend + kBK - 1) / kBK;
 
-  stage(kg, ld, 0, S, smem, w, lane);
-  stage(vg, ld, 0, S, smem + kImg, w, lane);
+  stage(kg, ld, 0, L, smem, w, lane);
+  stage(vg, ld, 0, L, smem + kImg, w, lane);
   bf16x8_t qf[4], df[4];
   float dsum;
   {
@@ -356,7 +433,7 @@ __global__ __launch_bounds__(kThreads, 2) void f64_dq_kernel(F64Args a) {
       }
     }
     dsum = part + __shfl_xor(part, 32, 64);
-    if (h == 0 && qrow < S) a.dsum[static_cast<int64_t>(bh) * S + qrow] = dsum;
+    if (h == 0 && qrow < S) a.dsum[static_cast<int64_t>(bh) * S + qrow] = pad ? 0.f : dsum;
   }
   const float lse = a.lse[static_cast<int64_t>(bh) * S + qc];
   f32x16 dq[2] = {zero16(), zero16()};
@@ -367,13 +444,13 @@ __global__ __launch_bounds__(kThreads, 2) void f64_dq_kernel(F64Args a) {
     __syncthreads();
     if (t + 1 < nt) {
       char* nb = smem + ((t + 1) & 1) * 2 * kImg;
-      stage(kg, ld, (t + 1) * kBK, S, nb, w, lane);
-      stage(vg, ld, (t + 1) * kBK, S, nb + kImg, w, lane);
+      stage(kg, ld, (t + 1) * kBK, L, nb, w, lane);
+      stage(vg, ld, (t + 1) * kBK, L, nb + kImg, w, lane);
     }
 #pragma unroll
     for (int hf = 0; hf < 2; ++hf) {
       const int k0 = t * kBK + 64 * hf;
-      if (k0 >= S || (CAUSAL && k0 > qmin + 31)) continue;
+      if (k0 >= kvis || (CAUSAL && k0 > qmin + 31)) continue;
       f32x16 s0 = zero16(), s1 = zero16(), p0 = zero16(), p1 = zero16();
 #pragma unroll
       for (int ks = 0; ks < 4; ++ks) {
@@ -382,14 +459,17 @@ __global__ __launch_bounds__(kThreads, 2) void f64_dq_kernel(F64Args a) {
         p0 = mfma(rowfrag(vimg, 64 * hf + r, 2 * ks + h), df[ks], p0);
         p1 = mfma(rowfrag(vimg, 64 * hf + 32 + r, 2 * ks + h), df[ks], p1);
       }
-      const bool edge = CAUSAL ? (k0 + 63 > qmin) : (k0 + 64 > S);
+      // causal with lengths: one bound, the last visible key min(row, L - 1) = qc (see forward)
+      constexpr bool kOne = CAUSAL && VL;
+      const int qlast = kOne ? qc : qrow;
+      const bool edge = CAUSAL ? (k0 + 63 > (kOne ? min(qmin, L - 1) : qmin)) : (k0 + 64 > L);
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
         float e0 = fexp2(fmaf(s0[i], a.c, -lse)), e1 = fexp2(fmaf(s1[i], a.c, -lse));
         if (edge) {
           const int key = k0 + acc_row(i, h);
-          if ((CAUSAL && key > qrow) || key >= S) e0 = 0.f;
-          if ((CAUSAL && key + 32 > qrow) || key + 32 >= S) e1 = 0.f;
+          if ((CAUSAL && key > qlast) || (!kOne && key >= L)) e0 = 0.f;
+          if ((CAUSAL && key + 32 > qlast) || (!kOne && key + 32 >= L)) e1 = 0.f;
         }
         s0[i] = e0 * (p0[i] - dsum);   // dS^T
         s1[i] = e1 * (p1[i] - dsum);
@@ -407,13 +487,14 @@ __global__ __launch_bounds__(kThreads, 2) void f64_dq_kernel(F64Args a) {
       }
     }
   }
-  store_row(a.out + (static_cast<int64_t>(b) * S + qc) * ld + hh * kD, dq, a.scale, h, qrow < S);
+  store_row(a.out + (static_cast<int64_t>(b) * S + min(qrow, S - 1)) * ld + hh * kD, dq, a.scale, h,
+            qrow < S, pad);
 }
 
 // --------------------------------------------------------------------------- backward: dK, dV
 // 4 waves x 32 keys; the lane's K and V rows in registers (B operands of S = Q K^T and
 // dP = dO V^T), Q / dO tiles of 128 queries with their lse / D in LDS.
-template <bool CAUSAL>
+template <bool CAUSAL, bool VL>
 __global__ __launch_bounds__(kThreads, 2) void f64_dkdv_kernel(F64Args a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
@@ -429,16 +510,26 @@ __global__ __launch_bounds__(kThreads, 2) void f64_dkdv_kernel(F64Args a) {
   const float* lseg = a.lse + static_cast<int64_t>(bh) * S;
   const float* dsg = a.dsum + static_cast<int64_t>(bh) * S;
   const int kb0 = kb * kBK, kmin = kb0 + 32 * w, key = kmin + r;
-  const int kc = min(key, S - 1);
+  const int L = seq_len<VL>(a, b);   // queries and valid keys: rows [0, L)
+  if (VL && kb0 >= L) {
+    uint16_t* z = a.out + static_cast<int64_t>(b) * S * ld + (H + hh) * kD;
+    zero_block(z, ld, kb0, kBK, S, nullptr);
+    zero_block(z + H * kD, ld, kb0, kBK, S, nullptr);
+    return;
+  }
+  // queries that see a key of the wave: none for a partial block's wave of padded keys (no MFMA)
+  const int qvis = VL && kmin >= L ? 0 : L;
+  const bool pad = VL && key >= L;
+  const int kc = min(key, L - 1);
   const int qstart = CAUSAL ? kb0 : 0;
-  const int nt = (S - qstart + kBK - 1) / kBK;
+  const int nt = (L - qstart + kBK - 1) / kBK;
 
   auto stage_all = [&](int t, char* buf) {
     const int row0 = qstart + t * kBK;
-    stage(qg, ld, row0, S, buf, w, lane);
-    stage(dog, ld_o, row0, S, buf + kImg, w, lane);
+    stage(qg, ld, row0, L, buf, w, lane);
+    stage(dog, ld_o, row0, L, buf + kImg, w, lane);
     // lse (waves 0, 1) / D (waves 2, 3) of the tile's 128 queries: one 4-B DMA per lane
-    const float* src = (w < 2 ? lseg : dsg) + min(row0 + 64 * (w & 1) + lane, S - 1);
+    const float* src = (w < 2 ? lseg : dsg) + min(row0 + 64 * (w & 1) + lane, L - 1);
     __builtin_amdgcn_global_load_lds((g_void*)src, (lds_void*)(buf + 2 * kImg + 256 * w), 4, 0, 0);
   };
   stage_all(0, smem);
@@ -467,7 +558,7 @@ __global__ __launch_bounds__(kThreads, 2) void f64_dkdv_kernel(F64Args a) {
     for (int qs = 0; qs < 4; ++qs) {
       const int qq0 = q0 + 32 * qs;
       // no query of the sub-tile sees a key of the wave: past S, or (causal) all before them
-      if (qq0 >= S || (CAUSAL && qq0 + 31 < kmin)) continue;
+      if (qq0 >= qvis || (CAUSAL && qq0 + 31 < kmin)) continue;
       f32x16 s = zero16(), dp = zero16();
 #pragma unroll
       for (int ks = 0; ks < 4; ++ks) {
@@ -475,20 +566,20 @@ __global__ __launch_bounds__(kThreads, 2) void f64_dkdv_kernel(F64Args a) {
         dp = mfma(rowfrag(dimg, 32 * qs + r, 2 * ks + h), vf[ks], dp);
       }
       // s[i] = S[query qq0 + acc_row(i, h)][key]; registers 4g..4g+3: 4 consecutive queries
-      const bool edge = (CAUSAL && qq0 < kmin + 31) || qq0 + 32 > S;
+      const bool edge = (CAUSAL && qq0 < kmin + 31) || qq0 + 32 > L;
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
         const int ql = 32 * qs + 8 * g + 4 * h;
-        const float4 L = *reinterpret_cast<const float4*>(lsel + ql);
+        const float4 Ls = *reinterpret_cast<const float4*>(lsel + ql);
         const float4 Dd = *reinterpret_cast<const float4*>(dsl + ql);
-        const float Lv[4] = {L.x, L.y, L.z, L.w}, Dv[4] = {Dd.x, Dd.y, Dd.z, Dd.w};
+        const float Lv[4] = {Ls.x, Ls.y, Ls.z, Ls.w}, Dv[4] = {Dd.x, Dd.y, Dd.z, Dd.w};
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           const int i = 4 * g + e;
           float p = fexp2(fmaf(s[i], a.c, -Lv[e]));
           if (edge) {
             const int qi = qq0 + 8 * g + 4 * h + e;
-            if ((CAUSAL && qi < key) || qi >= S) p = 0.f;
+            if ((CAUSAL && qi < key) || qi >= L) p = 0.f;
           }
           s[i] = p;
           dp[i] = p * (dp[i] - Dv[e]);
@@ -506,15 +597,17 @@ __global__ __launch_bounds__(kThreads, 2) void f64_dkdv_kernel(F64Args a) {
       }
     }
   }
-  uint16_t* row = a.out + (static_cast<int64_t>(b) * S + kc) * ld + (H + hh) * kD;
-  store_row(row, dk, a.scale, h, key < S);
-  store_row(row + H * kD, dv, 1.f, h, key < S);
+  uint16_t* row = a.out + (static_cast<int64_t>(b) * S + min(key, S - 1)) * ld + (H + hh) * kD;
+  store_row(row, dk, a.scale, h, key < S, pad);
+  store_row(row + H * kD, dv, 1.f, h, key < S, pad);
 }
 
 typedef void (*F64Kernel)(F64Args);
 
 hipError_t launch_f64(F64Kernel kern, const F64Args& a, int smem, int rows, hipStream_t st) {
-  // dynamic LDS at / above the default limit: set once per kernel
+  // dynamic LDS at / above the default limit: set once per kernel. One slot per instantiation
+  // this file launches: forward {causal, full} x {NQ 1, 2}, dQ and dK / dV {causal, full}, each
+  // with and without lengths (8 + 8); a 17th would just set its attribute on every launch.
   static const void* done[16] = {};
   const void* f = reinterpret_cast<const void*>(kern);
   bool set = false;
@@ -560,7 +653,7 @@ bool f64_shape_ok(int B, int H, int S) {
 
 hipError_t launch_flash64_fwd(const void* qkv, void* o, float* lse, int B, int H, int S,
                               float scale, bool causal, hipStream_t st, float rescale_thr,
-                              int nq) {
+                              int nq, const int* lens) {
   if (!f64_shape_ok(B, H, S) || nq < 0 || nq > 2) return hipErrorInvalidValue;
   F64Args a{};
   a.qkv = static_cast<const uint16_t*>(qkv);
@@ -570,16 +663,26 @@ hipError_t launch_flash64_fwd(const void* qkv, void* o, float* lse, int B, int H
   a.scale = scale;
   a.c = scale * 1.4426950408889634f;
   a.thr = rescale_thr < 0.f ? 0.f : rescale_thr;
-  if ((nq ? nq : f64_nq(B, H, S, causal)) == 2)
-    return causal ? launch_f64(f64_fwd_kernel<true, 2>, a, kFwdSmem, 256, st)
-                  : launch_f64(f64_fwd_kernel<false, 2>, a, kFwdSmem, 256, st);
-  return causal ? launch_f64(f64_fwd_kernel<true, 1>, a, kFwdSmem, 128, st)
-                : launch_f64(f64_fwd_kernel<false, 1>, a, kFwdSmem, 128, st);
+  a.lens = lens;
+  // the grid and the pick of NQ come from S with or without lengths: the host never reads lens
+  const bool two = (nq ? nq : f64_nq(B, H, S, causal)) == 2;
+  if (lens != nullptr) {
+    if (two)
+      return causal ? launch_f64(f64_fwd_kernel<true, 2, true>, a, kFwdSmem, 256, st)
+                    : launch_f64(f64_fwd_kernel<false, 2, true>, a, kFwdSmem, 256, st);
+    return causal ? launch_f64(f64_fwd_kernel<true, 1, true>, a, kFwdSmem, 128, st)
+                  : launch_f64(f64_fwd_kernel<false, 1, true>, a, kFwdSmem, 128, st);
+  }
+  if (two)
+    return causal ? launch_f64(f64_fwd_kernel<true, 2, false>, a, kFwdSmem, 256, st)
+                  : launch_f64(f64_fwd_kernel<false, 2, false>, a, kFwdSmem, 256, st);
+  return causal ? launch_f64(f64_fwd_kernel<true, 1, false>, a, kFwdSmem, 128, st)
+                : launch_f64(f64_fwd_kernel<false, 1, false>, a, kFwdSmem, 128, st);
 }
 
 hipError_t launch_flash64_bwd(const void* qkv, const void* o, const void* dout, const float* lse,
                               float* dsum, void* dqkv, int B, int H, int S, float scale,
-                              bool causal, hipStream_t st) {
+                              bool causal, hipStream_t st, const int* lens) {
   if (!f64_shape_ok(B, H, S)) return hipErrorInvalidValue;
   F64Args a{};
   a.qkv = static_cast<const uint16_t*>(qkv);
@@ -591,12 +694,20 @@ hipError_t launch_flash64_bwd(const void* qkv, const void* o, const void* dout, 
   a.B = B; a.H = H; a.S = S;
   a.scale = scale;
   a.c = scale * 1.4426950408889634f;
+  a.lens = lens;
   // dQ first: it also writes D = rowsum(dO * O), which the dK / dV kernel reads
-  hipError_t e = causal ? launch_f64(f64_dq_kernel<true>, a, kFwdSmem, 128, st)
-                        : launch_f64(f64_dq_kernel<false>, a, kFwdSmem, 128, st);
+  if (lens != nullptr) {
+    hipError_t e = causal ? launch_f64(f64_dq_kernel<true, true>, a, kFwdSmem, 128, st)
+                          : launch_f64(f64_dq_kernel<false, true>, a, kFwdSmem, 128, st);
+    if (e != hipSuccess) return e;
+    return causal ? launch_f64(f64_dkdv_kernel<true, true>, a, kKVSmem, kBK, st)
+                  : launch_f64(f64_dkdv_kernel<false, true>, a, kKVSmem, kBK, st);
+  }
+  hipError_t e = causal ? launch_f64(f64_dq_kernel<true, false>, a, kFwdSmem, 128, st)
+                        : launch_f64(f64_dq_kernel<false, false>, a, kFwdSmem, 128, st);
   if (e != hipSuccess) return e;
-  return causal ? launch_f64(f64_dkdv_kernel<true>, a, kKVSmem, kBK, st)
-                : launch_f64(f64_dkdv_kernel<false>, a, kKVSmem, kBK, st);
+  return causal ? launch_f64(f64_dkdv_kernel<true, false>, a, kKVSmem, kBK, st)
+                : launch_f64(f64_dkdv_kernel<false, false>, a, kKVSmem, kBK, st);
 }
 
 }  // namespace cml

@@ -403,13 +403,16 @@ hipError_t launch_flash_bwd(const void* q, const void* k, const void* v, const v
 // launch_attn_fwd / bwd: qkv [B, S, 3, H, 64] -> o [B, S, H * 64], lse fp32 [B, H, S] (log2
 // domain). Backward: dqkv [B, S, 3, H, 64], every element written once; dsum [B, H, S] fp32
 // scratch. csrc/kernels/flash_attn64.hip. rescale_thr as in launch_flash_fwd; nq: 32-query groups
-// per forward wave (1 | 2; 0 = chosen from the grid size).
+// per forward wave (1 | 2; 0 = chosen from the grid size). lens: device int32 [B], sequence b is
+// rows [0, lens[b]) of its batch entry (clamped into [1, S] by the kernels, never read on the
+// host); o / lse / dqkv / dsum are zero on the padded rows and nothing depends on what qkv, o or
+// dout hold there. nullptr: every sequence is S rows (the kernels without the length variant).
 hipError_t launch_flash64_fwd(const void* qkv, void* o, float* lse, int B, int H, int S,
                               float scale, bool causal, hipStream_t stream,
-                              float rescale_thr = 8.f, int nq = 0);
+                              float rescale_thr = 8.f, int nq = 0, const int* lens = nullptr);
 hipError_t launch_flash64_bwd(const void* qkv, const void* o, const void* dout, const float* lse,
                               float* dsum, void* dqkv, int B, int H, int S, float scale,
-                              bool causal, hipStream_t stream);
+                              bool causal, hipStream_t stream, const int* lens = nullptr);
 // SwiGLU over h = [a | b] ([M, 2F]): y = silu(a) * b; backward writes dh [M, 2F].
 hipError_t launch_swiglu_fwd(const void* h, void* y, int64_t M, int F, hipStream_t stream);
 hipError_t launch_swiglu_bwd(const void* dy, const void* h, void* dh, int64_t M, int F,
