@@ -31,10 +31,15 @@ CXX = os.environ.get("CXX", "g++")
 EXT_SUFFIX = sysconfig.get_config_var("EXT_SUFFIX") or ".so"
 # extra hipcc flags of single kernel sources (csrc/kernels/*.hip are all compiled; a new file
 # needs no entry). flash_attn64.hip: scalar fp32 VALU only, no packed fp32 pairs in its softmax
-# rescale and store scaling
+# rescale and store scaling; flash_attn_doc.hip (flash_attn.hip's document-masked instantiations
+# and the bounds kernel) likewise
+_NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 SRC_FLAGS = {
-    "flash_attn64.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+    "flash_attn64.hip": _NO_PK_F32,
+    "flash_attn_doc.hip": _NO_PK_F32,
 }
+# sources that include another source (besides the headers every object depends on)
+SRC_DEPS = {"flash_attn_doc.hip": ["flash_attn.hip"]}
 
 
 def _torch_paths():
@@ -85,7 +90,8 @@ def build_kernels(force: bool = False, verbose: bool = False) -> str:
     for src in sorted(glob.glob(os.path.join(CSRC, "kernels", "*.hip"))):
         obj = os.path.join(BUILD, os.path.basename(src) + ".o")
         objs.append(obj)
-        if force or _newer(obj, [src] + hdrs):
+        deps = [os.path.join(CSRC, "kernels", d) for d in SRC_DEPS.get(os.path.basename(src), [])]
+        if force or _newer(obj, [src] + deps + hdrs):
             jobs.append([HIPCC, f"--offload-arch={ARCH}", *common,
                          *SRC_FLAGS.get(os.path.basename(src), []), "-I", CSRC, "-c", src, "-o", obj])
     bsrc = os.path.join(CSRC, "bindings.cpp")

@@ -3,7 +3,9 @@
 Attention runs own MFMA kernels: BERT's short sequences ``csrc/kernels/attention.hip`` (past
 S = 128 the head-dim-64 flash kernels of ``csrc/kernels/flash_attn64.hip``; a batch padded to S
 with a length per sequence, ``BertMLM(ids, lens)``, runs their length variants at every S), Llama's
-causal GQA attention (head dim 128) ``csrc/kernels/flash_attn.hip`` forward and backward. The
+causal GQA attention (head dim 128) ``csrc/kernels/flash_attn.hip`` forward and backward (rows that
+pack several documents, ``Llama(ids, doc_ids)``, run their document-masked variants: a token
+attends only to the earlier tokens of its own document). The
 GEMMs are gemm.hip or hipBLASLt. Everything between them runs the hand-written HIP kernels of
 ``csrc/kernels/transformer.hip`` (``ops.transformer``) on bf16 GPU tensors:
   * the q / k / v projections are ONE fused GEMM. BERT's attention (S <= 128, head dim 64) runs
@@ -34,8 +36,8 @@ import torch.nn as nn
 
 from ..ops.bn import ResidualLink
 from ..ops.transformer import (LayerNorm, Linear, LinearNB, RMSNorm, add_norm, bert_embed,
-                               ffn_gelu, fused_qkv_attention, linear, linear_gelu, qkv_attention,
-                               rope_tables, swiglu)
+                               doc_bounds, ffn_gelu, fused_qkv_attention, linear, linear_gelu,
+                               qkv_attention, rope_tables, swiglu)
 
 
 # =============================================================================== BERT
@@ -126,7 +128,8 @@ class LlamaConfig:
 class LlamaBlock(nn.Module):
     """Pre-norm block. The residual add that ends a block is fused with the next norm, so a block
     takes (x, m): the residual stream before the previous block's MLP output m was added
-    (m = None for the first block), and returns its own (x, m)."""
+    (m = None for the first block), and returns its own (x, m). ``bounds``: the document bounds
+    of packed rows (``ops.transformer.doc_bounds``), None for one document per row."""
 
     def __init__(self, c: LlamaConfig):
         super().__init__()
@@ -140,10 +143,11 @@ class LlamaBlock(nn.Module):
         self.n1 = RMSNorm(c.d, c.eps)
         self.n2 = RMSNorm(c.d, c.eps)
 
-    def forward(self, x, m, cos, sin):
+    def forward(self, x, m, cos, sin, bounds=None):
         B, S, D = x.shape
         x, h = add_norm(x, m, self.n1.weight, None, self.c.eps)
-        a = qkv_attention(self.wqkv(h), self.c.heads, self.c.kv_heads, self.hd, cos, sin)
+        a = qkv_attention(self.wqkv(h), self.c.heads, self.c.kv_heads, self.hd, cos, sin,
+                          bounds=bounds)
         x, h = add_norm(x, self.wo(a), self.n2.weight, None, self.c.eps)
         return x, self.w2(swiglu(self.w13(h)))
 
@@ -161,16 +165,21 @@ class Llama(nn.Module):
             if isinstance(m, (nn.Linear, nn.Embedding)):
                 nn.init.normal_(m.weight, std=0.02)
 
-    def forward(self, ids: torch.Tensor) -> torch.Tensor:
+    def forward(self, ids: torch.Tensor, doc_ids: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """doc_ids (integer [B, S]): rows pack several documents, a document being a run of equal
+        consecutive ids; attention stays inside a document (RoPE positions stay absolute). The
+        bounds are computed once and shared by every layer."""
         B, S = ids.shape
         x = self.tok(ids)
         cos, sin = rope_tables(S, self.c.d // self.c.heads, self.c.rope_theta, ids.device)
+        bounds = None if doc_ids is None else doc_bounds(doc_ids.to(ids.device))
         m = None
         for l in self.layers:
             if self.ckpt and self.training:
-                x, m = torch.utils.checkpoint.checkpoint(l, x, m, cos, sin, use_reentrant=False)
+                x, m = torch.utils.checkpoint.checkpoint(l, x, m, cos, sin, bounds,
+                                                         use_reentrant=False)
             else:
-                x, m = l(x, m, cos, sin)
+                x, m = l(x, m, cos, sin, bounds)
         _, h = add_norm(x, m, self.norm.weight, None, self.c.eps)
         return self.out(h)
 

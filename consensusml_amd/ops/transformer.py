@@ -454,86 +454,140 @@ def _flash_ok(*ts: torch.Tensor) -> bool:
             and all(t.is_contiguous() and t.data_ptr() % 16 == 0 for t in ts))
 
 
+def doc_bounds(doc_ids: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Document bounds of packed rows. ``doc_ids`` is an integer ``[B, S]`` tensor; a document is
+    a maximal run of equal consecutive ids within a row (a repeated id later in the row starts a
+    new document; ids need not be sorted or dense). Returns int32 ``(lo, hi)`` of shape ``[B, S]``:
+    ``lo[b, s]`` is the first index of s's run and ``hi[b, s]`` one past its last, both
+    non-decreasing along s. They are the ``bounds`` of ``flash_attention`` / ``qkv_attention``:
+    query i attends to key j iff ``lo[b, i] <= j <= i`` (seen from the key: ``j <= i < hi[b, j]``).
+    GPU tensors: one launch of csrc/kernels/flash_attn_doc.hip, the ids are never read on the
+    host. Compute it once per forward and share it among the layers."""
+    if doc_ids.dim() != 2 or doc_ids.is_floating_point() or doc_ids.dtype == torch.bool:
+        raise ValueError("doc_ids must be an integer [B, S] tensor")
+    if doc_ids.is_cuda:
+        if doc_ids.dtype not in (torch.int32, torch.int64):
+            doc_ids = doc_ids.long()
+        lo, hi = lib().doc_bounds(doc_ids)
+        return lo, hi
+    B, S = doc_ids.shape
+    pos = torch.arange(S).expand(B, S)
+    cut = doc_ids[:, 1:] != doc_ids[:, :-1]                       # a run starts at s + 1
+    start = torch.cat((torch.ones(B, 1, dtype=torch.bool), cut), 1)
+    end = torch.cat((cut, torch.ones(B, 1, dtype=torch.bool)), 1)
+    lo = torch.where(start, pos, 0).cummax(1).values
+    hi = torch.where(end, pos + 1, S).flip(1).cummin(1).values.flip(1)
+    return lo.int(), hi.int()
+
+
+def _dev_bounds(bounds, causal: bool, dev: torch.device):
+    """(lo, hi) as contiguous int32 tensors on dev; (None, None) without bounds."""
+    if bounds is None:
+        return None, None
+    if not causal:
+        raise ValueError("document bounds are causal only: causal=False with bounds")
+    lo, hi = bounds
+    return (lo.to(device=dev, dtype=torch.int32).contiguous(),
+            hi.to(device=dev, dtype=torch.int32).contiguous())
+
+
 class _FlashFn(torch.autograd.Function):
     """softmax(q k^T scale [+ causal mask]) v on csrc/kernels/flash_attn.hip: q [B, H, S, 128],
     k / v [B, KV, S, 128] -> o [B, S, H * 128]. The backward's per-query-head dk / dv are summed
     over each kv head's group here (the fused QKV path, ``_RopeFlashFn``, sums them inside the RoPE
-    backward kernel instead)."""
+    backward kernel instead). lo / hi (int32 [B, S] on the device, or None) select the kernels'
+    document variants."""
 
     @staticmethod
-    def forward(ctx, q, k, v, causal, scale):
-        o, lse = lib().flash_fwd(q, k, v, causal, scale)
-        ctx.save_for_backward(q, k, v, o, lse)
+    def forward(ctx, q, k, v, causal, scale, lo=None, hi=None):
+        o, lse = lib().flash_fwd(q, k, v, causal, scale, lo=lo)
+        ctx.save_for_backward(q, k, v, o, lse, lo, hi)
         ctx.causal, ctx.scale = causal, scale
         return o
 
     @staticmethod
     def backward(ctx, do):
-        q, k, v, o, lse = ctx.saved_tensors
-        dq, dkh, dvh = lib().flash_bwd(q, k, v, o, do, lse, ctx.causal, ctx.scale)
+        q, k, v, o, lse, lo, hi = ctx.saved_tensors
+        dq, dkh, dvh = lib().flash_bwd(q, k, v, o, do, lse, ctx.causal, ctx.scale, lo=lo, hi=hi)
         B, H, S, D = q.shape
         KV = k.shape[1]
         if H != KV:
             dkh = dkh.view(B, KV, H // KV, S, D).float().sum(2).to(q.dtype)
             dvh = dvh.view(B, KV, H // KV, S, D).float().sum(2).to(q.dtype)
-        return dq, dkh, dvh, None, None
+        return dq, dkh, dvh, None, None, None, None
 
 
-def _sdpa_rows(q, k, v, causal: bool, scale: float) -> torch.Tensor:
-    """Reference composition of flash_attention (any device / dtype): [B, S, H * hd]."""
+def _sdpa_rows(q, k, v, causal: bool, scale: float, lo=None) -> torch.Tensor:
+    """Reference composition of flash_attention (any device / dtype): [B, S, H * hd]. lo: the
+    document mask ``lo[b, i] <= j <= i`` as a boolean attn_mask, broadcast over the heads."""
     B, H, S, hd = q.shape
-    o = F.scaled_dot_product_attention(q, k, v, is_causal=causal, scale=scale,
-                                       enable_gqa=H != k.shape[1])
+    mask = None
+    if lo is not None:
+        pos = torch.arange(S, device=q.device)
+        mask = ((lo[:, :, None] <= pos) & (pos <= pos[:, None]))[:, None]
+    o = F.scaled_dot_product_attention(q, k, v, attn_mask=mask, is_causal=causal and mask is None,
+                                       scale=scale, enable_gqa=H != k.shape[1])
     return o.transpose(1, 2).reshape(B, S, H * hd)
 
 
 def flash_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, causal: bool = True,
-                    scale: Optional[float] = None) -> torch.Tensor:
+                    scale: Optional[float] = None,
+                    bounds: Optional[Tuple[torch.Tensor, torch.Tensor]] = None) -> torch.Tensor:
     """Multi-head attention with grouped-query heads (H % KV == 0): q [B, H, S, hd], k / v
     [B, KV, S, hd] -> [B, S, H * hd] (the output projection's input rows). bf16 GPU tensors with
     hd = 128 run the flash kernels of csrc/kernels/flash_attn.hip (forward and backward);
-    anything else runs SDPA."""
+    anything else runs SDPA.
+
+    ``bounds = doc_bounds(doc_ids)``: rows are several documents packed to S tokens, and a query
+    attends only to the earlier keys of its own document (causal only: ``causal=False`` raises
+    ValueError). The kernels' document variants neither stage nor compute key tiles outside a
+    query block's documents; the SDPA path takes the same mask as a boolean ``attn_mask``."""
     hd = q.shape[-1]
     scale = float(scale) if scale is not None else 1.0 / math.sqrt(hd)
+    lo, hi = _dev_bounds(bounds, causal, q.device)
     if hd == 128 and _flash_ok(q, k, v):
-        return _FlashFn.apply(q, k, v, bool(causal), scale)
-    return _sdpa_rows(q, k, v, causal, scale)
+        return _FlashFn.apply(q, k, v, bool(causal), scale, lo, hi)
+    return _sdpa_rows(q, k, v, causal, scale, lo)
 
 
 class _RopeFlashFn(torch.autograd.Function):
     """QKV split + RoPE + flash attention from the fused projection ``qkv [B, S, (H + 2 KV) 128]``
     to ``o [B, S, H 128]``. Backward: the flash backward, then ONE RoPE-backward pass that also
     sums the per-query-head dk / dv of each kv head's group (transformer.hip rope_bwd, grp) and
-    writes dqkv in the fused layout."""
+    writes dqkv in the fused layout. lo / hi as in ``_FlashFn``."""
 
     @staticmethod
-    def forward(ctx, qkv, cos, sin, H, KV, causal, scale):
+    def forward(ctx, qkv, cos, sin, H, KV, causal, scale, lo=None, hi=None):
         q, k, v = lib().rope_fwd(qkv, cos, sin, H, KV, 128)
-        o, lse = lib().flash_fwd(q, k, v, causal, scale)
-        ctx.save_for_backward(q, k, v, o, lse, cos, sin)
+        o, lse = lib().flash_fwd(q, k, v, causal, scale, lo=lo)
+        ctx.save_for_backward(q, k, v, o, lse, cos, sin, lo, hi)
         ctx.cfg = (H, KV, causal, scale)
         return o
 
     @staticmethod
     def backward(ctx, do):
-        q, k, v, o, lse, cos, sin = ctx.saved_tensors
+        q, k, v, o, lse, cos, sin, lo, hi = ctx.saved_tensors
         H, KV, causal, scale = ctx.cfg
-        dq, dkh, dvh = lib().flash_bwd(q, k, v, o, do, lse, causal, scale)
+        dq, dkh, dvh = lib().flash_bwd(q, k, v, o, do, lse, causal, scale, lo=lo, hi=hi)
         dqkv = lib().rope_bwd(dq, dkh, dvh, cos, sin, H // KV)
-        return dqkv, None, None, None, None, None, None
+        return dqkv, None, None, None, None, None, None, None, None
 
 
 def qkv_attention(qkv: torch.Tensor, H: int, KV: int, hd: int,
                   cos: Optional[torch.Tensor] = None, sin: Optional[torch.Tensor] = None,
-                  causal: bool = True) -> torch.Tensor:
+                  causal: bool = True,
+                  bounds: Optional[Tuple[torch.Tensor, torch.Tensor]] = None) -> torch.Tensor:
     """Attention straight from the fused projection ``qkv [B, S, (H + 2 KV) hd]`` (RoPE on q / k
     when cos / sin are given) to ``[B, S, H hd]``. bf16 GPU tensors with hd = 128 run
-    ``_RopeFlashFn`` (own kernels end to end); otherwise qkv_split + SDPA."""
+    ``_RopeFlashFn`` (own kernels end to end); otherwise qkv_split + SDPA. ``bounds``: the
+    document mask of ``flash_attention`` (RoPE positions stay absolute: within a document the
+    scores depend on position differences only)."""
     scale = 1.0 / math.sqrt(hd)
+    lo, hi = _dev_bounds(bounds, causal, qkv.device)
     if hd == 128 and _flash_ok(qkv) and (cos is None or (cos.is_cuda and sin.is_cuda)):
-        return _RopeFlashFn.apply(qkv, cos, sin, H, KV, bool(causal), scale)
+        return _RopeFlashFn.apply(qkv, cos, sin, H, KV, bool(causal), scale, lo, hi)
     q, k, v = qkv_split(qkv, H, KV, hd, cos, sin)
-    return _sdpa_rows(q, k, v, causal, scale)
+    return _sdpa_rows(q, k, v, causal, scale, lo)
 
 
 # ============================================================================ SwiGLU

@@ -2591,9 +2591,20 @@ void check_flash_qkv(const Tensor& q, const Tensor& k, const Tensor& v) {
     TORCH_CHECK((reinterpret_cast<uintptr_t>(t->data_ptr()) & 15) == 0, "flash: 16-B aligned q / k / v");
 }
 
+// lo / hi: int32 [B, S] document bounds (doc_bounds) on q's device, never read on the host
+const int* flash_bound(const optional<Tensor>& t, const Tensor& q, bool causal) {
+  if (!t.has_value()) return nullptr;
+  TORCH_CHECK(causal, "flash: document bounds are causal only");
+  TORCH_CHECK(t->scalar_type() == at::kInt && t->dim() == 2 && t->size(0) == q.size(0) &&
+                  t->size(1) == q.size(2) && t->is_contiguous() && t->device() == q.device(),
+              "flash: lo / hi must be int32 [B, S], contiguous, on q's device");
+  return t->data_ptr<int>();
+}
+
 std::vector<Tensor> flash_fwd(const Tensor& q, const Tensor& k, const Tensor& v, bool causal,
-                              double scale, double rescale_thr) {
+                              double scale, double rescale_thr, const optional<Tensor>& lo) {
   check_flash_qkv(q, k, v);
+  const int* lo_p = flash_bound(lo, q, causal);
   const int64_t B = q.size(0), H = q.size(1), S = q.size(2), KV = k.size(1);
   const c10::DeviceGuard guard(q.device());
   Tensor o = at::empty({B, S, H * 128}, q.options());
@@ -2602,14 +2613,18 @@ std::vector<Tensor> flash_fwd(const Tensor& q, const Tensor& k, const Tensor& v,
                                       lse.data_ptr<float>(), static_cast<int>(B), static_cast<int>(H),
                                       static_cast<int>(KV), static_cast<int>(S),
                                       static_cast<float>(scale), causal, cur_stream(),
-                                      static_cast<float>(rescale_thr)));
+                                      static_cast<float>(rescale_thr), lo_p));
   return {o, lse};
 }
 
 // -> (dq [B, H, S, 128], dk / dv per query head [B, H, S, 128])
 std::vector<Tensor> flash_bwd(const Tensor& q, const Tensor& k, const Tensor& v, const Tensor& o,
-                              const Tensor& dout_in, const Tensor& lse, bool causal, double scale) {
+                              const Tensor& dout_in, const Tensor& lse, bool causal, double scale,
+                              const optional<Tensor>& lo, const optional<Tensor>& hi) {
   check_flash_qkv(q, k, v);
+  TORCH_CHECK(lo.has_value() == hi.has_value(), "flash_bwd: lo and hi come together");
+  const int* lo_p = flash_bound(lo, q, causal);
+  const int* hi_p = flash_bound(hi, q, causal);
   const int64_t B = q.size(0), H = q.size(1), S = q.size(2), KV = k.size(1);
   Tensor dout = dout_in.contiguous();
   check_bf16c(o, "o");
@@ -2632,8 +2647,26 @@ std::vector<Tensor> flash_bwd(const Tensor& q, const Tensor& k, const Tensor& v,
                                       dq.data_ptr(), dk.data_ptr(), dv.data_ptr(),
                                       static_cast<int>(B), static_cast<int>(H), static_cast<int>(KV),
                                       static_cast<int>(S), static_cast<float>(scale), causal,
-                                      cur_stream()));
+                                      cur_stream(), lo_p, hi_p));
   return {dq, dk, dv};
+}
+
+// doc_ids [B, S] int32 / int64 on the GPU -> (lo, hi) int32 [B, S]: the run of equal consecutive
+// ids around each token is [lo, hi). One launch; the ids are never read on the host.
+std::vector<Tensor> doc_bounds(const Tensor& ids_in) {
+  TORCH_CHECK(ids_in.is_cuda() && ids_in.dim() == 2 && ids_in.size(0) >= 1 && ids_in.size(1) >= 1 &&
+                  ids_in.size(1) < (1LL << 31) &&
+                  (ids_in.scalar_type() == at::kInt || ids_in.scalar_type() == at::kLong),
+              "doc_bounds: doc_ids must be a GPU int32 / int64 [B, S] tensor");
+  Tensor ids = ids_in.contiguous();
+  const c10::DeviceGuard guard(ids.device());
+  Tensor lo = at::empty(ids.sizes(), ids.options().dtype(at::kInt));
+  Tensor hi = at::empty_like(lo);
+  CML_CHECK_HIP(cml::launch_doc_bounds(ids.data_ptr(), static_cast<int>(ids.element_size()),
+                                       lo.data_ptr<int>(), hi.data_ptr<int>(),
+                                       static_cast<int>(ids.size(0)), static_cast<int>(ids.size(1)),
+                                       cur_stream()));
+  return {lo, hi};
 }
 
 // Flash attention, head dim 64, fused layouts (csrc/kernels/flash_attn64.hip): qkv [B, S, 3 H 64]
@@ -3389,8 +3422,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("grp") = 1);
   m.def("flash_fwd", &flash_fwd, "flash attention forward, head dim 128, GQA, causal / full",
         py::arg("q"), py::arg("k"), py::arg("v"), py::arg("causal"), py::arg("scale"),
-        py::arg("rescale_thr") = 8.0);
-  m.def("flash_bwd", &flash_bwd, "flash attention backward (dq, per-query-head dk / dv)");
+        py::arg("rescale_thr") = 8.0, py::arg("lo") = py::none());
+  m.def("flash_bwd", &flash_bwd, "flash attention backward (dq, per-query-head dk / dv)",
+        py::arg("q"), py::arg("k"), py::arg("v"), py::arg("o"), py::arg("dout"), py::arg("lse"),
+        py::arg("causal"), py::arg("scale"), py::arg("lo") = py::none(),
+        py::arg("hi") = py::none());
+  m.def("doc_bounds", &doc_bounds, "document bounds (lo, hi) of packed rows from doc ids");
   m.def("flash64_fwd", &flash64_fwd, "flash attention forward, head dim 64, fused qkv in",
         py::arg("qkv"), py::arg("H"), py::arg("causal"), py::arg("scale"),
         py::arg("rescale_thr") = 8.0, py::arg("nq") = 0, py::arg("lens") = py::none());

@@ -38,6 +38,16 @@
 // contiguous (batch, head) ranges (the 4 query heads of a kv head read its K / V from one L2),
 // heaviest causal blocks first. Causal tiles that are fully masked for a wave are skipped
 // wave-uniformly (the barrier count stays uniform).
+// Documents (DOC = true, causal only; instantiated in flash_attn_doc.hip, which also holds the
+// kernel that makes the bounds): rows pack several documents and query i attends to keys
+// lo[b, i] <= j <= i, i.e. key j is seen by queries j <= i < hi[b, j] (int32 [B, S], both
+// non-decreasing along a row). The forward and dQ start their tile loop at lo of the block's
+// first query / 64, a wave skips tiles that end before lo of its first query, and the key < lo
+// mask runs only on tiles that start before lo of the wave's last query; dK / dV end their query
+// loop at hi of the block's last key and mirror the rest with hi. Without a boundary in reach a
+// tile runs the plain instruction stream, masked elements are exact zeros, and the summation
+// order is the plain kernels': one document per row gives their bits. The work order is still
+// the causal one (heaviest block first by row index, not by document).
 //
 // Replaces ROCm SDPA's AOTriton kernels (attn_fwd / bwd_kernel_dk_dv / bwd_kernel_dq /
 // bwd_preprocess: 84 ms of the 4 x 2048 Llama-3-8B step, profiles/r04_12/llama_kernels.md).
@@ -49,6 +59,30 @@
 #include "kernels.h"
 
 namespace cml {
+
+struct FaArgs {
+  const uint16_t* q;      // [B, H, S, 128]
+  const uint16_t* k;      // [B, KV, S, 128]
+  const uint16_t* v;
+  const uint16_t* o;      // [B, S, H, 128]
+  const uint16_t* dout;   // [B, S, H, 128]
+  uint16_t* out;          // forward: o; backward: dq [B, H, S, 128]
+  uint16_t* dk;           // [B, H, S, 128]
+  uint16_t* dv;
+  float* lse;             // [B, H, S]
+  float* dsum;            // [B, H, S]
+  const int* lo;          // DOC: [B, S] first key of each query's document (forward, dQ)
+  const int* hi;          // DOC: [B, S] one past the last query of each key's document (dK dV)
+  int B, H, KV, S;
+  float c;                // scale * log2(e)
+  float scale;
+  float thr;              // forward: deferred-rescale threshold (log2 units), see fa_fwd_kernel
+};
+
+// the DOC instantiations and their launches: flash_attn_doc.hip (this file's second compilation)
+hipError_t launch_fa_doc_fwd(const FaArgs& a, hipStream_t st);
+hipError_t launch_fa_doc_bwd(const FaArgs& a, hipStream_t st);
+
 namespace {
 
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
@@ -63,23 +97,6 @@ constexpr int kBQ = 128;                // queries (forward, dQ) / keys (dK dV) 
 constexpr int kBK = 64;                 // rows per staged tile
 constexpr int kImg = kBK * 256;         // one [64][128] bf16 image: 16 KB
 constexpr int kThreads = 256;
-
-struct FaArgs {
-  const uint16_t* q;      // [B, H, S, 128]
-  const uint16_t* k;      // [B, KV, S, 128]
-  const uint16_t* v;
-  const uint16_t* o;      // [B, S, H, 128]
-  const uint16_t* dout;   // [B, S, H, 128]
-  uint16_t* out;          // forward: o; backward: dq [B, H, S, 128]
-  uint16_t* dk;           // [B, H, S, 128]
-  uint16_t* dv;
-  float* lse;             // [B, H, S]
-  float* dsum;            // [B, H, S]
-  int B, H, KV, S;
-  float c;                // scale * log2(e)
-  float scale;
-  float thr;              // forward: deferred-rescale threshold (log2 units), see fa_fwd_kernel
-};
 
 __device__ __forceinline__ f32x16 mfma(bf16x8_t a, bf16x8_t b, f32x16 c) {
   return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
@@ -117,6 +134,9 @@ __device__ __forceinline__ bf16x8_t acc_frag(const f32x16& x, int u) {
                                                  pk_bf16(x[o + 6], x[o + 7])));
 }
 __device__ __forceinline__ float fexp2(float x) { return __builtin_amdgcn_exp2f(x); }
+// DOC forward: a running max that is still -inf (no visible key yet) counts as 0 inside an exp2
+// argument, so that -inf - (-inf) never forms; a finite max passes through bit for bit
+__device__ __forceinline__ float fin(float m) { return m == -INFINITY ? 0.f : m; }
 
 // One row of 128 outputs times sc as bf16: o[dt][4g..4g+3] = elements 32 dt + 8 g + 4 h + 0..3
 // of the lane's row (lanes r and r + 32 hold one row). permlane32_swap pairs groups g, g + 1 so
@@ -177,8 +197,9 @@ __device__ __forceinline__ void work_item(int nblk, int BH, bool heavy_last, int
 // ------------------------------------------------------------------------------------- forward
 // NWV waves x 32 queries per workgroup: 4 (two workgroups per CU) or 8 (one; each staged K / V
 // tile feeds twice the queries, half the L2 -> LDS traffic per FLOP)
-template <bool CAUSAL, int NWV = 4>
+template <bool CAUSAL, int NWV = 4, bool DOC = false>
 __global__ __launch_bounds__(64 * NWV, 8 / NWV) void fa_fwd_kernel(FaArgs a) {
+  static_assert(CAUSAL || !DOC, "document bounds are causal only");
   constexpr int BQ = 32 * NWV;
   extern __shared__ __attribute__((aligned(16))) char smem[];   // 2 x (K image, V image)
   const int lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
@@ -193,9 +214,20 @@ __global__ __launch_bounds__(64 * NWV, 8 / NWV) void fa_fwd_kernel(FaArgs a) {
   const uint16_t* vg = a.v + kvoff;
   const int kend = CAUSAL ? min(S, q0 + BQ) : S;
   const int nt = (kend + kBK - 1) / kBK;
+  // DOC: lo is non-decreasing along a row, so the block's / wave's smallest bound is its first
+  // query's and the wave's largest its last query's. Tiles before the block's first visible key
+  // are neither staged nor computed (t0 keeps the buffer parity of tile t)
+  int t0 = 0, lo_row = 0, lo_first = 0, lo_last = 0;
+  if (DOC) {
+    const int* lob = a.lo + static_cast<int64_t>(b) * S;
+    t0 = max(lob[q0], 0) / kBK;
+    lo_row = lob[min(qrow, S - 1)];
+    lo_first = lob[min(qmin, S - 1)];
+    lo_last = lob[min(qmin + 31, S - 1)];
+  }
 
-  stage<NWV>(kg, kD, 0, S, smem, w, lane);
-  stage<NWV>(vg, kD, 0, S, smem + kImg, w, lane);
+  stage<NWV>(kg, kD, t0 * kBK, S, smem + (t0 & 1) * 2 * kImg, w, lane);
+  stage<NWV>(vg, kD, t0 * kBK, S, smem + (t0 & 1) * 2 * kImg + kImg, w, lane);
   bf16x8_t qf[8];   // B operand of S^T = K Q^T: Q[qrow][16 ks + 8 h + j]
   {
     const uint16_t* qp = a.q + (static_cast<int64_t>(bh) * S + min(qrow, S - 1)) * kD + 8 * h;
@@ -204,7 +236,7 @@ __global__ __launch_bounds__(64 * NWV, 8 / NWV) void fa_fwd_kernel(FaArgs a) {
   }
   f32x16 o[4] = {zero16(), zero16(), zero16(), zero16()};
   float m = -INFINITY, l = 0.f;
-  for (int t = 0; t < nt; ++t) {
+  for (int t = t0; t < nt; ++t) {
     const char* kimg = smem + (t & 1) * 2 * kImg;
     const char* vimg = kimg + kImg;
     // tile t landed (this wave's DMAs: a barrier does not wait for global_load_lds, and hipcc
@@ -219,6 +251,7 @@ __global__ __launch_bounds__(64 * NWV, 8 / NWV) void fa_fwd_kernel(FaArgs a) {
     }
     const int k0 = t * kBK;
     if (CAUSAL && k0 > qmin + 31) continue;   // every key of the tile is after every query
+    if (DOC && k0 + kBK - 1 < lo_first) continue;   // ... or before every query's document
     // S^T: s0 = keys k0 + 0..31, s1 = keys k0 + 32..63 (rows), query qrow (lane)
     f32x16 s0 = zero16(), s1 = zero16();
 #pragma unroll
@@ -226,12 +259,15 @@ __global__ __launch_bounds__(64 * NWV, 8 / NWV) void fa_fwd_kernel(FaArgs a) {
       s0 = mfma(rowfrag(kimg, r, 2 * ks + h), qf[ks], s0);
       s1 = mfma(rowfrag(kimg, 32 + r, 2 * ks + h), qf[ks], s1);
     }
-    if (CAUSAL ? (k0 + kBK - 1 > qmin) : (k0 + kBK > S)) {
+    // DOC: only a tile that holds a key before some query's document takes the key < lo mask;
+    // the interior tiles of a long document run the instruction stream of the plain kernel
+    if ((CAUSAL ? (k0 + kBK - 1 > qmin) : (k0 + kBK > S)) || (DOC && k0 < lo_last)) {
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
         const int key = k0 + acc_row(i, h);
-        if ((CAUSAL && key > qrow) || key >= S) s0[i] = -INFINITY;
-        if ((CAUSAL && key + 32 > qrow) || key + 32 >= S) s1[i] = -INFINITY;
+        if ((CAUSAL && key > qrow) || key >= S || (DOC && key < lo_row)) s0[i] = -INFINITY;
+        if ((CAUSAL && key + 32 > qrow) || key + 32 >= S || (DOC && key + 32 < lo_row))
+          s1[i] = -INFINITY;
       }
     }
     float mt = -INFINITY;
@@ -243,9 +279,12 @@ __global__ __launch_bounds__(64 * NWV, 8 / NWV) void fa_fwd_kernel(FaArgs a) {
     // (fp32 O / l accumulators, bf16 P keeps its relative precision); the first tile always
     // sets m (finite from then on: key 0 is visible to every query). thr = 0: the textbook
     // rescale at every max increase.
+    // DOC: a lane of a later document than the wave's first query sees nothing in the tiles
+    // before its own document: m and mt stay -inf there, and fin() keeps alpha and the
+    // exponentials NaN-free (alpha = 0 on O = l = 0, P = exp2(-inf) = 0) until its keys arrive.
     if (__any(mt > m + a.thr)) {
       const float mn = fmaxf(m, mt);
-      const float alpha = fexp2(m - mn);
+      const float alpha = fexp2(m - (DOC ? fin(mn) : mn));
       m = mn;
       l *= alpha;
 #pragma unroll
@@ -254,10 +293,11 @@ __global__ __launch_bounds__(64 * NWV, 8 / NWV) void fa_fwd_kernel(FaArgs a) {
         for (int i = 0; i < 16; ++i) o[dt][i] *= alpha;
     }
     float ls = 0.f;
+    const float ms = DOC ? fin(m) : m;
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
-      s0[i] = fexp2(fmaf(s0[i], a.c, -m));
-      s1[i] = fexp2(fmaf(s1[i], a.c, -m));
+      s0[i] = fexp2(fmaf(s0[i], a.c, -ms));
+      s1[i] = fexp2(fmaf(s1[i], a.c, -ms));
       ls += s0[i] + s1[i];
     }
     l += ls;
@@ -280,8 +320,9 @@ __global__ __launch_bounds__(64 * NWV, 8 / NWV) void fa_fwd_kernel(FaArgs a) {
 }
 
 // ------------------------------------------------------------------------------ backward: dQ
-template <bool CAUSAL, int NWV = 4>
+template <bool CAUSAL, int NWV = 4, bool DOC = false>
 __global__ __launch_bounds__(64 * NWV, 8 / NWV) void fa_dq_kernel(FaArgs a) {
+  static_assert(CAUSAL || !DOC, "document bounds are causal only");
   constexpr int BQ = 32 * NWV;
   extern __shared__ __attribute__((aligned(16))) char smem[];   // 2 x (K image, V image)
   const int lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
@@ -297,9 +338,20 @@ __global__ __launch_bounds__(64 * NWV, 8 / NWV) void fa_dq_kernel(FaArgs a) {
   const uint16_t* vg = a.v + kvoff;
   const int kend = CAUSAL ? min(S, q0 + BQ) : S;
   const int nt = (kend + kBK - 1) / kBK;
+  // DOC: lo is non-decreasing along a row, so the block's / wave's smallest bound is its first
+  // query's and the wave's largest its last query's. Tiles before the block's first visible key
+  // are neither staged nor computed (t0 keeps the buffer parity of tile t)
+  int t0 = 0, lo_row = 0, lo_first = 0, lo_last = 0;
+  if (DOC) {
+    const int* lob = a.lo + static_cast<int64_t>(b) * S;
+    t0 = max(lob[q0], 0) / kBK;
+    lo_row = lob[min(qrow, S - 1)];
+    lo_first = lob[min(qmin, S - 1)];
+    lo_last = lob[min(qmin + 31, S - 1)];
+  }
 
-  stage<NWV>(kg, kD, 0, S, smem, w, lane);
-  stage<NWV>(vg, kD, 0, S, smem + kImg, w, lane);
+  stage<NWV>(kg, kD, t0 * kBK, S, smem + (t0 & 1) * 2 * kImg, w, lane);
+  stage<NWV>(vg, kD, t0 * kBK, S, smem + (t0 & 1) * 2 * kImg + kImg, w, lane);
   bf16x8_t qf[8], df[8];
   float dsum;
   {
@@ -326,7 +378,7 @@ __global__ __launch_bounds__(64 * NWV, 8 / NWV) void fa_dq_kernel(FaArgs a) {
   }
   const float lse = a.lse[static_cast<int64_t>(bh) * S + qc];
   f32x16 dq[4] = {zero16(), zero16(), zero16(), zero16()};
-  for (int t = 0; t < nt; ++t) {
+  for (int t = t0; t < nt; ++t) {
     const char* kimg = smem + (t & 1) * 2 * kImg;
     const char* vimg = kimg + kImg;
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // tile t landed (see fa_fwd_kernel)
@@ -338,6 +390,7 @@ __global__ __launch_bounds__(64 * NWV, 8 / NWV) void fa_dq_kernel(FaArgs a) {
     }
     const int k0 = t * kBK;
     if (CAUSAL && k0 > qmin + 31) continue;
+    if (DOC && k0 + kBK - 1 < lo_first) continue;
     f32x16 s0 = zero16(), s1 = zero16(), p0 = zero16(), p1 = zero16();
 #pragma unroll
     for (int ks = 0; ks < 8; ++ks) {
@@ -346,14 +399,14 @@ __global__ __launch_bounds__(64 * NWV, 8 / NWV) void fa_dq_kernel(FaArgs a) {
       p0 = mfma(rowfrag(vimg, r, 2 * ks + h), df[ks], p0);
       p1 = mfma(rowfrag(vimg, 32 + r, 2 * ks + h), df[ks], p1);
     }
-    const bool edge = CAUSAL ? (k0 + kBK - 1 > qmin) : (k0 + kBK > S);
+    const bool edge = (CAUSAL ? (k0 + kBK - 1 > qmin) : (k0 + kBK > S)) || (DOC && k0 < lo_last);
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
       float e0 = fexp2(fmaf(s0[i], a.c, -lse)), e1 = fexp2(fmaf(s1[i], a.c, -lse));
-      if (edge) {
+      if (edge) {   // masked P is assigned 0 (exp2 of another document's score may be inf)
         const int key = k0 + acc_row(i, h);
-        if ((CAUSAL && key > qrow) || key >= S) e0 = 0.f;
-        if ((CAUSAL && key + 32 > qrow) || key + 32 >= S) e1 = 0.f;
+        if ((CAUSAL && key > qrow) || key >= S || (DOC && key < lo_row)) e0 = 0.f;
+        if ((CAUSAL && key + 32 > qrow) || key + 32 >= S || (DOC && key + 32 < lo_row)) e1 = 0.f;
       }
       s0[i] = e0 * (p0[i] - dsum);   // dS^T
       s1[i] = e1 * (p1[i] - dsum);
@@ -383,8 +436,9 @@ constexpr int kKVThreads = 512;
 constexpr int kKVBuf = 2 * kImg + 512;
 constexpr int kVImg = kKVKeys * 256;
 
-template <bool CAUSAL>
+template <bool CAUSAL, bool DOC = false>
 __global__ __launch_bounds__(kKVThreads, 2) void fa_dkdv_kernel(FaArgs a) {
+  static_assert(CAUSAL || !DOC, "document bounds are causal only");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* vimg = smem;
   char* bufs = smem + kVImg;
@@ -402,7 +456,18 @@ __global__ __launch_bounds__(kKVThreads, 2) void fa_dkdv_kernel(FaArgs a) {
   const float* lseg = a.lse + static_cast<int64_t>(bh) * S;
   const float* dsg = a.dsum + static_cast<int64_t>(bh) * S;
   const int qstart = CAUSAL ? kb0 : 0;
-  const int nt = (S - qstart + kBK - 1) / kBK;
+  // DOC: hi is non-decreasing along a row: no query at or past hi of the block's last key sees
+  // any key of the block (the query loop ends there), none at or past hi_last any key of the
+  // wave, and only a sub-tile reaching hi_first holds a query past some key's document
+  int qend = S, hi_key = S, hi_first = S, hi_last = S;
+  if (DOC) {
+    const int* hib = a.hi + static_cast<int64_t>(b) * S;
+    qend = hib[min(kb0 + kKVKeys - 1, S - 1)];
+    hi_key = hib[min(key, S - 1)];
+    hi_first = hib[min(kmin, S - 1)];
+    hi_last = hib[min(kmin + 31, S - 1)];
+  }
+  const int nt = (qend - qstart + kBK - 1) / kBK;
 
   auto stage_all = [&](int t, char* buf) {
     const int row0 = qstart + t * kBK;
@@ -437,7 +502,7 @@ __global__ __launch_bounds__(kKVThreads, 2) void fa_dkdv_kernel(FaArgs a) {
     for (int qs = 0; qs < 2; ++qs) {
       const int qq0 = q0 + 32 * qs;
       // causal: a sub-tile whose every query is before every key of the wave contributes nothing
-      if (!CAUSAL || qq0 + 31 >= kmin) {
+      if ((!CAUSAL || qq0 + 31 >= kmin) && (!DOC || qq0 < hi_last)) {
         f32x16 s = zero16(), dp = zero16();
         // the V rows are loop-invariant: an opaque base keeps them LDS reads (hoisted, they
         // would pin 32 more VGPRs for the whole loop)
@@ -449,7 +514,8 @@ __global__ __launch_bounds__(kKVThreads, 2) void fa_dkdv_kernel(FaArgs a) {
           dp = mfma(rowfrag(dimg, 32 * qs + r, 2 * ks + h), rowfrag(vimg, vrow, 2 * ks + h), dp);
         }
         // s[i] = S[query qq0 + acc_row(i, h)][key]; registers 4g..4g+3: 4 consecutive queries
-        const bool edge = (CAUSAL && qq0 < kmin + 31) || qq0 + 32 > S;
+        const bool edge = (CAUSAL && qq0 < kmin + 31) || qq0 + 32 > S ||
+                          (DOC && qq0 + 31 >= hi_first);
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
           const int ql = 32 * qs + 8 * g + 4 * h;
@@ -462,7 +528,7 @@ __global__ __launch_bounds__(kKVThreads, 2) void fa_dkdv_kernel(FaArgs a) {
             float p = fexp2(fmaf(s[i], a.c, -Lv[e]));
             if (edge) {
               const int qi = qq0 + 8 * g + 4 * h + e;
-              if ((CAUSAL && qi < key) || qi >= S) p = 0.f;
+              if ((CAUSAL && qi < key) || qi >= S || (DOC && qi >= hi_key)) p = 0.f;
             }
             s[i] = p;
             dp[i] = p * (dp[i] - Dv[e]);
@@ -521,17 +587,34 @@ int fa_waves() {
   return w;
 }
 
+}  // namespace
+
+#ifdef CML_FA_DOC_TU
+// (launch_fa's table is per compilation: 12 kernels in flash_attn.hip, these 5 here)
+hipError_t launch_fa_doc_fwd(const FaArgs& a, hipStream_t st) {
+  return fa_waves() == 8 ? launch_fa(fa_fwd_kernel<true, 8, true>, a, 4 * kImg, st, 256, 512)
+                         : launch_fa(fa_fwd_kernel<true, 4, true>, a, 4 * kImg, st);
+}
+
+hipError_t launch_fa_doc_bwd(const FaArgs& a, hipStream_t st) {
+  const hipError_t e = fa_waves() == 8
+                           ? launch_fa(fa_dq_kernel<true, 8, true>, a, 4 * kImg, st, 256, 512)
+                           : launch_fa(fa_dq_kernel<true, 4, true>, a, 4 * kImg, st);
+  if (e != hipSuccess) return e;
+  return launch_fa(fa_dkdv_kernel<true, true>, a, kVImg + 2 * kKVBuf, st, kKVKeys, kKVThreads);
+}
+#else
+namespace {
 bool fa_shape_ok(int B, int H, int KV, int S) {
   return B >= 1 && H >= 1 && KV >= 1 && H % KV == 0 && S >= 1 &&
          static_cast<int64_t>((S + kBQ - 1) / kBQ) * B * H < (1LL << 31);
 }
-
 }  // namespace
 
 hipError_t launch_flash_fwd(const void* q, const void* k, const void* v, void* o, float* lse, int B,
                             int H, int KV, int S, float scale, bool causal, hipStream_t st,
-                            float rescale_thr) {
-  if (!fa_shape_ok(B, H, KV, S)) return hipErrorInvalidValue;
+                            float rescale_thr, const int* lo) {
+  if (!fa_shape_ok(B, H, KV, S) || (lo != nullptr && !causal)) return hipErrorInvalidValue;
   FaArgs a{};
   a.q = static_cast<const uint16_t*>(q);
   a.k = static_cast<const uint16_t*>(k);
@@ -542,6 +625,8 @@ hipError_t launch_flash_fwd(const void* q, const void* k, const void* v, void* o
   a.scale = scale;
   a.c = scale * 1.4426950408889634f;
   a.thr = rescale_thr < 0.f ? 0.f : rescale_thr;
+  a.lo = lo;
+  if (lo != nullptr) return launch_fa_doc_fwd(a, st);
   if (fa_waves() == 8)
     return causal ? launch_fa(fa_fwd_kernel<true, 8>, a, 4 * kImg, st, 256, 512)
                   : launch_fa(fa_fwd_kernel<false, 8>, a, 4 * kImg, st, 256, 512);
@@ -552,8 +637,9 @@ hipError_t launch_flash_fwd(const void* q, const void* k, const void* v, void* o
 hipError_t launch_flash_bwd(const void* q, const void* k, const void* v, const void* o,
                             const void* dout, const float* lse, float* dsum, void* dq, void* dk,
                             void* dv, int B, int H, int KV, int S, float scale, bool causal,
-                            hipStream_t st) {
-  if (!fa_shape_ok(B, H, KV, S)) return hipErrorInvalidValue;
+                            hipStream_t st, const int* lo, const int* hi) {
+  if (!fa_shape_ok(B, H, KV, S) || (lo == nullptr) != (hi == nullptr) || (lo != nullptr && !causal))
+    return hipErrorInvalidValue;
   FaArgs a{};
   a.q = static_cast<const uint16_t*>(q);
   a.k = static_cast<const uint16_t*>(k);
@@ -568,6 +654,9 @@ hipError_t launch_flash_bwd(const void* q, const void* k, const void* v, const v
   a.B = B; a.H = H; a.KV = KV; a.S = S;
   a.scale = scale;
   a.c = scale * 1.4426950408889634f;
+  a.lo = lo;
+  a.hi = hi;
+  if (lo != nullptr) return launch_fa_doc_bwd(a, st);
   // dQ first: it also writes D = rowsum(dO * O), which the dK / dV kernel reads
   hipError_t e;
   if (fa_waves() == 8)
@@ -581,5 +670,6 @@ hipError_t launch_flash_bwd(const void* q, const void* k, const void* v, const v
   return causal ? launch_fa(fa_dkdv_kernel<true>, a, smem, st, kKVKeys, kKVThreads)
                 : launch_fa(fa_dkdv_kernel<false>, a, smem, st, kKVKeys, kKVThreads);
 }
+#endif  // CML_FA_DOC_TU
 
 }  // namespace cml

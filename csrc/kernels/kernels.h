@@ -392,13 +392,22 @@ hipError_t launch_rope_bwd(const void* dq, const void* dk, const void* dv, const
 // fp32 scratch (D = rowsum(dO * O)). csrc/kernels/flash_attn.hip.
 // rescale_thr: deferred online-softmax rescale threshold in log2 units (0 = rescale at every
 // max increase; 8 = scores exponentiated against a max up to 2^8 stale, see flash_attn.hip).
+// lo / hi: device int32 [B, S] document bounds from launch_doc_bounds (causal only; the backward
+// takes both or neither): query i attends to keys lo[b, i] <= j <= i, key j is seen by queries
+// j <= i < hi[b, j]. Tiles outside the bounds are neither staged nor computed. nullptr: the
+// kernels without the document variant.
 hipError_t launch_flash_fwd(const void* q, const void* k, const void* v, void* o, float* lse, int B,
                             int H, int KV, int S, float scale, bool causal, hipStream_t stream,
-                            float rescale_thr = 8.f);
+                            float rescale_thr = 8.f, const int* lo = nullptr);
 hipError_t launch_flash_bwd(const void* q, const void* k, const void* v, const void* o,
                             const void* dout, const float* lse, float* dsum, void* dq, void* dk,
                             void* dv, int B, int H, int KV, int S, float scale, bool causal,
-                            hipStream_t stream);
+                            hipStream_t stream, const int* lo = nullptr, const int* hi = nullptr);
+// Document bounds of packed rows: ids [B, S] (int32 or int64: id_bytes = 4 | 8); a document is a
+// maximal run of equal consecutive ids. lo[b, s] = first index of s's run, hi[b, s] = one past
+// its last; one launch, a workgroup per row, any S >= 1. csrc/kernels/flash_attn_doc.hip.
+hipError_t launch_doc_bounds(const void* ids, int id_bytes, int* lo, int* hi, int B, int S,
+                             hipStream_t stream);
 // Flash attention, head dim 64, MHA, causal or full, any S >= 1, in the fused layouts of
 // launch_attn_fwd / bwd: qkv [B, S, 3, H, 64] -> o [B, S, H * 64], lse fp32 [B, H, S] (log2
 // domain). Backward: dqkv [B, S, 3, H, 64], every element written once; dsum [B, H, S] fp32
