@@ -149,9 +149,37 @@ class OptimConfig:
     lars_exclude_1d  LARS: tensors with fewer than 2 dimensions (biases, BatchNorm / LayerNorm
                      affine) are not adapted (q = 1): they take the plain SGD step, weight decay
                      included
-    eps              Adam's denominator term; LARS: the term added to the ratio's denominator
+    eps              Adam's and LAMB's denominator term; LARS: the term added to the ratio's
+                     denominator
+    name=lamb        LAMB (You et al. 2020) on the AGGREGATE: Adam's moments, and every adapted
+                     tensor's step scaled by the trust ratio of the Adam DIRECTION. Per parameter
+                     tensor t, over exactly its elements, with p the fp32 master, m and v the fp32
+                     moments, x = fp32(float(g) * scale) the aggregate (the rule's output or the
+                     mean), k the 1-based step, b1, b2 = betas:
+                       m' = fma(b1, m, (1 - b1) x)        v' = fma(b2, v, (1 - b2) x x)
+                       denom = fma(sqrt(v'), 1 / sqrt(1 - b2^k), eps)
+                       r = (m' / denom) * (1 / (1 - b1^k))
+                       u = fma(weight_decay, p, r)
+                       wn = ||p||, un = ||u||   (fp64 sums of the fp32 values)
+                       q = wn / un if the tensor is adapted and wn > 0 and un > 0, else 1
+                       p' = fma(-(lr q), u, p)
+                     On the first step m = v = 0 and the state is not read. A non-finite wn or un
+                     gives q = 0 for that tensor: its p, m and v stay bit for bit, its bf16 / fp32
+                     parameters are rewritten from the unchanged master and the event is counted
+                     in ``engine.lamb_stats[t, 3]``: a NaN in the aggregate poisons no state, the
+                     moments included. Three device stages as LARS (aggregate -> per-tensor norms
+                     of u -> update; sharded topology: ONE all-reduce of the fp64 [T, 2] sums), so
+                     ``topology.early_update`` is off. The norm stage only reads and the update
+                     recomputes m', v', u with the same device function: 44 B per element with an
+                     fp32 aggregate where storing the moments in the norm stage would move 40 B,
+                     the price of leaving a non-finite tensor's moments untouched.
+                     ``engine.lamb_stats`` (fp64 [T, 4]) = [wn, un, q, non-finite steps] per
+                     tensor. Not implemented together with ``clip_norm`` or ``worker_momentum``;
+                     no trust-ratio clamp, one weight decay for all tensors
+    lamb_exclude_1d  LAMB: tensors with fewer than 2 dimensions are not adapted (q = 1): they
+                     take p - lr * u
     """
-    name: str = "sgd"            # sgd | adam | adamw | lars
+    name: str = "sgd"            # sgd | adam | adamw | lars | lamb
     lr: float = 0.1
     momentum: float = 0.9
     nesterov: bool = False
@@ -162,6 +190,7 @@ class OptimConfig:
     clip_norm: float = 0.0
     trust_coef: float = 0.001
     lars_exclude_1d: bool = True
+    lamb_exclude_1d: bool = True
 
     def validate(self) -> None:
         c = self.clip_norm
@@ -170,13 +199,13 @@ class OptimConfig:
         t = self.trust_coef
         if isinstance(t, bool) or not isinstance(t, (int, float)) or not math.isfinite(t) or t <= 0:
             raise ValueError(f"optim.trust_coef must be a finite number > 0 (got {t!r})")
-        if self.name == "lars" and c > 0:
-            raise ValueError("optim.name=lars with optim.clip_norm > 0 is not implemented")
+        if self.name in ("lars", "lamb") and c > 0:
+            raise ValueError(f"optim.name={self.name} with optim.clip_norm > 0 is not implemented")
         if not self.worker_momentum:
             return
-        if self.name == "lars":
-            raise ValueError("optim.worker_momentum is not implemented with optim.name=lars "
-                             "(it needs optim.name=sgd)")
+        if self.name in ("lars", "lamb"):
+            raise ValueError("optim.worker_momentum is not implemented with "
+                             f"optim.name={self.name} (it needs optim.name=sgd)")
         if self.name != "sgd":
             raise ValueError(f"optim.worker_momentum needs optim.name=sgd (got {self.name!r})")
         if self.momentum == 0:
@@ -193,7 +222,7 @@ class TopologyConfig:
     ``early_update`` (gossip, one worker per rank: each bucket's optimizer step runs during
     backward) is forced off while ``optim.clip_norm`` > 0: the update of the first bucket would
     need the gradient norm over all of them. The engine logs the switch once. The same holds for
-    ``optim.name=lars``, whose update waits for the per-tensor norms.
+    ``optim.name=lars`` and ``optim.name=lamb``, whose updates wait for the per-tensor norms.
     """
     kind: str = "sharded"        # allreduce | allgather | sharded | gossip
     bucket_mb: float = 64.0      # bucket size in MB of gradient (bf16 on the wire)

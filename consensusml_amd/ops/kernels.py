@@ -96,8 +96,11 @@ def rule_combine(rule: str, n: int, f: int, trim: Optional[int] = None, *,
 class OptArgs:
     """Hyper-parameters of one fused optimizer step (SGD or Adam/AdamW), or of the LARS step
     (``lars_update``: SGD's fields; the trust coefficient and the ratio's eps go to ``lars_ratio``,
-    so this class keeps the fields the recorded engine traces list)."""
-    kind: str = "sgd"            # none | sgd | adam (L2 weight decay) | adamw (decoupled) | lars
+    so this class keeps the fields the recorded engine traces list), or of the LAMB step
+    (``lamb_norms`` / ``lamb_update``: Adam's fields; ``first`` = the moments are zero and not
+    read)."""
+    # none | sgd | adam (L2 weight decay) | adamw (decoupled) | lars | lamb
+    kind: str = "sgd"
     lr: float = 0.1
     momentum: float = 0.0
     weight_decay: float = 0.0
@@ -110,8 +113,9 @@ class OptArgs:
     gscale: float = 1.0
 
     def opt_id(self) -> int:
-        if self.kind == "lars":
-            raise ValueError("OptArgs(kind='lars') is the step of lars_update, not of agg_update")
+        if self.kind in ("lars", "lamb"):
+            raise ValueError(f"OptArgs(kind={self.kind!r}) is the step of {self.kind}_update, not "
+                             "of agg_update")
         return {"none": 0, "sgd": 1, "adamw": 2, "adam": 3 if self.weight_decay else 2}[self.kind]
 
 
@@ -767,5 +771,70 @@ def lars_update(g: torch.Tensor, scale: float, plan: LarsPlan, q: torch.Tensor, 
         master[o:o + n].copy_(p[o:o + n])
         if opt.momentum:
             s1[o:o + n].copy_(b[o:o + n])
+        if pout is not None:
+            pout[:n].copy_(p[o:o + n].to(pout.dtype))
+
+
+# --------------------------------------------------------------------------- LAMB
+def _lamb_scalars(opt: OptArgs, who: str):
+    """(weight_decay, beta1, beta2, eps, inv_bc1, inv_sqrt_bc2, first): the bias corrections of
+    the 1-based step in double, as ``agg_update`` forms Adam's."""
+    if opt.kind != "lamb":
+        raise ValueError(f"{who} takes OptArgs(kind='lamb'), got {opt.kind!r}")
+    if opt.step < 1:
+        raise ValueError(f"{who}: the step is 1-based (got {opt.step})")
+    return (opt.weight_decay, opt.beta1, opt.beta2, opt.eps, 1.0 / (1.0 - opt.beta1 ** opt.step),
+            1.0 / math.sqrt(1.0 - opt.beta2 ** opt.step), bool(opt.first))
+
+
+def lamb_norms(master: torch.Tensor, g: torch.Tensor, scale: float, plan: LarsPlan, opt: OptArgs,
+               s1: torch.Tensor, s2: torch.Tensor, out: Optional[torch.Tensor] = None,
+               grid_cap: int = 0) -> torch.Tensor:
+    """out (fp64 [T, 2]) = per tensor (sum p^2, sum u^2) over exactly the tensor's elements, u the
+    LAMB direction ``OptimConfig`` defines from the fp32 master, the gradient row ``g`` (bf16 /
+    fp32) times ``scale`` and the moments ``s1``, ``s2`` (``reference.lamb_norms``); ``opt`` =
+    OptArgs(kind="lamb"). Nothing but ``out`` is written. GPU: one read-only pass, fp64 partials
+    per work item summed in a fixed order, no atomics. ``lars_ratio(out, adapt, 1.0, 0.0, 0.0,
+    ...)`` turns the pairs into the factors ``lamb_update`` takes."""
+    sc = _lamb_scalars(opt, "lamb_norms")
+    if out is None:
+        out = torch.zeros(plan.T, 2, dtype=torch.float64, device=master.device)
+    if master.is_cuda:
+        items, item_off, _, work = plan.on(master.device)
+        lib().lamb_norms(master, g, float(scale), s1, s2, items, item_off, plan.total, work, out,
+                         *sc, grid_cap)
+        return out
+    out.copy_(ref.lamb_norms(master, g, s1, s2, plan.starts[:-1], plan.numels, scale, *sc))
+    return out
+
+
+def lamb_update(g: torch.Tensor, scale: float, plan: LarsPlan, q: torch.Tensor, opt: OptArgs,
+                master: torch.Tensor, s1: torch.Tensor, s2: torch.Tensor, segs=None,
+                grid_cap: int = 0) -> None:
+    """The LAMB step in place over the state vector (master and both moments):
+    ``reference.lamb_update`` with the factors ``q`` on the gradient row ``g`` times ``scale``,
+    ``opt`` = OptArgs(kind="lamb"). A tensor with q == 0 keeps master and moments bit for bit.
+    ``segs``: output segments (param_out or None, state offset, length) -- the parameters
+    rewritten from the master (bf16 / fp32); None = no parameter output over the whole vector.
+    GPU: 16 segments per launch."""
+    sc = _lamb_scalars(opt, "lamb_update")
+    if segs is None:
+        segs = [(None, 0, plan.total)]
+    segs = [(p, int(o), int(n)) for p, o, n in segs]
+    if master.is_cuda:
+        _, _, starts, _ = plan.on(master.device)
+        lib().lamb_update(g, float(scale), master, s1, s2, q, starts, plan.starts,
+                          [p for p, _, _ in segs], [o for _, o, _ in segs],
+                          [n for _, _, n in segs], opt.lr, *sc, grid_cap)
+        return
+    for _, o, n in segs:
+        if o % 8 or o < 0 or o + n > plan.total:
+            raise ValueError(f"lamb_update: segment [{o}, +{n}) must start at a multiple of 8 "
+                             f"inside the state vector of {plan.total}")
+    p, m, v = ref.lamb_update(master, g, s1, s2, q, plan.starts, scale, opt.lr, *sc)
+    for pout, o, n in segs:     # (the reference computes the whole vector; segments select)
+        master[o:o + n].copy_(p[o:o + n])
+        s1[o:o + n].copy_(m[o:o + n])
+        s2[o:o + n].copy_(v[o:o + n])
         if pout is not None:
             pout[:n].copy_(p[o:o + n].to(pout.dtype))

@@ -573,5 +573,65 @@ def lars_update(p: torch.Tensor, g: torch.Tensor, buf: Optional[torch.Tensor], q
                       first)
 
 
+# --------------------------------------------------------------------------- LAMB
+
+def lamb_dir(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, scale: float,
+             weight_decay: float, beta1: float, beta2: float, eps: float, inv_bc1: float,
+             inv_sqrt_bc2: float, first: bool = False
+             ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(m', v', u) of LAMB per element in fp32, the operation order of ``lamb_dir``
+    (csrc/kernels/lamb.hip; torch on the CPU does not fuse, so the fmas round twice here):
+    x = float(g) * scale; m' = b1 m + (1 - b1) x; v' = b2 v + (1 - b2) x x; u = weight_decay p +
+    (m' / (sqrt(v') inv_sqrt_bc2 + eps)) inv_bc1. ``first``: m = v = 0, not read."""
+    f = lambda c: torch.tensor(c, dtype=torch.float32)
+    p = p.float()
+    x = g.float() * f(scale)
+    m = torch.zeros_like(p) if first else m.float()
+    v = torch.zeros_like(p) if first else v.float()
+    m = f(beta1) * m + (f(1.0) - f(beta1)) * x
+    v = f(beta2) * v + (f(1.0) - f(beta2)) * x * x
+    r = (m / (v.sqrt() * f(inv_sqrt_bc2) + f(eps))) * f(inv_bc1)
+    return m, v, f(weight_decay) * p + r
+
+
+def lamb_norms(master: torch.Tensor, g: torch.Tensor, s1: torch.Tensor, s2: torch.Tensor, starts,
+               numels, scale: float, weight_decay: float, beta1: float, beta2: float, eps: float,
+               inv_bc1: float, inv_sqrt_bc2: float, first: bool = False) -> torch.Tensor:
+    """fp64 [T, 2]: per tensor t over exactly its elements [starts[t], starts[t] + numels[t]) of
+    the state vector, (sum p^2, sum u^2) with u the fp32 direction of ``lamb_dir``; squares and
+    sums are fp64 (``lamb_norm_partial``, csrc/kernels/lamb.hip)."""
+    D = min(master.numel(), g.numel())
+    cpu = lambda t: t.detach().reshape(-1)[:D].cpu()
+    p = cpu(master).float()
+    _, _, u = lamb_dir(p, cpu(g), cpu(s1), cpu(s2), scale, weight_decay, beta1, beta2, eps,
+                       inv_bc1, inv_sqrt_bc2, first)
+    out = torch.zeros(len(numels), 2, dtype=torch.float64)
+    for t, (s, n) in enumerate(zip(starts, numels)):
+        out[t, 0] = (p[s:s + n].double() ** 2).sum()
+        out[t, 1] = (u[s:s + n].double() ** 2).sum()
+    return out
+
+
+def lamb_update(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor,
+                q: torch.Tensor, starts, scale: float, lr: float, weight_decay: float,
+                beta1: float, beta2: float, eps: float, inv_bc1: float, inv_sqrt_bc2: float,
+                first: bool = False) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The LAMB step over a whole state vector (returns new copies of master and moments): per
+    element of tensor t, p' = p - (lr q[t]) u with (m', v', u) of ``lamb_dir``; where q[t] == 0
+    master and moments are returned unchanged, so a NaN gradient poisons no state. ``starts``:
+    T + 1 ascending starts as ``lars_update`` takes them (``lamb_update``,
+    csrc/kernels/lamb.hip)."""
+    D = int(starts[-1])
+    spans = torch.as_tensor([starts[t + 1] - starts[t] for t in range(len(starts) - 1)])
+    spans[0] += starts[0]
+    qe = torch.repeat_interleave(q.detach().float().cpu(), spans)
+    p, m, v = p[:D].float(), m[:D].float(), v[:D].float()
+    m2, v2, u = lamb_dir(p, g[:D], m, v, scale, weight_decay, beta1, beta2, eps, inv_bc1,
+                         inv_sqrt_bc2, first)
+    keep = qe == 0
+    p2 = p - (torch.tensor(lr, dtype=torch.float32) * qe) * u
+    return torch.where(keep, p, p2), torch.where(keep, m, m2), torch.where(keep, v, v2)
+
+
 __all__ = [n for n in dir() if not n.startswith("_") and n not in ("math", "torch", "Optional",
                                                                      "Tuple", "annotations")]

@@ -1,4 +1,5 @@
-"""Fused optimizers over flat buffers: ``FusedSGD``, ``FusedAdam``, ``FusedAdamW``, ``FusedLARS``.
+"""Fused optimizers over flat buffers: ``FusedSGD``, ``FusedAdam``, ``FusedAdamW``, ``FusedLARS``,
+``FusedLAMB``.
 
 Drop-in ``torch.optim.Optimizer`` subclasses for code that does not go through the consensus
 engine. At construction every parameter of a param group becomes a view into
@@ -361,7 +362,79 @@ class FusedLARS(_FusedBase):
         return loss
 
 
+class FusedLAMB(_FusedBase):
+    """LAMB (You et al. 2020) as ``OptimConfig`` defines it: Adam's moments give the direction
+    u = weight_decay * p + (m' / (sqrt(v') / sqrt(1 - b2^k) + eps)) / (1 - b1^k), and every tensor
+    steps by lr * q * u with q = ||p|| / ||u|| (norms over the fp32 master and over u, fp64 sums
+    on the device; q = 1 for a tensor that is excluded or has a zero norm; where a norm is not
+    finite the tensor's master and moments stay untouched). ``exclude_1d``: tensors with fewer
+    than 2 dimensions (biases, norm affine) take q = 1. fp32 and bf16 parameters (fp16 parameters
+    raise TypeError). Three launches per flat buffer (``csrc/kernels/lamb.hip`` and the ratio
+    kernel of ``lars.hip``): the norms of u, the ratios, the update.
+
+    The state is ``exp_avg`` / ``exp_avg_sq`` (+ ``master``), so a ``torch.optim.AdamW`` state
+    dict loads. ``lamb_stats``: per flat buffer an fp64 [T, 4] device tensor of [wn, un, q, steps
+    with a non-finite norm], rows in that buffer's parameter order."""
+    _kind = "lamb"
+    _state_keys = ("exp_avg", "exp_avg_sq")
+
+    def __init__(self, params, lr: float = 1e-3, betas: Tuple[float, float] = (0.9, 0.999),
+                 eps: float = 1e-6, weight_decay: float = 0.0, exclude_1d: bool = True,
+                 max_grad_norm: float = 0.0):
+        if max_grad_norm:
+            raise ValueError("FusedLAMB with max_grad_norm > 0 is not implemented")
+        super().__init__(params, dict(lr=lr, betas=tuple(betas), eps=eps,
+                                      weight_decay=weight_decay, exclude_1d=exclude_1d))
+        self.lamb_stats: List[torch.Tensor] = []
+        self._lamb = []
+        for group, flats in zip(self.param_groups, self._flats):
+            for fl in flats:
+                if fl.grad.dtype == torch.float16:
+                    raise TypeError("FusedLAMB takes fp32 / bf16 parameters")
+                dev, T = fl.grad.device, len(fl.params)
+                plan = K.lars_plan(fl.offsets, [p.numel() for p in fl.params], total=fl.total)
+                adapt = torch.tensor([not (group["exclude_1d"] and p.dim() < 2)
+                                      for p in fl.params], dtype=torch.uint8, device=dev)
+                bufs = (plan, adapt, torch.zeros(T, 2, dtype=torch.float64, device=dev),
+                        torch.ones(T, dtype=torch.float32, device=dev),
+                        torch.zeros(T, K.LARS_STATS, dtype=torch.float64, device=dev))
+                self._lamb.append(bufs)
+                self.lamb_stats.append(bufs[4])
+
+    def load_state_dict(self, state_dict) -> None:
+        super().load_state_dict(state_dict)
+        for group in self.param_groups:   # a torch.optim.AdamW state dict carries no LAMB keys
+            for k, v in self.defaults.items():
+                group.setdefault(k, v)
+
+    def _opt_args(self, group, step):
+        b1, b2 = group["betas"]
+        return OptArgs(kind="lamb", lr=group["lr"], weight_decay=group["weight_decay"], beta1=b1,
+                       beta2=b2, eps=group["eps"], step=step, first=step == 1)
+
+    @torch.no_grad()
+    def step(self, closure=None, grad_scale: float = 1.0):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        bufs = iter(self._lamb)
+        for group, flats in zip(self.param_groups, self._flats):
+            group["step"] += 1
+            o = self._opt_args(group, group["step"])
+            for fl in flats:
+                fl.sync_foreign_grads()
+                plan, adapt, pairs, q, stats = next(bufs)
+                m, v = fl.states
+                K.lamb_norms(fl.master, fl.grad, grad_scale, plan, o, m, v, out=pairs)
+                K.lars_ratio(pairs, adapt, 1.0, 0.0, 0.0, q, stats)
+                K.lamb_update(fl.grad, grad_scale, plan, q, o, fl.master, m, v,
+                              segs=[(fl.param if fl.lowp else None, 0, fl.total)])
+        return loss
+
+
 def build_optimizer(name: str, params, **kw) -> torch.optim.Optimizer:
-    """``OptimConfig.name`` -> fused optimizer (sgd | adam | adamw | lars)."""
-    cls = {"sgd": FusedSGD, "adam": FusedAdam, "adamw": FusedAdamW, "lars": FusedLARS}[name]
+    """``OptimConfig.name`` -> fused optimizer (sgd | adam | adamw | lars | lamb)."""
+    cls = {"sgd": FusedSGD, "adam": FusedAdam, "adamw": FusedAdamW, "lars": FusedLARS,
+           "lamb": FusedLAMB}[name]
     return cls(params, **kw)

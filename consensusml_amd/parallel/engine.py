@@ -47,6 +47,13 @@ ops.kernels.seg_sq_norm over the master and the aggregate (fp64 [T, 2] sums; sha
 all-reduce of that vector), ops.kernels.lars_ratio (the DEVICE factors q and ``lars_stats``) and
 ops.kernels.lars_update, the SGD-momentum update that multiplies tensor t's gradient by q[t]. The
 sharded topology's parameter all-gathers follow the update.
+
+LAMB (optim.name = lamb, defined in ``OptimConfig``) runs at the same places on the same tables:
+stage 2 is ops.kernels.lamb_norms, a read-only pass that forms the Adam direction u from the
+aggregate, the master and both moments and sums p^2 and u^2 per tensor (sharded, N > 1: the same
+ONE all-reduce), ops.kernels.lars_ratio with trust 1 and no decay or eps term gives q = wn / un
+and ``lamb_stats``, and ops.kernels.lamb_update recomputes u, applies p - lr q[t] u and stores the
+moments -- except for a tensor whose norm was not finite, whose master and moments stay as they are.
 """
 from __future__ import annotations
 
@@ -178,7 +185,7 @@ class ConsensusEngine:
         self.s1 = (torch.zeros_like(self.master)
                    if (oname not in ("sgd", "lars") or cfg.optim.momentum)
                    and not self.worker_momentum else None)
-        self.s2 = torch.zeros_like(self.master) if oname in ("adam", "adamw") else None
+        self.s2 = torch.zeros_like(self.master) if oname in ("adam", "adamw", "lamb") else None
         self.step_count = 0
 
         # -------------------------------------------------- exchange buffers
@@ -218,8 +225,11 @@ class ConsensusEngine:
         self._clip_direct = self.topo == "allreduce" or (self.topo == "gossip" and self.V == 1)
         # optim.name=lars: the same three stages with per-tensor norms (module docstring)
         self.lars = oname == "lars"
+        # optim.name=lamb: the same stages and tables, norms of the Adam direction
+        self.lamb = oname == "lamb"
+        self.trust = self.lars or self.lamb     # the update waits for per-tensor trust ratios
         self.gout = None
-        if self.rule == "centered_clip" or ((self.clip or self.lars) and not self._clip_direct):
+        if self.rule == "centered_clip" or ((self.clip or self.trust) and not self._clip_direct):
             self.gout = torch.zeros(self.state_len, dtype=torch.float32, device=dev)
         # [norm of the aggregate, clipping coefficient, steps whose norm was not finite (their
         # coefficient is 0: a zero gradient), squared norm] of the last step, fp64 on the device
@@ -231,8 +241,8 @@ class ConsensusEngine:
                            if self.clip and self.topo == "sharded" and self.group_active
                            and self.N > 1 else None)
         self._clip_work: Optional[torch.Tensor] = None
-        if self.lars:
-            self._setup_lars()
+        if self.trust:
+            self._setup_lars(cfg.optim.lamb_exclude_1d if self.lamb else cfg.optim.lars_exclude_1d)
 
         # -------------------------------------------------- gradient capture + overlap hooks
         # Copy-on-ready: autograd produces fresh .grad tensors; when every parameter of a bucket
@@ -269,15 +279,15 @@ class ConsensusEngine:
         self.early_update = (self.topo == "gossip" and self.V == 1 and dev.type == "cuda"
                              and cfg.fault.kind not in COLLUSION
                              and cfg.topology.early_update and not self.clip
-                             and not self.lars)
+                             and not self.trust)
         if self.clip and self.topo == "gossip" and self.V == 1 and cfg.topology.early_update:
             # the first bucket's update needs the norm over all of them
             _log.info("optim.clip_norm > 0: topology.early_update is off (the update waits for "
                       "the global gradient norm)")
-        if self.lars and self.topo == "gossip" and self.V == 1 and cfg.topology.early_update:
+        if self.trust and self.topo == "gossip" and self.V == 1 and cfg.topology.early_update:
             # a tensor's update needs its norms, and the stages run over the whole vector
-            _log.info("optim.name=lars: topology.early_update is off (the update waits for the "
-                      "per-tensor norms)")
+            _log.info(f"optim.name={oname}: topology.early_update is off (the update waits for "
+                      "the per-tensor norms)")
         self._updated: set = set()
         self._opt_stream = torch.cuda.Stream(device=dev) if self.early_update else None
         # Sharded topology: the bf16 parameter all-gather of each bucket is not waited for at the
@@ -718,7 +728,7 @@ class ConsensusEngine:
     # ================================================================ optimizer args
     def _opt_args(self, gscale: float = 1.0) -> K.OptArgs:
         o = self.cfg.optim
-        kind = o.name if o.name in ("sgd", "adam", "adamw", "lars") else "adamw"
+        kind = o.name if o.name in ("sgd", "adam", "adamw", "lars", "lamb") else "adamw"
         wd = o.weight_decay
         # 'adam' = torch.optim.Adam (L2 term in the gradient), 'adamw' = decoupled decay
         mom = o.momentum if kind in ("sgd", "lars") and not self.worker_momentum else 0.0
@@ -880,11 +890,12 @@ class ConsensusEngine:
         K.agg_update(row, combine="weighted", w=self.w_clip, n=1, D=fl.total, opt=self._opt_args(),
                      master=m, s1=s1, s2=s2, param_out=fl.flat_param)
 
-    # ================================================================ LARS
-    def _setup_lars(self) -> None:
+    # ================================================================ LARS / LAMB
+    def _setup_lars(self, exclude_1d: bool) -> None:
         """The tables of the vector the update runs over (rebuilt from the layout, so a
-        checkpoint carries nothing of them) and the per-tensor device buffers."""
-        fl, o, dev = self.flat, self.cfg.optim, self.device
+        checkpoint carries nothing of them) and the per-tensor device buffers; LAMB shares
+        them. ``exclude_1d``: tensors with fewer than 2 dimensions are not adapted."""
+        fl, dev = self.flat, self.device
         shard = self.topo == "sharded" and self.group_active
         ranges = fl.tensor_ranges(self.rank if shard else None)   # ascending in the vector
         self._lars_plan = K.lars_plan([s for _, s, _ in ranges], [n for _, _, n in ranges],
@@ -895,7 +906,7 @@ class ConsensusEngine:
         self._lars_row = torch.empty(T, dtype=torch.int64).scatter_(
             0, order, torch.arange(T)).to(dev)
         self._lars_adapt = torch.tensor(
-            [not (o.lars_exclude_1d and fl.params[i].dim() < 2) for i, _, _ in ranges],
+            [not (exclude_1d and fl.params[i].dim() < 2) for i, _, _ in ranges],
             dtype=torch.uint8, device=dev)
         self._lars_pairs = torch.zeros(T, 2, dtype=torch.float64, device=dev)
         self._lars_red = (torch.zeros(T, 2, dtype=torch.float64, device=dev)
@@ -909,22 +920,37 @@ class ConsensusEngine:
         was not finite] of the last step (None unless optim.name=lars)."""
         return self._lars_stats[self._lars_row] if self.lars else None
 
+    @property
+    def lamb_stats(self) -> Optional[torch.Tensor]:
+        """fp64 [T, 4] on the device, rows in ``flat.params`` order: [wn, un, q, steps whose norm
+        was not finite] of the last step (None unless optim.name=lamb)."""
+        return self._lars_stats[self._lars_row] if self.lamb else None
+
     def _lars_row_update(self, row: torch.Tensor, scale: float, segs) -> None:
-        """Stages 2 + 3 of LARS over ONE row co-indexed with the state vector (a gradient row
-        times ``scale``, or the materialised fp32 aggregate with scale 1): the per-tensor norms --
-        sharded, N > 1: ONE all-reduce of the fp64 [T, 2] sums, issued by every rank at this
-        point of the step, so every rank derives identical ratios -- then the update with the
+        """Stages 2 + 3 of LARS / LAMB over ONE row co-indexed with the state vector (a gradient
+        row times ``scale``, or the materialised fp32 aggregate with scale 1): the per-tensor
+        norms -- sharded, N > 1: ONE all-reduce of the fp64 [T, 2] sums, issued by every rank at
+        this point of the step, so every rank derives identical ratios -- then the update with the
         device factors q. ``segs``: (parameters, state offset, length) the update rewrites."""
-        o = self.cfg.optim
-        K.seg_sq_norm(self.master, row, scale, self._lars_plan, out=self._lars_pairs)
+        o, opt, plan = self.cfg.optim, self._opt_args(), self._lars_plan
+        if self.lamb:
+            K.lamb_norms(self.master, row, scale, plan, opt, self.s1, self.s2,
+                         out=self._lars_pairs)
+        else:
+            K.seg_sq_norm(self.master, row, scale, plan, out=self._lars_pairs)
         red = self._lars_red
         if red is not None:
             red.copy_(self._lars_pairs)
             dist.all_reduce(red)
-        K.lars_ratio(self._lars_pairs, self._lars_adapt, o.trust_coef, o.weight_decay, o.eps,
-                     self._lars_q, self._lars_stats, reduced=red)
-        K.lars_update(row, scale, self._lars_plan, self._lars_q, self._opt_args(), self.master,
-                      self.s1, segs=segs)
+        # LAMB: q = wn / un, the decay is inside u
+        trust, wd, eps = (1.0, 0.0, 0.0) if self.lamb else (o.trust_coef, o.weight_decay, o.eps)
+        K.lars_ratio(self._lars_pairs, self._lars_adapt, trust, wd, eps, self._lars_q,
+                     self._lars_stats, reduced=red)
+        if self.lamb:
+            K.lamb_update(row, scale, plan, self._lars_q, opt, self.master, self.s1, self.s2,
+                          segs=segs)
+        else:
+            K.lars_update(row, scale, plan, self._lars_q, opt, self.master, self.s1, segs=segs)
 
     def _lars_full_update(self, row: torch.Tensor, scale: float) -> None:
         fl = self.flat
@@ -940,7 +966,7 @@ class ConsensusEngine:
         if self.clip:       # direct path: every rank holds the same summed row, no collective
             self._clipped_row_update(fl.flat_grad[0], 1.0 / self.n)
             return
-        if self.lars:
+        if self.trust:
             self._lars_full_update(fl.flat_grad[0], 1.0 / self.n)
             return
         opt = self._opt_args(gscale=1.0 / self.n)
@@ -981,7 +1007,8 @@ class ConsensusEngine:
         if self.record_stats:
             self._record_stats(cols)
         opt = self._opt_args()
-        staged = self.clip or self.lars     # clipping / LARS: the rule kernels are stage 1 only
+        # clipping / LARS / LAMB: the rule kernels are stage 1 only
+        staged = self.clip or self.trust
         rule_opt = opt if not staged else K.OptArgs(kind="none")
         # prefetch: earliest layers (highest bucket index) first, the next forward needs them first
         order = list(reversed(cols)) if self.param_prefetch else cols
@@ -1016,13 +1043,13 @@ class ConsensusEngine:
                 self._gather_params(b, pout, works)
         elif self.clip:     # every rank holds the full aggregate: no collective
             self._clipped_row_update(self.gout, 1.0)
-        elif self.lars and sharded:
+        elif self.trust and sharded:
             # stages 2 + 3 over this rank's shards; the parameter all-gathers follow the update
             self._lars_row_update(self.gout, 1.0,
                                   [(pout, off, length) for _, _, length, off, pout in segs])
             for b, _, _, _, pout in segs:
                 self._gather_params(b, pout, works)
-        elif self.lars:     # every rank holds the full aggregate: no collective
+        elif self.trust:    # every rank holds the full aggregate: no collective
             self._lars_full_update(self.gout, 1.0)
         for w in works:
             w.wait()
@@ -1092,10 +1119,10 @@ class ConsensusEngine:
             K.agg_update(fl.flat_grad, combine="weighted", n=self.V,
                          opt=K.OptArgs(kind="none", gscale=1.0 / self.V), gout=self.gout)
             self._clipped_row_update(self.gout, 1.0)
-        elif self.lars and self.V == 1:
+        elif self.trust and self.V == 1:
             # every rank adapts its own local gradient; direct path: the row is the gradient
             self._lars_full_update(fl.flat_grad[0], 1.0)
-        elif self.lars:
+        elif self.trust:
             K.agg_update(fl.flat_grad, combine="weighted", n=self.V,
                          opt=K.OptArgs(kind="none", gscale=1.0 / self.V), gout=self.gout)
             self._lars_full_update(self.gout, 1.0)

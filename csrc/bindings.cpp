@@ -2193,6 +2193,30 @@ int check_lars_rows(const Tensor& master, const Tensor& g, int64_t vec_len) {
   return dtype_of(g);
 }
 
+// pairs[t] = the sum, in item order, of the pairs work[2 i], work[2 i + 1] of tensor t's items
+void fold_item_pairs(Tensor& work, const Tensor& item_off, int64_t I, int64_t T, Tensor& pairs) {
+  CML_CHECK_HIP(cml::launch_lars_finalize(work.data_ptr<double>(), item_off.data_ptr<int64_t>(), I,
+                                          static_cast<int>(T), pairs.data_ptr<double>(), nullptr,
+                                          nullptr, 0.0, 0.0, 0.0, nullptr, nullptr, cur_stream()));
+}
+
+// the tables of a segmented norm pass (seg_sq_norm, lamb_norms): returns (I, T)
+std::pair<int64_t, int64_t> check_item_tables(const Tensor& master, const Tensor& items,
+                                              const Tensor& item_off, const Tensor& work,
+                                              const Tensor& pairs, int64_t grid_cap,
+                                              const char* who) {
+  TORCH_CHECK(grid_cap >= 0 && grid_cap <= (1 << 20), who, ": grid_cap out of range");
+  TORCH_CHECK(items.dim() == 2 && items.size(1) == 3, who, ": items must be [I, 3]");
+  const int64_t I = items.size(0);
+  const int64_t T = item_off.numel() - 1;
+  TORCH_CHECK(T >= 0 && T <= INT_MAX, who, ": item_off must hold T + 1 entries");
+  check_table(items, at::kLong, 3 * I, master, "items");
+  check_table(item_off, at::kLong, T + 1, master, "item_off");
+  check_table(work, at::kDouble, 2 * I, master, "work");
+  check_table(pairs, at::kDouble, 2 * T, master, "pairs");
+  return {I, T};
+}
+
 // pairs[t] (fp64 [T, 2]) = (sum p^2, sum (fp32(g * scale))^2) over tensor t's elements. items:
 // device int64 [I, 3] of (tensor, start, len); item_off: device int64 [T + 1], tensor t's items
 // are [item_off[t], item_off[t + 1]); work: fp64, at least 2 I elements.
@@ -2200,23 +2224,14 @@ void seg_sq_norm(const Tensor& master, const Tensor& g, double scale, const Tens
                  const Tensor& item_off, int64_t vec_len, Tensor& work, Tensor& pairs,
                  int64_t grid_cap) {
   const int dt = check_lars_rows(master, g, vec_len);
-  TORCH_CHECK(grid_cap >= 0 && grid_cap <= (1 << 20), "seg_sq_norm: grid_cap out of range");
-  TORCH_CHECK(items.dim() == 2 && items.size(1) == 3, "seg_sq_norm: items must be [I, 3]");
-  const int64_t I = items.size(0);
-  const int64_t T = item_off.numel() - 1;
-  TORCH_CHECK(T >= 0 && T <= INT_MAX, "seg_sq_norm: item_off must hold T + 1 entries");
-  check_table(items, at::kLong, 3 * I, master, "items");
-  check_table(item_off, at::kLong, T + 1, master, "item_off");
-  check_table(work, at::kDouble, 2 * I, master, "work");
-  check_table(pairs, at::kDouble, 2 * T, master, "pairs");
+  const auto [I, T] = check_item_tables(master, items, item_off, work, pairs, grid_cap,
+                                        "seg_sq_norm");
   const c10::DeviceGuard guard(master.device());
   CML_CHECK_HIP(cml::launch_seg_sq_norm_partial(
       dt, master.data_ptr<float>(), g.data_ptr(), static_cast<float>(scale),
       items.data_ptr<int64_t>(), I, vec_len, work.data_ptr<double>(), static_cast<int>(grid_cap),
       cur_stream()));
-  CML_CHECK_HIP(cml::launch_lars_finalize(work.data_ptr<double>(), item_off.data_ptr<int64_t>(), I,
-                                          static_cast<int>(T), pairs.data_ptr<double>(), nullptr,
-                                          nullptr, 0.0, 0.0, 0.0, nullptr, nullptr, cur_stream()));
+  fold_item_pairs(work, item_off, I, T, pairs);
 }
 
 // q[t] (fp32) and stats[t] (fp64 [4]: wn, gn, q, non-finite count) from pairs[t] = (sum p^2, sum
@@ -2242,6 +2257,61 @@ void lars_ratio(const Tensor& pairs, const Tensor& adapt, double trust, double w
                                           cur_stream()));
 }
 
+// the T + 1 host values of the device table `starts` of lars_update / lamb_update: ascending from
+// 0, all multiples of 8, starts[T] = the vector length. Returns T.
+int64_t check_lars_starts(const std::vector<int64_t>& starts_host, const char* who) {
+  TORCH_CHECK(starts_host.size() >= 2, who, ": starts must hold T + 1 >= 2 entries");
+  const int64_t T = static_cast<int64_t>(starts_host.size()) - 1;
+  TORCH_CHECK(T <= INT_MAX, who, ": too many tensors");
+  TORCH_CHECK(starts_host[0] == 0, who, ": the first tensor must start at 0");
+  for (int64_t t = 0; t <= T; ++t) {
+    TORCH_CHECK(starts_host[t] % 8 == 0, who, ": tensor start ", starts_host[t],
+                " is not a multiple of 8 elements");
+    TORCH_CHECK(t == 0 || starts_host[t] >= starts_host[t - 1], who,
+                ": tensor starts must ascend");
+  }
+  return T;
+}
+
+// the output segments (param_out or None, state offset, length) of lars_update / lamb_update,
+// checked against the state vector; pf32: the parameter outputs are fp32
+std::vector<cml::LarsSeg> lars_segs(const std::vector<optional<Tensor>>& pouts,
+                                    const std::vector<int64_t>& offs,
+                                    const std::vector<int64_t>& lens, int64_t vec_len,
+                                    const Tensor& master, const char* who, bool& pf32) {
+  const size_t ns = pouts.size();
+  TORCH_CHECK(ns >= 1 && offs.size() == ns && lens.size() == ns,
+              who, ": matching pouts / offs / lens");
+  const bool has_out = pouts[0].has_value() && pouts[0]->defined();
+  pf32 = false;
+  std::vector<cml::LarsSeg> segs(ns);
+  for (size_t i = 0; i < ns; ++i) {
+    TORCH_CHECK(offs[i] >= 0 && lens[i] >= 0 && offs[i] % 8 == 0 && offs[i] <= vec_len &&
+                    lens[i] <= vec_len - offs[i],
+                who, ": segment ", i, " [", offs[i], ", +", lens[i],
+                ") must start at a multiple of 8 inside the state vector of ", vec_len);
+    const bool has = pouts[i].has_value() && pouts[i]->defined();
+    TORCH_CHECK(has == has_out, who, ": every segment or none has a param_out");
+    void* p = nullptr;
+    if (has) {
+      const Tensor& P = *pouts[i];
+      check_dev(P, "param_out");
+      const bool f32 = P.scalar_type() == at::kFloat;
+      TORCH_CHECK(f32 || P.scalar_type() == at::kBFloat16, who, ": param_out bf16 or fp32");
+      TORCH_CHECK(i == 0 || f32 == pf32, who, ": param_outs of one dtype");
+      pf32 = f32;
+      TORCH_CHECK(P.device() == master.device() && P.is_contiguous() && P.numel() >= lens[i],
+                  who, ": param_out ", i, " must be contiguous with at least ", lens[i],
+                  " elements on master's device");
+      p = P.data_ptr();
+      TORCH_CHECK((reinterpret_cast<uintptr_t>(p) & 15) == 0,
+                  who, ": param_out must be 16-B aligned");
+    }
+    segs[i] = cml::LarsSeg{p, offs[i], lens[i]};
+  }
+  return segs;
+}
+
 // The LARS update over output segments (param_out or None, state offset, length), at most 16 per
 // launch. starts_host: the T + 1 values of the device table `starts`, checked here: ascending from
 // 0, all multiples of 8 (a 16-B vector never straddles two tensors), starts[T] = the vector length.
@@ -2250,16 +2320,7 @@ void lars_update(const Tensor& g, double scale, Tensor& master, const optional<T
                  const std::vector<optional<Tensor>>& pouts, const std::vector<int64_t>& offs,
                  const std::vector<int64_t>& lens, double lr, double momentum, double weight_decay,
                  bool nesterov, bool first, int64_t grid_cap) {
-  TORCH_CHECK(starts_host.size() >= 2, "lars_update: starts must hold T + 1 >= 2 entries");
-  const int64_t T = static_cast<int64_t>(starts_host.size()) - 1;
-  TORCH_CHECK(T <= INT_MAX, "lars_update: too many tensors");
-  TORCH_CHECK(starts_host[0] == 0, "lars_update: the first tensor must start at 0");
-  for (int64_t t = 0; t <= T; ++t) {
-    TORCH_CHECK(starts_host[t] % 8 == 0, "lars_update: tensor start ", starts_host[t],
-                " is not a multiple of 8 elements");
-    TORCH_CHECK(t == 0 || starts_host[t] >= starts_host[t - 1],
-                "lars_update: tensor starts must ascend");
-  }
+  const int64_t T = check_lars_starts(starts_host, "lars_update");
   const int64_t vec_len = starts_host[T];
   const int dt = check_lars_rows(master, g, vec_len);
   TORCH_CHECK(grid_cap >= 0 && grid_cap <= (1 << 20), "lars_update: grid_cap out of range");
@@ -2270,36 +2331,10 @@ void lars_update(const Tensor& g, double scale, Tensor& master, const optional<T
   if (s1p) TORCH_CHECK(s1->device() == master.device() &&
                            (reinterpret_cast<uintptr_t>(s1p) & 15) == 0,
                        "lars_update: s1 on master's device, 16-B aligned");
-  const size_t ns = pouts.size();
-  TORCH_CHECK(ns >= 1 && offs.size() == ns && lens.size() == ns,
-              "lars_update: matching pouts / offs / lens");
-  const bool has_out = pouts[0].has_value() && pouts[0]->defined();
   bool pf32 = false;
-  std::vector<cml::LarsSeg> segs(ns);
-  for (size_t i = 0; i < ns; ++i) {
-    TORCH_CHECK(offs[i] >= 0 && lens[i] >= 0 && offs[i] % 8 == 0 && offs[i] <= vec_len &&
-                    lens[i] <= vec_len - offs[i],
-                "lars_update: segment ", i, " [", offs[i], ", +", lens[i],
-                ") must start at a multiple of 8 inside the state vector of ", vec_len);
-    const bool has = pouts[i].has_value() && pouts[i]->defined();
-    TORCH_CHECK(has == has_out, "lars_update: every segment or none has a param_out");
-    void* p = nullptr;
-    if (has) {
-      const Tensor& P = *pouts[i];
-      check_dev(P, "param_out");
-      const bool f32 = P.scalar_type() == at::kFloat;
-      TORCH_CHECK(f32 || P.scalar_type() == at::kBFloat16, "lars_update: param_out bf16 or fp32");
-      TORCH_CHECK(i == 0 || f32 == pf32, "lars_update: param_outs of one dtype");
-      pf32 = f32;
-      TORCH_CHECK(P.device() == master.device() && P.is_contiguous() && P.numel() >= lens[i],
-                  "lars_update: param_out ", i, " must be contiguous with at least ", lens[i],
-                  " elements on master's device");
-      p = P.data_ptr();
-      TORCH_CHECK((reinterpret_cast<uintptr_t>(p) & 15) == 0,
-                  "lars_update: param_out must be 16-B aligned");
-    }
-    segs[i] = cml::LarsSeg{p, offs[i], lens[i]};
-  }
+  std::vector<cml::LarsSeg> segs =
+      lars_segs(pouts, offs, lens, vec_len, master, "lars_update", pf32);
+  const size_t ns = segs.size();
   cml::LarsUpd u{};
   u.lr = static_cast<float>(lr);
   u.momentum = static_cast<float>(momentum);
@@ -2312,6 +2347,90 @@ void lars_update(const Tensor& g, double scale, Tensor& master, const optional<T
     const int n = static_cast<int>(std::min(ns, a + cml::kLarsMaxSegs) - a);
     CML_CHECK_HIP(cml::launch_lars_update(dt, g.data_ptr(), static_cast<float>(scale),
                                           master.data_ptr<float>(), s1p, q.data_ptr<float>(),
+                                          starts.data_ptr<int64_t>(), static_cast<int>(T),
+                                          segs.data() + a, n, u, static_cast<int>(grid_cap),
+                                          cur_stream()));
+  }
+}
+
+// ---------------------------------------------------------------- LAMB
+// a moment row of the state vector: fp32, contiguous, 16-B aligned, at least vec_len long
+float* check_lamb_moment(const Tensor& s, const Tensor& master, int64_t vec_len,
+                         const char* name) {
+  check_table(s, at::kFloat, vec_len, master, name);
+  TORCH_CHECK((reinterpret_cast<uintptr_t>(s.data_ptr()) & 15) == 0, "lamb: ", name,
+              " must be 16-B aligned");
+  return s.data_ptr<float>();
+}
+
+// the step's scalars; the bias corrections are computed by the caller in double
+cml::LambUpd lamb_upd(double lr, double weight_decay, double beta1, double beta2, double eps,
+                      double inv_bc1, double inv_sqrt_bc2, bool first) {
+  TORCH_CHECK(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0,
+              "lamb: betas must be in [0, 1)");
+  TORCH_CHECK(eps >= 0.0 && inv_bc1 > 0.0 && inv_sqrt_bc2 > 0.0,
+              "lamb: eps must not be negative, the bias corrections positive");
+  cml::LambUpd u{};
+  u.lr = static_cast<float>(lr);
+  u.weight_decay = static_cast<float>(weight_decay);
+  u.beta1 = static_cast<float>(beta1);
+  u.beta2 = static_cast<float>(beta2);
+  u.eps = static_cast<float>(eps);
+  u.inv_bc1 = static_cast<float>(inv_bc1);
+  u.inv_sqrt_bc2 = static_cast<float>(inv_sqrt_bc2);
+  u.first = first ? 1 : 0;
+  return u;
+}
+
+// pairs[t] (fp64 [T, 2]) = (sum p^2, sum u^2) over tensor t's elements, u the LAMB direction of
+// kernels.h from the master, the gradient row g times scale and the moments s1, s2 (not read when
+// `first`). Tables as seg_sq_norm's. Nothing is written but work and pairs.
+void lamb_norms(const Tensor& master, const Tensor& g, double scale, const Tensor& s1,
+                const Tensor& s2, const Tensor& items, const Tensor& item_off, int64_t vec_len,
+                Tensor& work, Tensor& pairs, double weight_decay, double beta1, double beta2,
+                double eps, double inv_bc1, double inv_sqrt_bc2, bool first, int64_t grid_cap) {
+  const int dt = check_lars_rows(master, g, vec_len);
+  const float* s1p = check_lamb_moment(s1, master, vec_len, "s1");
+  const float* s2p = check_lamb_moment(s2, master, vec_len, "s2");
+  const auto [I, T] = check_item_tables(master, items, item_off, work, pairs, grid_cap,
+                                        "lamb_norms");
+  const cml::LambUpd u = lamb_upd(0.0, weight_decay, beta1, beta2, eps, inv_bc1, inv_sqrt_bc2,
+                                  first);
+  const c10::DeviceGuard guard(master.device());
+  CML_CHECK_HIP(cml::launch_lamb_norm_partial(
+      dt, master.data_ptr<float>(), g.data_ptr(), static_cast<float>(scale), s1p, s2p,
+      items.data_ptr<int64_t>(), I, vec_len, u, work.data_ptr<double>(),
+      static_cast<int>(grid_cap), cur_stream()));
+  fold_item_pairs(work, item_off, I, T, pairs);
+}
+
+// The LAMB update over output segments (param_out or None, state offset, length), at most 16 per
+// launch; starts / starts_host as lars_update's. q: the device factors of lars_ratio.
+void lamb_update(const Tensor& g, double scale, Tensor& master, Tensor& s1, Tensor& s2,
+                 const Tensor& q, const Tensor& starts, const std::vector<int64_t>& starts_host,
+                 const std::vector<optional<Tensor>>& pouts, const std::vector<int64_t>& offs,
+                 const std::vector<int64_t>& lens, double lr, double weight_decay, double beta1,
+                 double beta2, double eps, double inv_bc1, double inv_sqrt_bc2, bool first,
+                 int64_t grid_cap) {
+  const int64_t T = check_lars_starts(starts_host, "lamb_update");
+  const int64_t vec_len = starts_host[T];
+  const int dt = check_lars_rows(master, g, vec_len);
+  TORCH_CHECK(grid_cap >= 0 && grid_cap <= (1 << 20), "lamb_update: grid_cap out of range");
+  check_table(q, at::kFloat, T, master, "q");
+  check_table(starts, at::kLong, T + 1, master, "starts");
+  float* s1p = check_lamb_moment(s1, master, vec_len, "s1");
+  float* s2p = check_lamb_moment(s2, master, vec_len, "s2");
+  bool pf32 = false;
+  std::vector<cml::LarsSeg> segs =
+      lars_segs(pouts, offs, lens, vec_len, master, "lamb_update", pf32);
+  const size_t ns = segs.size();
+  cml::LambUpd u = lamb_upd(lr, weight_decay, beta1, beta2, eps, inv_bc1, inv_sqrt_bc2, first);
+  u.param_f32 = pf32;
+  const c10::DeviceGuard guard(master.device());
+  for (size_t a = 0; a < ns; a += cml::kLarsMaxSegs) {
+    const int n = static_cast<int>(std::min(ns, a + cml::kLarsMaxSegs) - a);
+    CML_CHECK_HIP(cml::launch_lamb_update(dt, g.data_ptr(), static_cast<float>(scale),
+                                          master.data_ptr<float>(), s1p, s2p, q.data_ptr<float>(),
                                           starts.data_ptr<int64_t>(), static_cast<int>(T),
                                           segs.data() + a, n, u, static_cast<int>(grid_cap),
                                           cur_stream()));
@@ -3263,6 +3382,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("starts"), py::arg("starts_host"), py::arg("pouts"), py::arg("offs"),
         py::arg("lens"), py::arg("lr"), py::arg("momentum"), py::arg("weight_decay"),
         py::arg("nesterov"), py::arg("first"), py::arg("grid_cap") = 0);
+  m.def("lamb_norms", &lamb_norms,
+        "per-tensor (sum p^2, sum u^2) of the LAMB direction u, in fp64 over a table of work items",
+        py::arg("master"), py::arg("g"), py::arg("scale"), py::arg("s1"), py::arg("s2"),
+        py::arg("items"), py::arg("item_off"), py::arg("vec_len"), py::arg("work"),
+        py::arg("pairs"), py::arg("weight_decay"), py::arg("beta1"), py::arg("beta2"),
+        py::arg("eps"), py::arg("inv_bc1"), py::arg("inv_sqrt_bc2"), py::arg("first"),
+        py::arg("grid_cap") = 0);
+  m.def("lamb_update", &lamb_update, "LAMB update with a per-tensor step factor",
+        py::arg("g"), py::arg("scale"), py::arg("master"), py::arg("s1"), py::arg("s2"),
+        py::arg("q"), py::arg("starts"), py::arg("starts_host"), py::arg("pouts"),
+        py::arg("offs"), py::arg("lens"), py::arg("lr"), py::arg("weight_decay"),
+        py::arg("beta1"), py::arg("beta2"), py::arg("eps"), py::arg("inv_bc1"),
+        py::arg("inv_sqrt_bc2"), py::arg("first"), py::arg("grid_cap") = 0);
   m.def("bn_fwd", &bn_fwd, "fused NHWC BatchNorm(+res)(+ReLU) forward");
   m.def("bn_bwd", &bn_bwd, "fused NHWC BatchNorm(+res)(+ReLU) backward");
   m.def("bn_fwd2", &bn_fwd2, "relu(BN(x1) + BN(x2)) forward (downsample-block tail)");

@@ -335,6 +335,36 @@ hipError_t launch_lars_update(int dtype, const void* g, float scale, float* mast
                               const float* q, const int64_t* starts, int T, const LarsSeg* segs,
                               int nseg, const LarsUpd& u, int grid_cap, hipStream_t stream);
 
+// LAMB: Adam's moments with a per-tensor trust ratio on the Adam direction (lamb.hip,
+// optim.name=lamb), over the state vector, item table, starts table and output segments LARS
+// defines above, with the moments s1 = m and s2 = v. Per element, x = fp32(g * scale):
+//   m' = fma(beta1, m, (1 - beta1) x)      v' = fma(beta2, v, (1 - beta2) x x)
+//   u = fma(weight_decay, p, (m' / fma(sqrt(v'), inv_sqrt_bc2, eps)) * inv_bc1)
+// with m = v = 0, not read, when `first`. inv_bc1 = 1 / (1 - beta1^k) and inv_sqrt_bc2 =
+// 1 / sqrt(1 - beta2^k) of the 1-based step k come from the host.
+// lamb_norm_partial: item i writes work[2 i] = sum p^2 and work[2 i + 1] = sum u^2 over its
+// elements (fp64, fixed order, every slot written on every launch, no atomics, no state written;
+// an item outside [0, vec_len) reads nothing and writes zeros). lars_finalize folds the items and,
+// with trust = 1, wd = 0, eps = 0, gives q[t] = wn / un (1 where the tensor is not adapted or a
+// norm is 0; 0 where one is not finite) and the stats.
+// lamb_update: p' = fma(-(lr q[t]), u, p); m', v', p' and the parameter output (bf16, fp32 when
+// param_f32) are stored, except that q[t] == 0 stores no state: the parameters are rewritten from
+// the unchanged master. Both kernels compute u by the same device function, so the norm is the
+// norm of what is applied, bit for bit.
+struct LambUpd {
+  float lr, weight_decay, beta1, beta2, eps, inv_bc1, inv_sqrt_bc2;
+  int first;
+  int param_f32;
+};
+hipError_t launch_lamb_norm_partial(int dtype, const float* master, const void* g, float scale,
+                                    const float* s1, const float* s2, const int64_t* items,
+                                    int64_t nitems, int64_t vec_len, const LambUpd& u, double* work,
+                                    int grid_cap, hipStream_t stream);
+hipError_t launch_lamb_update(int dtype, const void* g, float scale, float* master, float* s1,
+                              float* s2, const float* q, const int64_t* starts, int T,
+                              const LarsSeg* segs, int nseg, const LambUpd& u, int grid_cap,
+                              hipStream_t stream);
+
 // ---- transformer ops (transformer.hip); bf16 activations, fp32 statistics.
 // Cross-entropy over contiguous bf16 logits [R, V] (16-B aligned base): forward writes the
 // per-row logsumexp and loss (0 for ignored rows); backward writes
