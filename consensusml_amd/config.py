@@ -280,6 +280,7 @@ class ModelConfig:
     seq_len: int = 128
     in_features: int = 32
     hidden: int = 64
+    dropout: float = 0.0         # bert_*: hidden and attention-probability dropout (BERT: 0.1)
     extra: Dict[str, Any] = field(default_factory=dict)
 
 

@@ -78,7 +78,8 @@ def build_task(cfg: ModelConfig, device: torch.device, dtype: torch.dtype = torc
             return x.to(dtype).contiguous(memory_format=torch.channels_last), y
         return Task(name, model, make, _ce)
     if name in ("bert_base", "bert_tiny"):
-        model = (bert_base() if name == "bert_base" else bert_tiny()).to(device, dtype)
+        mk = bert_base if name == "bert_base" else bert_tiny
+        model = mk(dropout=cfg.dropout, attn_dropout=cfg.dropout).to(device, dtype)
         V = model.c.vocab
         S = cfg.seq_len
 

@@ -95,16 +95,85 @@ def _take_bias_parts(dy2: torch.Tensor):
     return None
 
 
+# ============================================================================ dropout
+# The fused dropout sites (add_norm, norm, fused_qkv_attention) draw their masks from a counter-
+# based generator on the device (csrc/kernels/dropout.h): the keep decision of an element is a pure
+# function of (seed, offset, linear element index), so nothing is stored and a backward regenerates
+# what its forward used. A site's (seed, offset) is its ``rng`` argument, or the next draw of the
+# process-wide stream below.
+class DropoutStream:
+    """A seed and a call counter: every dropout site takes ``next()`` in its forward."""
+
+    def __init__(self, seed: int = 0):
+        self.seed, self.counter = int(seed), 0
+
+    def manual_seed(self, seed: int) -> None:
+        self.seed, self.counter = int(seed) & (2 ** 63 - 1), 0
+
+    def next(self) -> Tuple[int, int]:
+        self.counter += 1
+        return self.seed, self.counter - 1
+
+    def state_dict(self) -> dict:
+        return {"seed": self.seed, "counter": self.counter}
+
+    def load_state_dict(self, st: dict) -> None:
+        self.seed, self.counter = int(st["seed"]), int(st["counter"])
+
+
+dropout_stream = DropoutStream()
+
+
+def _drop_thr(p: float) -> int:
+    """thr = round(p * 65536): a draw below it drops; the effective rate is thr / 65536."""
+    if not 0.0 <= p < 1.0:
+        raise ValueError(f"dropout must be in [0, 1), got {p}")
+    return min(int(round(p * 65536)), 65535)
+
+
+def _drop(p: float, training: bool, rng) -> Optional[Tuple[int, int, int]]:
+    """(seed, offset, thr) of an active dropout site, None for p = 0 / eval mode (which take no
+    draw from the stream)."""
+    thr = _drop_thr(float(p))
+    if not training or thr == 0:
+        return None
+    seed, offset = rng if rng is not None else dropout_stream.next()
+    return int(seed), int(offset), thr
+
+
+def dropout_mask(seed: int, offset: int, shape, p: float, device="cuda") -> torch.Tensor:
+    """The uint8 keep mask (1 = kept) that a fused dropout site with this ``(seed, offset)`` and
+    rate applies to a tensor of ``shape`` (hidden sites: the activation's shape; attention:
+    ``[B, H, S, S]``), written by the same device function. Kept values are scaled by
+    ``65536 / (65536 - round(p * 65536))``."""
+    return lib().dropout_mask(int(seed), int(offset), list(shape), _drop_thr(p), torch.device(device))
+
+
+def _keep_scaled(shape, dtype, device, drop) -> torch.Tensor:
+    """keep / (1 - p_eff) for the PyTorch compositions: the device mask on a GPU; on the CPU a
+    ``torch.Generator`` seeded with (seed, offset) (a different, equally distributed mask)."""
+    seed, offset, thr = drop
+    device = torch.device(device)
+    if device.type == "cuda":
+        keep = lib().dropout_mask(seed, offset, list(shape), thr, device)
+    else:
+        g = torch.Generator().manual_seed((seed * 0x9E3779B97F4A7C15 + offset) % (2 ** 63))
+        keep = torch.randint(0, 65536, tuple(shape), generator=g) >= thr
+    return keep.to(dtype) * (65536.0 / (65536 - thr))
+
+
 # ============================================================================ norms
 class _NormFn(torch.autograd.Function):
-    """y = norm(x) (no residual)."""
+    """y = norm(x) (no residual); ``drop``: y = keep * norm(x) / (1 - p) on the way to the store,
+    the backward masks dy on load."""
 
     @staticmethod
-    def forward(ctx, x, w, b, eps):
-        y, _, mean, rstd = lib().norm_fwd(x, None, w, b, eps)
+    def forward(ctx, x, w, b, eps, drop=None):
+        y, _, mean, rstd = lib().norm_fwd(x, None, w, b, eps, *(drop or ()))
         ctx.save_for_backward(x, w, mean if b is not None else None, rstd)
         ctx.ln = b is not None
         ctx.params = (w, b)
+        ctx.drop = drop
         return y
 
     @staticmethod
@@ -112,23 +181,25 @@ class _NormFn(torch.autograd.Function):
         x, w, mean, rstd = ctx.saved_tensors
         seg = _norm_bwd_workers(ctx, dy, None, x, w, mean, rstd)
         if seg is not None:
-            return seg, None, None, None
-        dx, dw, db = lib().norm_bwd(dy, None, x, w, mean, rstd)
-        return dx, dw, (db if ctx.ln else None), None
+            return seg[0], None, None, None, None
+        dx, dw, db, _ = lib().norm_bwd(dy, None, x, w, mean, rstd, *(ctx.drop or ()))
+        return dx, dw, (db if ctx.ln else None), None, None
 
 
 class _AddNormFn(torch.autograd.Function):
     """(s, y) = (x + r, norm(x + r)): the residual-stream update and the next sublayer's input in
     one pass. The backward adds the gradient of s (the stream's own consumers) to the norm's
-    input gradient on the way out: d x = d r = ds + norm_bwd(dy)."""
+    input gradient on the way out: d x = d r = ds + norm_bwd(dy). ``drop``: s = x +
+    keep * r / (1 - p), and the same backward pass also writes d r = keep * d x / (1 - p)."""
 
     @staticmethod
-    def forward(ctx, x, r, w, b, eps, x_link):
-        y, s, mean, rstd = lib().norm_fwd(x, r, w, b, eps)
+    def forward(ctx, x, r, w, b, eps, x_link, drop=None):
+        y, s, mean, rstd = lib().norm_fwd(x, r, w, b, eps, *(drop or ()))
         ctx.save_for_backward(s, w, mean if b is not None else None, rstd)
         ctx.ln = b is not None
         ctx.params = (w, b)
         ctx.x_link = x_link
+        ctx.drop = drop
         # an unused s (post-LN BERT) must arrive as None, not as a zero-filled tensor that the
         # backward would then read
         ctx.set_materialize_grads(False)
@@ -137,13 +208,20 @@ class _AddNormFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, ds, dy):
         s, w, mean, rstd = ctx.saved_tensors
+        drop = ctx.drop
         if dy is None:
-            return ds, ds, None, None, None, None
-        seg = _norm_bwd_workers(ctx, dy, ds, s, w, mean, rstd)
+            dr = ds if drop is None or ds is None else \
+                ds * _keep_scaled(ds.shape, ds.dtype, ds.device, drop)
+            return ds, dr, None, None, None, None, None
+        seg = _norm_bwd_workers(ctx, dy, ds, s, w, mean, rstd, drop is not None)
         if seg is not None:
-            dx, dw, db = seg, None, None
+            (dx, dr), dw, db = seg, None, None
+        elif drop is not None:
+            dx, dw, db, dr = lib().norm_bwd(dy, ds, s, w, mean, rstd, *drop, True)
         else:
-            dx, dw, db = lib().norm_bwd(dy, ds, s, w, mean, rstd)
+            dx, dw, db, _ = lib().norm_bwd(dy, ds, s, w, mean, rstd)
+        if drop is None:
+            dr = dx
         gx = dx
         link = ctx.x_link
         if link is not None and not link.closed and link.grad is None:
@@ -151,12 +229,14 @@ class _AddNormFn(torch.autograd.Function):
             # backward later and absorbs this gradient in its beta = 1 epilogue
             link.grad = dx
             gx = None
-        return gx, dx, dw, (db if ctx.ln else None), None, None
+        return gx, dr, dw, (db if ctx.ln else None), None, None, None
 
 
-def _norm_bwd_workers(ctx, dy, ds, x, w, mean, rstd) -> Optional[torch.Tensor]:
-    """Batched virtual workers (ops.worker_grads): dx, with worker v's dgamma / dbeta written to
-    row v of the engine's gradient buffer; None when no per-worker destination is active."""
+def _norm_bwd_workers(ctx, dy, ds, x, w, mean, rstd, drop_res: bool = False):
+    """Batched virtual workers (ops.worker_grads): (dx, dr), with worker v's dgamma / dbeta
+    written to row v of the engine's gradient buffer; None when no per-worker destination is
+    active. The op's dropout (``ctx.drop``) rides along; ``drop_res``: it acted on the residual
+    input, whose gradient is dr (else None)."""
     wg = WG.current()
     pw, pb = ctx.params
     if wg is None or not wg.has(pw):
@@ -164,16 +244,18 @@ def _norm_bwd_workers(ctx, dy, ds, x, w, mean, rstd) -> Optional[torch.Tensor]:
     V, D = wg.V, x.shape[-1]
     dwv, fw = wg.out(pw)
     dbv, fb = wg.out(pb) if ctx.ln else (None, True)
+    dr = torch.empty_like(x) if drop_res else None
+    dk = (*(ctx.drop or (0, 0, 0)), dr)
     if fw and fb:
         return lib().norm_bwd_seg(dy, ds, x, w, mean, rstd, V, dwv.view(V, D),
-                                  dbv.view(V, D) if dbv is not None else None)
+                                  dbv.view(V, D) if dbv is not None else None, *dk), dr
     tw = torch.empty(V, D, dtype=dwv.dtype, device=dwv.device)      # (second producer: add)
     tb = torch.empty_like(tw) if ctx.ln else None
-    dx = lib().norm_bwd_seg(dy, ds, x, w, mean, rstd, V, tw, tb)
+    dx = lib().norm_bwd_seg(dy, ds, x, w, mean, rstd, V, tw, tb, *dk)
     (dwv.view(V, D).copy_ if fw else dwv.view(V, D).add_)(tw)
     if ctx.ln:
         (dbv.view(V, D).copy_ if fb else dbv.view(V, D).add_)(tb)
-    return dx
+    return dx, dr
 
 
 def _norm_ref(x, w, b, eps):
@@ -189,24 +271,45 @@ def _norm_ok(x: torch.Tensor, D: int) -> bool:
     return D % 8 == 0 and D <= 4096 and x.is_contiguous() and x.data_ptr() % 16 == 0
 
 
-def norm(x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor], eps: float) -> torch.Tensor:
-    """LayerNorm (``b`` given) or RMSNorm (``b is None``) over the last dim."""
+def norm(x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor], eps: float,
+         dropout: float = 0.0, training: bool = True, rng=None) -> torch.Tensor:
+    """LayerNorm (``b`` given) or RMSNorm (``b is None``) over the last dim. ``dropout`` > 0 in
+    training mode drops the OUTPUT (BERT's embedding site): the fused kernel masks y on its way
+    to the store and dy on load; ``rng = (seed, offset)`` fixes the mask (default: the next draw
+    of ``dropout_stream``). Other tensors compose the same ops in PyTorch."""
+    drop = _drop(dropout, training, rng)
     if _gpu_bf16(x, w, b) and _norm_ok(x, x.shape[-1]):
-        return _NormFn.apply(x, w, b, float(eps))
-    return _norm_ref(x, w, b, eps)
+        if drop is None:
+            return _NormFn.apply(x, w, b, float(eps))
+        return _NormFn.apply(x, w, b, float(eps), drop)
+    y = _norm_ref(x, w, b, eps)
+    return y if drop is None else y * _keep_scaled(y.shape, y.dtype, y.device, drop)
 
 
 def add_norm(x: torch.Tensor, r: Optional[torch.Tensor], w: torch.Tensor,
-             b: Optional[torch.Tensor], eps: float,
-             x_link: Optional[ResidualLink] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+             b: Optional[torch.Tensor], eps: float, x_link: Optional[ResidualLink] = None,
+             dropout: float = 0.0, training: bool = True,
+             rng=None) -> Tuple[torch.Tensor, torch.Tensor]:
     """(s, norm(s)) with s = x + r (r None: s = x). ``x_link``: x also feeds a ``linear(...,
     link=x_link)`` whose backward runs after this op's (x's gradient is then added inside that
-    GEMM instead of by autograd)."""
+    GEMM instead of by autograd).
+
+    ``dropout`` > 0 in training mode drops the sublayer output r: s = x + keep * r / (1 - p) in
+    the same pass, and the backward writes r's gradient (exactly 0 where dropped) next to x's.
+    ``rng = (seed, offset)`` fixes the mask (default: the next draw of ``dropout_stream``);
+    ``dropout_mask(seed, offset, r.shape, p)`` returns it. dropout = 0 or ``training=False``
+    is today's op, bit for bit. CPU / fp32 / ineligible tensors compose the same ops in PyTorch
+    (the CPU mask comes from a ``torch.Generator`` and differs from the device one)."""
     if r is None:
         return x, norm(x, w, b, eps)
+    drop = _drop(dropout, training, rng)
     if _gpu_bf16(x, r, w, b) and _norm_ok(x, x.shape[-1]) and r.is_contiguous() \
             and r.data_ptr() % 16 == 0 and r.shape == x.shape:
-        return _AddNormFn.apply(x, r, w, b, float(eps), x_link)
+        if drop is None:
+            return _AddNormFn.apply(x, r, w, b, float(eps), x_link)
+        return _AddNormFn.apply(x, r, w, b, float(eps), x_link, drop)
+    if drop is not None:
+        r = r * _keep_scaled(r.shape, r.dtype, r.device, drop)
     s = x + r
     return s, _norm_ref(s, w, b, eps)
 
@@ -351,17 +454,24 @@ def qkv_split(qkv: torch.Tensor, H: int, KV: int, hd: int, cos: Optional[torch.T
 
 # ============================================================================ attention
 class _AttnFn(torch.autograd.Function):
+    """``drop``: the probabilities are dropped in registers between the two products, forward and
+    backward, from the regenerated mask (lse stays the undropped log-sum-exp)."""
+
     @staticmethod
-    def forward(ctx, qkv, H, scale):
-        out, lse = lib().attn_fwd(qkv, H, scale)
+    def forward(ctx, qkv, H, scale, drop=None):
+        if drop is not None and os.environ.get("CML_ATTN_BWD_V1", "")[:1] == "1":
+            raise RuntimeError("attention dropout needs the second attention backward: unset "
+                               "CML_ATTN_BWD_V1")
+        out, lse = lib().attn_fwd(qkv, H, scale, *(drop or ()))
         ctx.save_for_backward(qkv, out, lse)
-        ctx.H, ctx.scale = H, scale
+        ctx.H, ctx.scale, ctx.drop = H, scale, drop
         return out
 
     @staticmethod
     def backward(ctx, dout):
         qkv, out, lse = ctx.saved_tensors
-        return lib().attn_bwd(qkv, out, dout, lse, ctx.H, ctx.scale), None, None
+        return lib().attn_bwd(qkv, out, dout, lse, ctx.H, ctx.scale,
+                              *(ctx.drop or ())), None, None, None
 
 
 def _attn_ok(qkv: torch.Tensor, H: int, hd: int) -> bool:
@@ -416,8 +526,31 @@ def _lens_attention(qkv: torch.Tensor, H: int, hd: int, causal: bool,
     return o.transpose(1, 2).reshape(B, S, H * hd).masked_fill(~valid[:, :, None], 0)
 
 
+def _dropout_attention(qkv: torch.Tensor, H: int, hd: int, causal: bool,
+                       lens: Optional[torch.Tensor], drop) -> torch.Tensor:
+    """Attention with dropped probabilities as an explicit head-split softmax composition (fp32
+    scores, [B, H, S, S] materialised): o = (keep * softmax(q k^T / sqrt(hd)) / (1 - p)) v, with
+    the causal / length masks of ``fused_qkv_attention``."""
+    B, S, _ = qkv.shape
+    pos = torch.arange(S, device=qkv.device)
+    valid = None
+    if lens is not None:
+        valid = pos[None] < lens.to(qkv.device).long().clamp(1, S)[:, None]      # [B, S]
+        qkv = qkv.masked_fill(~valid[:, :, None], 0)
+    q, k, v = qkv_split(qkv, H, H, hd)
+    s = (q.float() @ k.float().transpose(-1, -2)) / math.sqrt(hd)
+    if valid is not None:
+        s = s.masked_fill(~valid[:, None, None, :], float("-inf"))
+    if causal:
+        s = s.masked_fill(pos[None, :] > pos[:, None], float("-inf"))
+    p = torch.softmax(s, -1) * _keep_scaled(s.shape, s.dtype, s.device, drop)
+    o = (p @ v.float()).to(qkv.dtype).transpose(1, 2).reshape(B, S, H * hd)
+    return o if valid is None else o.masked_fill(~valid[:, :, None], 0)
+
+
 def fused_qkv_attention(qkv: torch.Tensor, H: int, hd: int, causal: bool = False,
-                        lens: Optional[torch.Tensor] = None) -> torch.Tensor:
+                        lens: Optional[torch.Tensor] = None, dropout: float = 0.0,
+                        training: bool = True, rng=None) -> torch.Tensor:
     """Multi-head attention (full, or causal with ``causal=True``) straight from the fused
     projection ``qkv [B, S, 3 H hd]`` to ``[B, S, H hd]`` (the output projection's input layout).
     hd = 64 bf16 GPU tensors: non-causal S <= 128 (S % 32 == 0) runs csrc/kernels/attention.hip
@@ -431,8 +564,22 @@ def fused_qkv_attention(qkv: torch.Tensor, H: int, hd: int, causal: bool = False
     are exactly zero on padded rows, and nothing depends on what qkv or the output gradient hold
     there (NaN included). hd = 64 bf16 GPU tensors run the length variants of the flash kernels
     at every S (key tiles and query blocks past a length cost no work; lens is never read on the
-    host); anything else splits the heads and runs SDPA under a key-padding mask."""
+    host); anything else splits the heads and runs SDPA under a key-padding mask.
+
+    ``dropout`` > 0 in training mode drops attention probabilities (kept ones scaled by
+    1 / (1 - p)); ``rng = (seed, offset)`` fixes the mask (default: the next draw of
+    ``dropout_stream``), which ``dropout_mask(seed, offset, [B, H, S, S], p)`` returns. Where
+    csrc/kernels/attention.hip is eligible (no lens, not causal, S <= 128) the mask is applied
+    inside the kernel and nothing is materialised. Every other case with dropout > 0 — S > 128,
+    ``lens``, causal, CPU, or ``attn_kernel`` off — runs an explicit head-split softmax
+    composition in PyTorch with that mask (the flash kernels have no dropout variant yet).
+    dropout = 0 or ``training=False`` is today's dispatch, bit for bit."""
     B, S, _ = qkv.shape
+    drop = _drop(dropout, training, rng)
+    if drop is not None:
+        if lens is None and not causal and _attn_ok(qkv, H, hd):
+            return _AttnFn.apply(qkv, H, 1.0 / math.sqrt(hd), drop)
+        return _dropout_attention(qkv, H, hd, bool(causal), lens, drop)
     if lens is not None:
         if (hd == 64 and _P().flash_attn64 and _gpu_bf16(qkv) and qkv.is_contiguous()
                 and qkv.data_ptr() % 16 == 0):

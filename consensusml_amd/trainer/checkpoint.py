@@ -8,7 +8,8 @@ append-only standard table (`composite_code/rnotebook/cml_targetaml_seanalysis.R
                                          flat-buffer layout (buckets, shards, parameter offsets)
                                          and the PerfPolicy (kernel / fusion switches) in force
     <root>/step_<k>/rank<r>.pt           this rank's engine state (fp32 master / optimizer shard),
-                                         model buffers (BN statistics), RNG states
+                                         model buffers (BN statistics), RNG states, the dropout
+                                         stream's seed and counter (optional key ``dropout``)
     <root>/step_<k>/consensus_table.csv  per-parameter x per-worker gradient statistics of the
                                          checkpoint step (the standard table's training analogue)
     <root>/latest                        name of the newest complete checkpoint
@@ -37,6 +38,7 @@ from typing import Dict, List, Optional
 import torch
 import torch.distributed as dist
 
+from ..ops.transformer import dropout_stream
 from ..parallel.dist import barrier
 from ..perf import policy
 
@@ -77,6 +79,7 @@ def save_checkpoint(root: str, engine, cfg, extra: Optional[dict] = None,
                    for k, v in engine.state_dict().items()},
         "buffers": buffers,
         "rng": _rng_state(engine.device),
+        "dropout": dropout_stream.state_dict(),
         "gens": [g.get_state() for g in gens] if gens else None,
         "extra": extra or {},
     }
@@ -212,6 +215,8 @@ def load_checkpoint(path: str, engine, gens: Optional[list] = None) -> dict:
     torch.set_rng_state(st["rng"]["cpu"])
     if "cuda" in st["rng"] and engine.device.type == "cuda":
         torch.cuda.set_rng_state(st["rng"]["cuda"], engine.device)
+    if same and st.get("dropout"):        # (absent in checkpoints from before dropout)
+        dropout_stream.load_state_dict(st["dropout"])
     if same and gens and st.get("gens"):
         for g, s in zip(gens, st["gens"]):
             g.set_state(s)

@@ -17,6 +17,7 @@ import torch
 
 from ..config import TrainConfig
 from ..models import Task, build_task
+from ..ops.transformer import dropout_stream
 from ..parallel.dist import DistInfo, init_distributed
 from ..parallel.engine import ConsensusEngine
 from ..perf import policy as _P
@@ -42,6 +43,9 @@ class ConsensusTrainer:
             g.manual_seed(cfg.seed * 1000 + self.info.rank * V + v)
             self.gens.append(g)
         self.gen = self.gens[0]
+        # dropout masks (model.dropout): one stream per rank, so ranks draw different masks while
+        # the parameters stay replica-identical
+        dropout_stream.manual_seed(cfg.seed * 1000 + 500 + self.info.rank)
         # native record loader (csrc/runtime): one disjoint data share per global worker
         self.loaders = []
         if cfg.data_path:

@@ -2574,9 +2574,31 @@ std::vector<Tensor> ce_mean(const Tensor& loss, const Tensor& labels, int64_t ig
   return {out, count};
 }
 
+// Dropout arguments of the fused sites (csrc/kernels/dropout.h): thr = round(p * 65536), 0 = none.
+cml::DropSpec drop_spec(int64_t seed, int64_t offset, int64_t thr, const char* op) {
+  TORCH_CHECK(thr >= 0 && thr <= 65535, op, ": dropout threshold must be in [0, 65535]");
+  return {static_cast<uint64_t>(seed), static_cast<uint64_t>(offset), static_cast<uint32_t>(thr)};
+}
+
+// keep mask (uint8, 1 = kept) of `shape` on `device` for (seed, offset): what the fused dropout
+// sites apply to the element with that row-major linear index
+Tensor dropout_mask(int64_t seed, int64_t offset, const std::vector<int64_t>& shape, int64_t thr,
+                    const at::Device& device) {
+  TORCH_CHECK(device.is_cuda(), "dropout_mask: a GPU device");
+  TORCH_CHECK(thr >= 1, "dropout_mask: threshold must be in [1, 65535]");
+  const c10::DeviceGuard guard(device);
+  Tensor keep = at::empty(shape, at::TensorOptions().device(device).dtype(at::kByte));
+  if (keep.numel() == 0) return keep;
+  CML_CHECK_HIP(cml::launch_dropout_mask(keep.data_ptr<uint8_t>(), keep.numel(),
+                                         drop_spec(seed, offset, thr, "dropout_mask"), cur_stream()));
+  return keep;
+}
+
 // x (and res) [.., D] bf16 contiguous; w (and b) [D] bf16. Returns (y, sum|undef, mean|undef, rstd).
+// thr > 0: dropout on res (res given) or on y (see launch_norm_fwd).
 std::vector<Tensor> norm_fwd(const Tensor& x, const optional<Tensor>& res, const Tensor& w,
-                             const optional<Tensor>& b, double eps) {
+                             const optional<Tensor>& b, double eps, int64_t seed, int64_t offset,
+                             int64_t thr) {
   check_bf16c(x, "x");
   const int64_t D = x.size(-1);
   const int64_t M = x.numel() / D;
@@ -2604,13 +2626,15 @@ std::vector<Tensor> norm_fwd(const Tensor& x, const optional<Tensor>& res, const
                                      has_res ? sum.data_ptr() : nullptr,
                                      ln ? mean.data_ptr<float>() : nullptr, rstd.data_ptr<float>(),
                                      M, static_cast<int>(D), static_cast<float>(eps),
-                                     cur_stream()));
+                                     cur_stream(), drop_spec(seed, offset, thr, "norm_fwd")));
   return {y, sum, mean, rstd};
 }
 
-// Returns (dx, dw, db|undef). dres (optional) is added to dx.
+// Returns (dx, dw, db|undef, ddrop|undef). dres (optional) is added to dx. thr > 0: the forward's
+// dropout; drop_res: it acted on the residual input, whose gradient comes back as ddrop.
 std::vector<Tensor> norm_bwd(const Tensor& dy_in, const optional<Tensor>& dres_in, const Tensor& x,
-                             const Tensor& w, const optional<Tensor>& mean, const Tensor& rstd) {
+                             const Tensor& w, const optional<Tensor>& mean, const Tensor& rstd,
+                             int64_t seed, int64_t offset, int64_t thr, bool drop_res) {
   check_bf16c(x, "x");
   const int64_t D = x.size(-1);
   const int64_t M = x.numel() / D;
@@ -2632,14 +2656,17 @@ std::vector<Tensor> norm_bwd(const Tensor& dy_in, const optional<Tensor>& dres_i
   Tensor dx = at::empty_like(x);
   Tensor dw = at::empty_like(w);
   Tensor db = ln ? at::empty_like(w) : Tensor();
+  Tensor ddrop = thr > 0 && drop_res ? at::empty_like(x) : Tensor();
   Tensor work = at::empty({static_cast<int64_t>(cml::norm_workspace_bytes(M, static_cast<int>(D)) / 4 + 1)},
                           x.options().dtype(at::kFloat));
   CML_CHECK_HIP(cml::launch_norm_bwd(ln ? 1 : 0, dy.data_ptr(), dres.defined() ? dres.data_ptr() : nullptr,
                                      x.data_ptr(), w.data_ptr(), ln ? mean->data_ptr<float>() : nullptr,
                                      rstd.data_ptr<float>(), dx.data_ptr(), dw.data_ptr(),
                                      ln ? db.data_ptr() : nullptr, M, static_cast<int>(D),
-                                     work.data_ptr(), cur_stream()));
-  return {dx, dw, db};
+                                     work.data_ptr(), cur_stream(),
+                                     drop_spec(seed, offset, thr, "norm_bwd"), drop_res ? 1 : 0,
+                                     ddrop.defined() ? ddrop.data_ptr() : nullptr));
+  return {dx, dw, db, ddrop};
 }
 
 void check_rope_tables(const optional<Tensor>& c, const optional<Tensor>& s, int64_t S, int64_t hd) {
@@ -2881,7 +2908,8 @@ Tensor swiglu_bwd(const Tensor& dy_in, const Tensor& h) {
 }
 
 // qkv [B, S, 3 H 64] bf16 contiguous -> (O [B, S, H 64], lse fp32 [B, H, S])
-std::vector<Tensor> attn_fwd(const Tensor& qkv, int64_t H, double scale) {
+std::vector<Tensor> attn_fwd(const Tensor& qkv, int64_t H, double scale, int64_t seed,
+                             int64_t offset, int64_t thr) {
   check_bf16c(qkv, "qkv");
   TORCH_CHECK(qkv.dim() == 3 && qkv.size(2) == 3 * H * 64, "attn: qkv must be [B, S, 3 H 64]");
   const int64_t B = qkv.size(0), S = qkv.size(1);
@@ -2891,12 +2919,13 @@ std::vector<Tensor> attn_fwd(const Tensor& qkv, int64_t H, double scale) {
   Tensor lse = at::empty({B, H, S}, qkv.options().dtype(at::kFloat));
   CML_CHECK_HIP(cml::launch_attn_fwd(qkv.data_ptr(), out.data_ptr(), lse.data_ptr<float>(),
                                      static_cast<int>(B), static_cast<int>(S), static_cast<int>(H),
-                                     static_cast<float>(scale), cur_stream()));
+                                     static_cast<float>(scale), cur_stream(),
+                                     drop_spec(seed, offset, thr, "attn_fwd")));
   return {out, lse};
 }
 
 Tensor attn_bwd(const Tensor& qkv, const Tensor& out, const Tensor& dout_in, const Tensor& lse,
-                int64_t H, double scale) {
+                int64_t H, double scale, int64_t seed, int64_t offset, int64_t thr) {
   check_bf16c(qkv, "qkv");
   check_bf16c(out, "out");
   Tensor dout = dout_in.contiguous();
@@ -2913,7 +2942,8 @@ Tensor attn_bwd(const Tensor& qkv, const Tensor& out, const Tensor& dout_in, con
   CML_CHECK_HIP(cml::launch_attn_bwd(qkv.data_ptr(), out.data_ptr(), dout.data_ptr(),
                                      lse.data_ptr<float>(), dqkv.data_ptr(), static_cast<int>(B),
                                      static_cast<int>(S), static_cast<int>(H),
-                                     static_cast<float>(scale), cur_stream()));
+                                     static_cast<float>(scale), cur_stream(),
+                                     drop_spec(seed, offset, thr, "attn_bwd")));
   return dqkv;
 }
 
@@ -3263,7 +3293,8 @@ void colsum_seg(const Tensor& x_in, int64_t nseg, Tensor& out) {
 // (bf16 [nseg, D] views with one common row stride).
 Tensor norm_bwd_seg(const Tensor& dy_in, const optional<Tensor>& dres_in, const Tensor& x,
                     const Tensor& w, const optional<Tensor>& mean, const Tensor& rstd,
-                    int64_t nseg, Tensor& dw_out, const optional<Tensor>& db_out) {
+                    int64_t nseg, Tensor& dw_out, const optional<Tensor>& db_out, int64_t seed,
+                    int64_t offset, int64_t thr, const optional<Tensor>& ddrop_out) {
   check_bf16c(x, "x");
   const int64_t D = x.size(-1);
   const int64_t M = x.numel() / D;
@@ -3295,6 +3326,12 @@ Tensor norm_bwd_seg(const Tensor& dy_in, const optional<Tensor>& dres_in, const 
     TORCH_CHECK(db_out->stride(0) == dw_out.stride(0), "dw_out / db_out: one row stride");
     dbp = db_out->data_ptr();
   }
+  // dropout: ddrop_out given <=> the forward dropped its residual input (its gradient goes there)
+  const bool drop_res = ddrop_out.has_value() && ddrop_out->defined();
+  if (drop_res) {
+    check_bf16c(*ddrop_out, "ddrop_out");
+    TORCH_CHECK(thr > 0 && ddrop_out->sizes() == x.sizes(), "norm_bwd_seg: ddrop_out needs dropout and x's shape");
+  }
   const c10::DeviceGuard guard(x.device());
   Tensor dx = at::empty_like(x);
   Tensor work = at::empty({static_cast<int64_t>(cml::norm_workspace_bytes_seg(M, static_cast<int>(D),
@@ -3304,7 +3341,10 @@ Tensor norm_bwd_seg(const Tensor& dy_in, const optional<Tensor>& dres_in, const 
                                          x.data_ptr(), w.data_ptr(), ln ? mean->data_ptr<float>() : nullptr,
                                          rstd.data_ptr<float>(), dx.data_ptr(), dw_out.data_ptr(), dbp,
                                          M, static_cast<int>(D), static_cast<int>(nseg),
-                                         dw_out.stride(0), work.data_ptr(), cur_stream()));
+                                         dw_out.stride(0), work.data_ptr(), cur_stream(),
+                                         drop_spec(seed, offset, thr, "norm_bwd_seg"),
+                                         drop_res ? 1 : 0,
+                                         drop_res ? ddrop_out->data_ptr() : nullptr));
   return dx;
 }
 
@@ -3354,7 +3394,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("param_out"), py::arg("nbrs"), py::arg("w"), py::arg("w0"), py::arg("clip"),
         py::arg("work"), py::arg("param_out2") = py::none(), py::arg("grid_cap") = 0);
   m.def("colsum_seg", &colsum_seg, "per-segment column sums into strided rows");
-  m.def("norm_bwd_seg", &norm_bwd_seg, "LayerNorm / RMSNorm backward with per-segment dgamma / dbeta");
+  m.def("norm_bwd_seg", &norm_bwd_seg, "LayerNorm / RMSNorm backward with per-segment dgamma / dbeta",
+        py::arg("dy"), py::arg("dres"), py::arg("x"), py::arg("w"), py::arg("mean"), py::arg("rstd"),
+        py::arg("nseg"), py::arg("dw_out"), py::arg("db_out"), py::arg("seed") = 0,
+        py::arg("offset") = 0, py::arg("thr") = 0, py::arg("ddrop_out") = py::none());
+  m.def("dropout_mask", &dropout_mask, "uint8 keep mask of the fused dropout sites",
+        py::arg("seed"), py::arg("offset"), py::arg("shape"), py::arg("thr"), py::arg("device"));
   m.def("conv1x1g_mode", &cml::conv1x1g_mode, "fused 1x1 kernel family: 0 old, 1 glds, 2 auto");
   m.def("set_conv1x1g_mode", &cml::set_conv1x1g_mode, "select the fused 1x1 kernel family");
   m.def("set_conv1x1g_ablate", &cml::set_conv1x1g_ablate, "diagnostics: quad kernel ablation bits");
@@ -3546,8 +3591,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("transpose_bf16", &transpose_bf16, "w.t().contiguous() (LDS-tiled bf16 transpose)");
   m.def("gelu_bwd", &gelu_bwd, "dh = da * gelu'(h) (erf GELU), bf16");
   m.def("ce_part_fold", &ce_part_fold, "per-segment fold of ce_bwd_cs's column partials");
-  m.def("norm_fwd", &norm_fwd, "LayerNorm / RMSNorm (+ residual add) forward");
-  m.def("norm_bwd", &norm_bwd, "LayerNorm / RMSNorm backward (+ residual gradient)");
+  m.def("norm_fwd", &norm_fwd, "LayerNorm / RMSNorm (+ residual add, + dropout) forward",
+        py::arg("x"), py::arg("res"), py::arg("w"), py::arg("b"), py::arg("eps"),
+        py::arg("seed") = 0, py::arg("offset") = 0, py::arg("thr") = 0);
+  m.def("norm_bwd", &norm_bwd, "LayerNorm / RMSNorm backward (+ residual gradient, + dropout)",
+        py::arg("dy"), py::arg("dres"), py::arg("x"), py::arg("w"), py::arg("mean"), py::arg("rstd"),
+        py::arg("seed") = 0, py::arg("offset") = 0, py::arg("thr") = 0, py::arg("drop_res") = false);
   m.def("rope_fwd", &rope_fwd, "QKV split + RoPE into head-major q / k / v");
   m.def("rope_bwd", &rope_bwd, "inverse of rope_fwd (grp > 1: sums per-query-head dk / dv)",
         py::arg("dq"), py::arg("dk"), py::arg("dv"), py::arg("cos"), py::arg("sin"),
@@ -3568,8 +3617,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("causal"), py::arg("scale"), py::arg("lens") = py::none());
   m.def("swiglu_fwd", &swiglu_fwd, "silu(a) * b over [a | b]");
   m.def("swiglu_bwd", &swiglu_bwd, "SwiGLU backward");
-  m.def("attn_fwd", &attn_fwd, "short-sequence MFMA attention forward (fused qkv in)");
-  m.def("attn_bwd", &attn_bwd, "short-sequence MFMA attention backward (fused dqkv out)");
+  m.def("attn_fwd", &attn_fwd, "short-sequence MFMA attention forward (fused qkv in)",
+        py::arg("qkv"), py::arg("H"), py::arg("scale"), py::arg("seed") = 0, py::arg("offset") = 0,
+        py::arg("thr") = 0);
+  m.def("attn_bwd", &attn_bwd, "short-sequence MFMA attention backward (fused dqkv out)",
+        py::arg("qkv"), py::arg("out"), py::arg("dout"), py::arg("lse"), py::arg("H"),
+        py::arg("scale"), py::arg("seed") = 0, py::arg("offset") = 0, py::arg("thr") = 0);
   m.def("split_search", &split_search, "tree-ensemble histogram split search (one level)");
   m.def("svm_smo", &svm_smo, "batched dual C-SVC SMO (one wave per problem)");
   m.def("smo_max_n", &cml::smo_max_n);

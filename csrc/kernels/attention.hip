@@ -27,11 +27,30 @@
 // reads use (sw64 / sw256e below), so staging is 16-B loads + ds_write_b128 only. The first
 // backward (attn_bwd_kernel, CML_ATTN_BWD_V1=1) kept [64][S] transposed copies built with 2-B LDS
 // writes: 122 KB of LDS, one workgroup per CU.
+//
+// Dropout on the probabilities (template flag DROP of the forward and of attn_bwd2_kernel; the
+// first backward has none): the keep bits of dropout.h, index ((b H + h) S + q) S + k, are
+// generated once per workgroup into an S x S bit image in LDS (fill_keep_bits: 2 NT Philox calls
+// per thread, during staging) and applied in registers between the two products, so P is never
+// materialised and lse stays the undropped log-sum-exp. Resources of the instances (hipcc
+// -Rpass-analysis=kernel-resource-usage, VGPRs + AGPRs / LDS bytes / scratch bytes per lane),
+// plain -> DROP:
+//   forward  NT 1   62 + 32 /  8192 / 0  ->   62 + 32 /  8320 / 0
+//            NT 2   62 + 32 / 16384 / 0  ->   57 + 32 / 16896 / 0
+//            NT 3   88 + 48 / 24576 / 0  ->   96 + 48 / 25728 / 0
+//            NT 4  108 + 64 / 32768 / 0  ->  108 + 64 / 34816 / 0
+//   bwd2     NT 1   90 / 12544 / 0       ->  101 / 12672 / 0
+//            NT 2  140 / 25088 / 0       ->  167 / 25600 / 0
+//            NT 3  207 / 37632 / 0       ->  256 / 38784 / 40
+//            NT 4  255 / 50176 / 0       ->  256 / 52224 / 44
+// (bwd2's LDS is dynamic: bwd2_smem). The plain NT 4 backward already sits at the 256-VGPR limit
+// of two waves per SIMD, so its DROP instance spills 11 dwords per lane; occupancy is unchanged.
 #include <math.h>
 
 #include <cstdlib>
 
 #include "common.h"
+#include "dropout.h"
 #include "kernels.h"
 
 namespace cml {
@@ -103,13 +122,34 @@ __device__ __forceinline__ bf16x8_t trfrag256(const char* img, int ka, int kb, i
   return __builtin_bit_cast(bf16x8_t, make_uint4(lo.x, lo.y, hi.x, hi.y));
 }
 
-// ------------------------------------------------------------------------------------- forward
+// ------------------------------------------------------------------------- dropout keep bits
+// The S x S keep bits of one (batch, head) as an LDS image of S rows (queries) x NT words: bit
+// (k & 31) of word [q][k >> 5] is the dropout.h keep bit of linear index (bh S + q) S + k. The
+// image is S S / 8 consecutive mask groups, one byte each, in group order: thread t fills bytes
+// t, t + 64 NT, ... (2 NT Philox calls per thread) during the staging phase, ahead of the barrier
+// that staging needs anyway. A forward lane (one query, keys 32 kt + 8 g + 4 h + j in register
+// 4 g + j of tile kt) then reads its query's NT words; a backward lane (one key, queries in
+// registers) reads word [q][w] of each of its queries and tests bit r, a wave-wide broadcast.
 template <int NT>
+__device__ __forceinline__ void fill_keep_bits(uint32_t* img, const DropArgs& drop, int bh) {
+  constexpr int S = 32 * NT;
+  uint8_t* bytes = reinterpret_cast<uint8_t*>(img);
+  const uint64_t g0 = static_cast<uint64_t>(bh) * (S * S / 8);
+#pragma unroll
+  for (int it = 0; it < 2 * NT; ++it) {
+    const int g = threadIdx.x + it * 64 * NT;
+    bytes[g] = static_cast<uint8_t>(drop_keep8(drop, g0 + g));
+  }
+}
+
+// ------------------------------------------------------------------------------------- forward
+template <int NT, bool DROP>
 __global__ __launch_bounds__(64 * NT) void attn_fwd_kernel(const bf16* __restrict__ qkv,
                                                           bf16* __restrict__ out,
                                                           float* __restrict__ lse, int H,
-                                                          float scale) {
+                                                          float scale, DropArgs drop) {
   constexpr int S = 32 * NT;
+  __shared__ uint32_t Mk[DROP ? S * NT : 1];
   // K and V as swizzled [S][64] row images (sw64); V^T is read by ds_read_b64_tr_b16
   __shared__ __attribute__((aligned(16))) char Ks[S * 128];
   __shared__ __attribute__((aligned(16))) char Vs[S * 128];
@@ -133,6 +173,7 @@ __global__ __launch_bounds__(64 * NT) void attn_fwd_kernel(const bf16* __restric
     *reinterpret_cast<uint4*>(Ks + sw64(row, c)) = kv;
     *reinterpret_cast<uint4*>(Vs + sw64(row, c)) = vv;
   }
+  if constexpr (DROP) fill_keep_bits<NT>(Mk, drop, bh);
   __syncthreads();
   // S^T tiles: acc[kt][i] = S^T[key 32kt + acc_row(i, h)][query q]
   f32x16 acc[NT];
@@ -161,8 +202,19 @@ __global__ __launch_bounds__(64 * NT) void attn_fwd_kernel(const bf16* __restric
       l += p;
     }
   l += __shfl_xor(l, 32, 64);
-  const float inv = 1.f / l;
+  float inv = 1.f / l;
   if (h == 0) lse[static_cast<int64_t>(bh) * S + q] = m + __logf(l);
+  if constexpr (DROP) {
+    // P <- keep * P / (1 - p) in registers (lse above is the undropped one)
+    inv *= drop.scale;
+#pragma unroll
+    for (int kt = 0; kt < NT; ++kt) {
+      const uint32_t wd = Mk[q * NT + kt] >> (4 * h);
+#pragma unroll
+      for (int i = 0; i < 16; ++i)
+        if (!((wd >> (8 * (i >> 2) + (i & 3))) & 1u)) acc[kt][i] = 0.f;
+    }
+  }
   // O^T = V^T P^T over 2 d-tiles (V^T fragments by transposed reads of the V rows)
   f32x16 o[2] = {zero16(), zero16()};
 #pragma unroll
@@ -341,16 +393,20 @@ constexpr size_t bwd_smem() {
 //              in registers as bf16 meanwhile) into the space of Q and dO, which are dead by then.
 // LDS 3 S 128 B + 2 S 4 B (49 KB at S = 128, was 122 KB): two workgroups per CU, so one
 // workgroup's load phase overlaps the other's MFMAs.
+// DROP: the keep-bit image (fill_keep_bits, S NT words) follows Lq; with M = keep / (1 - p),
+//   dV^T += dO^T (P o M),  dS = P o (M o dP - D)  (D is unchanged: O already holds M).
 template <int NT>
-constexpr size_t bwd2_smem() { return 3 * (32 * NT) * 128 + 2 * (32 * NT) * sizeof(float); }
+constexpr size_t bwd2_smem(bool drop = false) {
+  return 3 * (32 * NT) * 128 + 2 * (32 * NT) * sizeof(float) + (drop ? 32 * NT * NT * 4 : 0);
+}
 
-template <int NT>
+template <int NT, bool DROP>
 __global__ __launch_bounds__(64 * NT, 2) void attn_bwd2_kernel(const bf16* __restrict__ qkv,
                                                               const bf16* __restrict__ out,
                                                               const bf16* __restrict__ dout,
                                                               const float* __restrict__ lse,
                                                               bf16* __restrict__ dqkv, int H,
-                                                              float scale) {
+                                                              float scale, DropArgs drop) {
   constexpr int S = 32 * NT;
   extern __shared__ __attribute__((aligned(16))) char smem2[];
   char* Qs = smem2;                    // [S][64]
@@ -359,6 +415,7 @@ __global__ __launch_bounds__(64 * NT, 2) void attn_bwd2_kernel(const bf16* __res
   char* dSt = smem2;                   // [S keys][S queries], over Q and dO after phase 1
   float* Dq = reinterpret_cast<float*>(Ks + S * 128);   // [S] rowsum(dO * O)
   float* Lq = Dq + S;                                   // [S] logsumexp
+  uint32_t* Mk = reinterpret_cast<uint32_t*>(Lq + S);   // [S][NT] keep bits (DROP only)
   const int bh = blockIdx.x, b = bh / H, hh = bh % H;
   const int64_t rs = 3LL * H * kHD;
   const int64_t os = static_cast<int64_t>(H) * kHD;
@@ -401,6 +458,7 @@ __global__ __launch_bounds__(64 * NT, 2) void attn_bwd2_kernel(const bf16* __res
       Lq[row] = lse[static_cast<int64_t>(bh) * S + row];
     }
   }
+  if constexpr (DROP) fill_keep_bits<NT>(Mk, drop, bh);
   __syncthreads();
   bf16x8_t kf[4];
 #pragma unroll
@@ -422,8 +480,14 @@ __global__ __launch_bounds__(64 * NT, 2) void attn_bwd2_kernel(const bf16* __res
     for (int i = 0; i < 16; ++i) {
       const int qi = 32 * qt + acc_row(i, h);
       const float p = __expf(fmaf(s[i], scale, -Lq[qi]));
-      s[i] = p;
-      dp[i] = p * (dp[i] - Dq[qi]);
+      if constexpr (DROP) {
+        const float mk = (Mk[qi * NT + w] >> r) & 1u ? drop.scale : 0.f;
+        s[i] = p * mk;
+        dp[i] = p * (mk * dp[i] - Dq[qi]);
+      } else {
+        s[i] = p;
+        dp[i] = p * (dp[i] - Dq[qi]);
+      }
     }
 #pragma unroll
     for (int g = 0; g < 4; ++g)
@@ -489,23 +553,34 @@ __global__ __launch_bounds__(64 * NT, 2) void attn_bwd2_kernel(const bf16* __res
 }  // namespace
 
 hipError_t launch_attn_fwd(const void* qkv, void* out, float* lse, int B, int S, int H,
-                           float scale, hipStream_t st) {
+                           float scale, hipStream_t st, const DropSpec& drop) {
   if (B < 1 || H < 1 || S % 32 || S < 32 || S > 128) return hipErrorInvalidValue;
+  if (drop.thr && !drop_valid(drop)) return hipErrorInvalidValue;
   const dim3 grid(static_cast<unsigned>(B * H));
   auto* q = reinterpret_cast<const bf16*>(qkv);
   auto* o = reinterpret_cast<bf16*>(out);
+  const DropArgs da = drop_args(drop);
+#define CML_AF(NT)                                                                          \
+  do {                                                                                      \
+    if (drop.thr) attn_fwd_kernel<NT, true><<<grid, 64 * NT, 0, st>>>(q, o, lse, H, scale, da); \
+    else attn_fwd_kernel<NT, false><<<grid, 64 * NT, 0, st>>>(q, o, lse, H, scale, da);      \
+  } while (0)
   switch (S / 32) {
-    case 1: attn_fwd_kernel<1><<<grid, 64, 0, st>>>(q, o, lse, H, scale); break;
-    case 2: attn_fwd_kernel<2><<<grid, 128, 0, st>>>(q, o, lse, H, scale); break;
-    case 3: attn_fwd_kernel<3><<<grid, 192, 0, st>>>(q, o, lse, H, scale); break;
-    default: attn_fwd_kernel<4><<<grid, 256, 0, st>>>(q, o, lse, H, scale); break;
+    case 1: CML_AF(1); break;
+    case 2: CML_AF(2); break;
+    case 3: CML_AF(3); break;
+    default: CML_AF(4); break;
   }
+#undef CML_AF
   return hipGetLastError();
 }
 
 hipError_t launch_attn_bwd(const void* qkv, const void* out, const void* dout, const float* lse,
-                           void* dqkv, int B, int S, int H, float scale, hipStream_t st) {
+                           void* dqkv, int B, int S, int H, float scale, hipStream_t st,
+                           const DropSpec& drop) {
   if (B < 1 || H < 1 || S % 32 || S < 32 || S > 128) return hipErrorInvalidValue;
+  if (drop.thr && !drop_valid(drop)) return hipErrorInvalidValue;
+  const DropArgs da = drop_args(drop);
   const dim3 grid(static_cast<unsigned>(B * H));
   auto* q = reinterpret_cast<const bf16*>(qkv);
   auto* o = reinterpret_cast<const bf16*>(out);
@@ -523,23 +598,30 @@ hipError_t launch_attn_bwd(const void* qkv, const void* out, const void* dout, c
     }                                                                                        \
     attn_bwd_kernel<NT><<<grid, 64 * NT, bwd_smem<NT>(), st>>>(q, o, d, lse, g, H, scale);    \
   } while (0)
-#define CML_AB2(NT)                                                                          \
-  do {                                                                                       \
-    static bool attr_set = false;                                                            \
-    if (!attr_set) {                                                                         \
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd2_kernel<NT>), \
-                                         hipFuncAttributeMaxDynamicSharedMemorySize,         \
-                                         static_cast<int>(bwd2_smem<NT>()));                 \
-      if (e != hipSuccess) return e;                                                         \
-      attr_set = true;                                                                       \
-    }                                                                                        \
-    attn_bwd2_kernel<NT><<<grid, 64 * NT, bwd2_smem<NT>(), st>>>(q, o, d, lse, g, H, scale);  \
+#define CML_AB2D(NT, DROP)                                                                    \
+  do {                                                                                        \
+    static bool attr_set = false;                                                             \
+    if (!attr_set) {                                                                          \
+      hipError_t e = hipFuncSetAttribute(                                                     \
+          reinterpret_cast<const void*>(attn_bwd2_kernel<NT, DROP>),                          \
+          hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(bwd2_smem<NT>(DROP))); \
+      if (e != hipSuccess) return e;                                                          \
+      attr_set = true;                                                                        \
+    }                                                                                         \
+    attn_bwd2_kernel<NT, DROP><<<grid, 64 * NT, bwd2_smem<NT>(DROP), st>>>(q, o, d, lse, g, H, \
+                                                                            scale, da);       \
+  } while (0)
+#define CML_AB2(NT)            \
+  do {                         \
+    if (drop.thr) CML_AB2D(NT, true); \
+    else CML_AB2D(NT, false);  \
   } while (0)
   static const bool v1 = [] {
     const char* e = std::getenv("CML_ATTN_BWD_V1");
     return e && e[0] == '1';
   }();
   if (v1) {
+    if (drop.thr) return hipErrorInvalidValue;   // the first backward has no dropout variant
     switch (S / 32) {
       case 1: CML_AB(1); break;
       case 2: CML_AB(2); break;
@@ -556,6 +638,7 @@ hipError_t launch_attn_bwd(const void* qkv, const void* out, const void* dout, c
   }
 #undef CML_AB
 #undef CML_AB2
+#undef CML_AB2D
   return hipGetLastError();
 }
 

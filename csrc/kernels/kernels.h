@@ -393,20 +393,33 @@ hipError_t launch_gelu_bwd(const void* da, const void* h, void* dh, int64_t n, h
 // LayerNorm (ln = 1, with bias b and mean) or RMSNorm (ln = 0) over rows of D (D % 8 == 0,
 // D <= 4096). res != null: normalise x + res and write the bf16 sum to `sum`.
 // Backward: dx (+ dres if given) and dw (+ db) via norm_workspace_bytes of partials.
+// Dropout (dropout.h; drop.thr = 0: none, today's kernels): a counter-based mask over the linear
+// index row * D + col, regenerated by the backward from the same (seed, offset).
+//   res != null: sum = x + keep * res / (1 - p), y = norm(sum); the backward also writes
+//                ddrop = keep * dx / (1 - p) (the gradient of res, exactly 0 where dropped).
+//   res == null: y = keep * norm(x) / (1 - p); the backward masks dy on load (ddrop unused).
+struct DropSpec {
+  uint64_t seed = 0, offset = 0;
+  uint32_t thr = 0;   // round(p * 65536) in [1, 65535]; 0 = no dropout
+};
 size_t norm_workspace_bytes(int64_t M, int D);
 hipError_t launch_norm_fwd(int ln, const void* x, const void* res, const void* w, const void* b,
                            void* y, void* sum, float* mean, float* rstd, int64_t M, int D,
-                           float eps, hipStream_t stream);
+                           float eps, hipStream_t stream, const DropSpec& drop = {});
 hipError_t launch_norm_bwd(int ln, const void* dy, const void* dres, const void* x,
                            const void* w, const float* mean, const float* rstd, void* dx,
-                           void* dw, void* db, int64_t M, int D, void* work, hipStream_t stream);
+                           void* dw, void* db, int64_t M, int D, void* work, hipStream_t stream,
+                           const DropSpec& drop = {}, int drop_res = 0, void* ddrop = nullptr);
+// keep[i] = 1 | 0 (uint8) for linear indices i < n of the dropout.h mask function
+hipError_t launch_dropout_mask(uint8_t* keep, int64_t n, const DropSpec& drop, hipStream_t stream);
 // Segmented backward (batched virtual workers): the M rows are nseg equal segments; segment z's
 // dgamma / dbeta go to dw / db + z ostride (bf16). Workspace: norm_workspace_bytes_seg.
 size_t norm_workspace_bytes_seg(int64_t M, int D, int nseg);
 hipError_t launch_norm_bwd_seg(int ln, const void* dy, const void* dres, const void* x,
                                const void* w, const float* mean, const float* rstd, void* dx,
                                void* dw, void* db, int64_t M, int D, int nseg, int64_t ostride,
-                               void* work, hipStream_t stream);
+                               void* work, hipStream_t stream, const DropSpec& drop = {},
+                               int drop_res = 0, void* ddrop = nullptr);
 // qkv [B, S, (H + 2 KV) hd] -> q [B, H, S, hd], k / v [B, KV, S, hd] with interleaved-pair RoPE
 // on q / k from fp32 cos / sin [S, hd / 2] (null: no rotation); backward is the inverse.
 hipError_t launch_rope_fwd(const void* qkv, const float* cosb, const float* sinb, void* q, void* k,
@@ -458,11 +471,14 @@ hipError_t launch_swiglu_bwd(const void* dy, const void* h, void* dh, int64_t M,
                              hipStream_t stream);
 // Short-sequence attention (S % 32 == 0, S <= 128, head dim 64, no mask) on MFMA: reads the
 // fused projection qkv [B, S, 3, H, 64], writes O [B, S, H * 64] and lse fp32 [B, H, S];
-// backward writes dqkv in the fused layout.
+// backward writes dqkv in the fused layout. Dropout (drop.thr > 0) acts on the probabilities,
+// mask index ((b * H + h) * S + q) * S + k; lse stays the undropped log-sum-exp. The first
+// backward (CML_ATTN_BWD_V1=1) has no dropout variant: -> hipErrorInvalidValue.
 hipError_t launch_attn_fwd(const void* qkv, void* out, float* lse, int B, int S, int H,
-                           float scale, hipStream_t stream);
+                           float scale, hipStream_t stream, const DropSpec& drop = {});
 hipError_t launch_attn_bwd(const void* qkv, const void* out, const void* dout, const float* lse,
-                           void* dqkv, int B, int S, int H, float scale, hipStream_t stream);
+                           void* dqkv, int B, int S, int H, float scale, hipStream_t stream,
+                           const DropSpec& drop = {});
 // Tree-ensemble split search, one level of T trees x L nodes: per (tree, node) the best
 // (gain, candidate slot, bin) over its kk candidate features (feats [T, L, kk]) from the binned
 // samples Xb [n, p] (uint8, B <= 64 bins) of that node (node_local [T, n], -1 = not in the level),

@@ -10,7 +10,9 @@
 //   * RMSNorm / LayerNorm: one wave (D <= 1024) or four waves per row, the whole row held in
 //     registers between its reductions (wave shuffles, + one LDS exchange for 4-wave rows) and
 //     its use; the backward's dweight / dbias are per-row-group partial rows folded by a
-//     fixed-order column kernel (deterministic, no atomics).
+//     fixed-order column kernel (deterministic, no atomics). Hidden dropout rides in the same
+//     passes (template flags): the counter-based mask of dropout.h is regenerated per 16-B chunk
+//     in registers, forward and backward, so no mask or dropped activation is ever stored.
 //   * RoPE: reads the fused [B, S, (H + 2 KV) hd] projection once and writes q / k rotated and v,
 //     each already [B, heads, S, hd] contiguous (the transpose copy is fused away); the backward
 //     writes the fused projection gradient in one pass (inverse rotation, v copied).
@@ -20,6 +22,7 @@
 #include <cstdlib>
 
 #include "common.h"
+#include "dropout.h"
 #include "kernels.h"
 
 namespace cml {
@@ -329,9 +332,15 @@ __device__ __forceinline__ void row_sum2(float& a, float& b, float* red, int& pa
   }
 }
 
+// the dropout.h mask group of the 16-B chunk at column c of row r
+__device__ __forceinline__ uint64_t row_group(int64_t r, int D, int c) {
+  return static_cast<uint64_t>(r * D + c) >> 3;
+}
+
 // LN (layer norm, with beta) or RMS (no mean, no beta). RES: y = norm(x + res), and the bf16 sum is
-// written to `sum` (the backward's input).
-template <int NV, int WPR, bool LN, bool RES>
+// written to `sum` (the backward's input). DROP (dropout.h): the mask acts on res before the add
+// (RES) or on y on its way to the store (no RES), one Philox call per 16-B chunk.
+template <int NV, int WPR, bool LN, bool RES, bool DROP>
 __global__ __launch_bounds__(kTB) void norm_fwd_kernel(const bf16* __restrict__ x,
                                                       const bf16* __restrict__ res,
                                                       const bf16* __restrict__ w,
@@ -339,7 +348,7 @@ __global__ __launch_bounds__(kTB) void norm_fwd_kernel(const bf16* __restrict__ 
                                                       bf16* __restrict__ y, bf16* __restrict__ sum,
                                                       float* __restrict__ mean_out,
                                                       float* __restrict__ rstd_out, int64_t M,
-                                                      int D, float eps) {
+                                                      int D, float eps, DropArgs drop) {
   __shared__ float red[2 * kWPB * 2];
   int parity = 0;
   const int lane = threadIdx.x & 63;
@@ -353,6 +362,13 @@ __global__ __launch_bounds__(kTB) void norm_fwd_kernel(const bf16* __restrict__ 
   if constexpr (RES) {
     float a[NV][8];
     row_load<NV, WPR>(res + r * D, D, sub, lane, a);
+    if constexpr (DROP) {
+#pragma unroll
+      for (int i = 0; i < NV; ++i) {
+        const int c = chunk_col<NV, WPR>(i, sub, lane);
+        if (c < D) drop_apply8(drop, row_group(r, D, c), a[i]);
+      }
+    }
 #pragma unroll
     for (int i = 0; i < NV; ++i)
 #pragma unroll
@@ -396,6 +412,7 @@ __global__ __launch_bounds__(kTB) void norm_fwd_kernel(const bf16* __restrict__ 
         if constexpr (LN) o += bv[k];
         v[i][k] = o;
       }
+      if constexpr (DROP && !RES) drop_apply8(drop, row_group(r, D, c), v[i]);
     }
   }
   row_store<NV, WPR>(y + r * D, D, sub, lane, v);
@@ -415,7 +432,10 @@ __global__ __launch_bounds__(kTB) void norm_fwd_kernel(const bf16* __restrict__ 
 // Segments (batched virtual workers): the M rows are nseg consecutive segments of Ms rows and
 // every workgroup works inside one segment (nbs workgroups per segment), so the partial rows of
 // segment s are part[s nbs .. (s + 1) nbs) and fold to that worker's own dgamma / dbeta.
-template <int NV, int WPR, bool LN, bool DR>
+// DROP (dropout.h), the forward's mask regenerated per 16-B chunk: 1 = the forward dropped its
+// residual input: ddrop = keep * dx / (1 - p) is written as a second output of the same pass
+// (exactly 0 where dropped); 2 = the forward dropped y: dy is masked on load.
+template <int NV, int WPR, bool LN, bool DR, int DROP>
 __global__ __launch_bounds__(kTB) void norm_bwd_kernel(const bf16* __restrict__ dy,
                                                       const bf16* __restrict__ dres,
                                                       const bf16* __restrict__ x,
@@ -424,7 +444,8 @@ __global__ __launch_bounds__(kTB) void norm_bwd_kernel(const bf16* __restrict__ 
                                                       const float* __restrict__ rstd,
                                                       bf16* __restrict__ dx, int64_t Mtot, int D,
                                                       float* __restrict__ part, int64_t Ms,
-                                                      int nbs) {
+                                                      int nbs, DropArgs drop,
+                                                      bf16* __restrict__ ddrop) {
   __shared__ float red[2 * kWPB * 2];
   int parity = 0;
   const int lane = threadIdx.x & 63;
@@ -460,6 +481,13 @@ __global__ __launch_bounds__(kTB) void norm_bwd_kernel(const bf16* __restrict__ 
       row_load<NV, WPR>(dy + rn * D, D, sub, lane, dn);
       if constexpr (DR) row_load<NV, WPR>(dres + rn * D, D, sub, lane, en);
     }
+    if constexpr (DROP == 2) {
+#pragma unroll
+      for (int i = 0; i < NV; ++i) {
+        const int c = chunk_col<NV, WPR>(i, sub, lane);
+        if (c < D) drop_apply8(drop, row_group(r, D, c), dv[i]);
+      }
+    }
     const float rs = rstd[r];
     const float mu = LN ? mean[r] : 0.f;
     float sg = 0.f, sgx = 0.f;
@@ -489,6 +517,16 @@ __global__ __launch_bounds__(kTB) void norm_bwd_kernel(const bf16* __restrict__ 
         for (int k = 0; k < 8; ++k) dv[i][k] += ev[i][k];
     }
     row_store<NV, WPR>(dx + r * D, D, sub, lane, dv);
+    if constexpr (DROP == 1) {
+#pragma unroll
+      for (int i = 0; i < NV; ++i) {
+        const int c = chunk_col<NV, WPR>(i, sub, lane);
+        if (c < D) {
+          drop_apply8(drop, row_group(r, D, c), dv[i]);
+          store_bf16<8>(ddrop + r * D + c, dv[i]);
+        }
+      }
+    }
 #pragma unroll
     for (int i = 0; i < NV; ++i)
 #pragma unroll
@@ -776,6 +814,20 @@ __global__ __launch_bounds__(kTB) void colsum_partial_kernel(const bf16* __restr
   }
 }
 
+// ============================================================================ dropout mask
+// keep[i] = 1 | 0 for i < n: one lane per group of 8 (dropout.h), what the fused sites apply
+__global__ __launch_bounds__(kTB) void dropout_mask_kernel(uint8_t* __restrict__ keep, int64_t n,
+                                                          DropArgs drop) {
+  const int64_t ng = (n + 7) / 8;
+  const int64_t stride = static_cast<int64_t>(gridDim.x) * kTB;
+  for (int64_t g = static_cast<int64_t>(blockIdx.x) * kTB + threadIdx.x; g < ng; g += stride) {
+    const uint32_t bits = drop_keep8(drop, static_cast<uint64_t>(g));
+#pragma unroll
+    for (int e = 0; e < 8; ++e)
+      if (g * 8 + e < n) keep[g * 8 + e] = (bits >> e) & 1u;
+  }
+}
+
 // CML_STREAM_GRID_CAP: the most workgroups of an elementwise launch (default 8192; 0 = no cap)
 int stream_grid(int64_t work_items) {
   static const int cap = [] {
@@ -888,10 +940,15 @@ namespace {
 template <int NV, int WPR>
 void norm_fwd_t(bool ln, bool resid, const bf16* x, const bf16* res, const bf16* w, const bf16* b,
                 bf16* y, bf16* sum, float* mean, float* rstd, int64_t M, int D, float eps,
-                hipStream_t st) {
+                hipStream_t st, const DropSpec& drop) {
   constexpr int kRPB = kWPB / WPR;
   const unsigned g = static_cast<unsigned>((M + kRPB - 1) / kRPB);
-#define CML_NF(L, R) norm_fwd_kernel<NV, WPR, L, R><<<g, kTB, 0, st>>>(x, res, w, b, y, sum, mean, rstd, M, D, eps)
+  const DropArgs da = drop_args(drop);
+#define CML_NF(L, R)                                                                              \
+  do {                                                                                            \
+    if (drop.thr) norm_fwd_kernel<NV, WPR, L, R, true><<<g, kTB, 0, st>>>(x, res, w, b, y, sum, mean, rstd, M, D, eps, da); \
+    else norm_fwd_kernel<NV, WPR, L, R, false><<<g, kTB, 0, st>>>(x, res, w, b, y, sum, mean, rstd, M, D, eps, da); \
+  } while (0)
   if (ln && resid) CML_NF(true, true);
   else if (ln) CML_NF(true, false);
   else if (resid) CML_NF(false, true);
@@ -902,14 +959,24 @@ void norm_fwd_t(bool ln, bool resid, const bf16* x, const bf16* res, const bf16*
 template <int NV, int WPR>
 void norm_bwd_t(bool ln, const bf16* dy, const bf16* dr, const bf16* x, const bf16* w,
                 const float* mean, const float* rstd, bf16* dx, int64_t M, int D, float* part,
-                int nblk, hipStream_t st, int64_t Ms, int nseg) {
+                int nblk, hipStream_t st, int64_t Ms, int nseg, const DropSpec& drop, int drop_res,
+                bf16* ddrop) {
   const unsigned g = static_cast<unsigned>(nblk) * nseg;
-#define CML_NB(L, R) norm_bwd_kernel<NV, WPR, L, R><<<g, kTB, 0, st>>>(dy, dr, x, w, mean, rstd, dx, M, D, part, Ms, nblk)
+  const DropArgs da = drop_args(drop);
+  const int mode = !drop.thr ? 0 : drop_res ? 1 : 2;   // (2: a plain norm, never with dr)
+#define CML_NBD(L, R, DM) norm_bwd_kernel<NV, WPR, L, R, DM><<<g, kTB, 0, st>>>(dy, dr, x, w, mean, rstd, dx, M, D, part, Ms, nblk, da, ddrop)
+#define CML_NB(L, R)                     \
+  do {                                   \
+    if (mode == 0) CML_NBD(L, R, 0);     \
+    else if (mode == 1) CML_NBD(L, R, 1); \
+    else CML_NBD(L, false, 2);           \
+  } while (0)
   if (ln && dr) CML_NB(true, true);
   else if (ln) CML_NB(true, false);
   else if (dr) CML_NB(false, true);
   else CML_NB(false, false);
 #undef CML_NB
+#undef CML_NBD
 }
 }  // namespace
 
@@ -920,9 +987,10 @@ size_t norm_workspace_bytes(int64_t M, int D) {
 
 hipError_t launch_norm_fwd(int ln, const void* x, const void* res, const void* w, const void* b,
                            void* y, void* sum, float* mean, float* rstd, int64_t M, int D,
-                           float eps, hipStream_t st) {
+                           float eps, hipStream_t st, const DropSpec& drop) {
   const NormGeom g = norm_geom(D);
   if (M < 1 || D % 8 || g.nv == 0 || (ln && (!b || !mean)) || (res && !sum)) return hipErrorInvalidValue;
+  if (drop.thr && !drop_valid(drop)) return hipErrorInvalidValue;
   auto* xb = reinterpret_cast<const bf16*>(x);
   auto* rb = reinterpret_cast<const bf16*>(res);
   auto* wb = reinterpret_cast<const bf16*>(w);
@@ -930,10 +998,10 @@ hipError_t launch_norm_fwd(int ln, const void* x, const void* res, const void* w
   auto* yb = reinterpret_cast<bf16*>(y);
   auto* sb = reinterpret_cast<bf16*>(sum);
   const bool r = res != nullptr;
-  if (g.wpr == 1 && g.nv == 1) norm_fwd_t<1, 1>(ln, r, xb, rb, wb, bb, yb, sb, mean, rstd, M, D, eps, st);
-  else if (g.wpr == 1) norm_fwd_t<2, 1>(ln, r, xb, rb, wb, bb, yb, sb, mean, rstd, M, D, eps, st);
-  else if (g.nv == 1) norm_fwd_t<1, 4>(ln, r, xb, rb, wb, bb, yb, sb, mean, rstd, M, D, eps, st);
-  else norm_fwd_t<2, 4>(ln, r, xb, rb, wb, bb, yb, sb, mean, rstd, M, D, eps, st);
+  if (g.wpr == 1 && g.nv == 1) norm_fwd_t<1, 1>(ln, r, xb, rb, wb, bb, yb, sb, mean, rstd, M, D, eps, st, drop);
+  else if (g.wpr == 1) norm_fwd_t<2, 1>(ln, r, xb, rb, wb, bb, yb, sb, mean, rstd, M, D, eps, st, drop);
+  else if (g.nv == 1) norm_fwd_t<1, 4>(ln, r, xb, rb, wb, bb, yb, sb, mean, rstd, M, D, eps, st, drop);
+  else norm_fwd_t<2, 4>(ln, r, xb, rb, wb, bb, yb, sb, mean, rstd, M, D, eps, st, drop);
   return hipGetLastError();
 }
 
@@ -946,11 +1014,15 @@ size_t norm_workspace_bytes_seg(int64_t M, int D, int nseg) {
 hipError_t launch_norm_bwd_seg(int ln, const void* dy, const void* dres, const void* x,
                                const void* w, const float* mean, const float* rstd, void* dx,
                                void* dw, void* db, int64_t M, int D, int nseg, int64_t ostride,
-                               void* work, hipStream_t st) {
+                               void* work, hipStream_t st, const DropSpec& drop, int drop_res,
+                               void* ddrop) {
   const NormGeom g = norm_geom(D);
   if (M < 1 || D % 8 || g.nv == 0 || (ln && (!db || !mean)) || nseg < 1 || M % nseg ||
       nseg > 65535)
     return hipErrorInvalidValue;
+  // dropped residual: its gradient needs a destination; dropped output: no stream gradient
+  if (drop.thr && (!drop_valid(drop) || (drop_res ? !ddrop : dres != nullptr))) return hipErrorInvalidValue;
+  auto* ddb = reinterpret_cast<bf16*>(ddrop);
   const int64_t Ms = M / nseg;
   const int ngrp = norm_bwd_blocks(Ms, g.wpr);
   auto* part = reinterpret_cast<float*>(work);
@@ -959,10 +1031,10 @@ hipError_t launch_norm_bwd_seg(int ln, const void* dy, const void* dres, const v
   auto* xb = reinterpret_cast<const bf16*>(x);
   auto* wb = reinterpret_cast<const bf16*>(w);
   auto* dxb = reinterpret_cast<bf16*>(dx);
-  if (g.wpr == 1 && g.nv == 1) norm_bwd_t<1, 1>(ln, dyb, drb, xb, wb, mean, rstd, dxb, M, D, part, ngrp, st, Ms, nseg);
-  else if (g.wpr == 1) norm_bwd_t<2, 1>(ln, dyb, drb, xb, wb, mean, rstd, dxb, M, D, part, ngrp, st, Ms, nseg);
-  else if (g.nv == 1) norm_bwd_t<1, 4>(ln, dyb, drb, xb, wb, mean, rstd, dxb, M, D, part, ngrp, st, Ms, nseg);
-  else norm_bwd_t<2, 4>(ln, dyb, drb, xb, wb, mean, rstd, dxb, M, D, part, ngrp, st, Ms, nseg);
+  if (g.wpr == 1 && g.nv == 1) norm_bwd_t<1, 1>(ln, dyb, drb, xb, wb, mean, rstd, dxb, M, D, part, ngrp, st, Ms, nseg, drop, drop_res, ddb);
+  else if (g.wpr == 1) norm_bwd_t<2, 1>(ln, dyb, drb, xb, wb, mean, rstd, dxb, M, D, part, ngrp, st, Ms, nseg, drop, drop_res, ddb);
+  else if (g.nv == 1) norm_bwd_t<1, 4>(ln, dyb, drb, xb, wb, mean, rstd, dxb, M, D, part, ngrp, st, Ms, nseg, drop, drop_res, ddb);
+  else norm_bwd_t<2, 4>(ln, dyb, drb, xb, wb, mean, rstd, dxb, M, D, part, ngrp, st, Ms, nseg, drop, drop_res, ddb);
   fold_kernel<<<dim3((D + 15) / 16, ln ? 2 : 1, nseg), kTB, 0, st>>>(
       part, ngrp, 2 * static_cast<int64_t>(D), D, reinterpret_cast<bf16*>(dw),
       reinterpret_cast<bf16*>(db), ostride);
@@ -971,8 +1043,16 @@ hipError_t launch_norm_bwd_seg(int ln, const void* dy, const void* dres, const v
 
 hipError_t launch_norm_bwd(int ln, const void* dy, const void* dres, const void* x,
                            const void* w, const float* mean, const float* rstd, void* dx,
-                           void* dw, void* db, int64_t M, int D, void* work, hipStream_t st) {
-  return launch_norm_bwd_seg(ln, dy, dres, x, w, mean, rstd, dx, dw, db, M, D, 1, 0, work, st);
+                           void* dw, void* db, int64_t M, int D, void* work, hipStream_t st,
+                           const DropSpec& drop, int drop_res, void* ddrop) {
+  return launch_norm_bwd_seg(ln, dy, dres, x, w, mean, rstd, dx, dw, db, M, D, 1, 0, work, st, drop,
+                             drop_res, ddrop);
+}
+
+hipError_t launch_dropout_mask(uint8_t* keep, int64_t n, const DropSpec& drop, hipStream_t st) {
+  if (n < 1 || !drop_valid(drop)) return hipErrorInvalidValue;
+  dropout_mask_kernel<<<stream_grid((n + 7) / 8), kTB, 0, st>>>(keep, n, drop_args(drop));
+  return hipGetLastError();
 }
 
 hipError_t launch_rope_fwd(const void* qkv, const float* cosb, const float* sinb, void* q, void* k,
