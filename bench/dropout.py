@@ -12,6 +12,11 @@ warm-up of three calls each; median, min and max over the repetitions), at BERT-
   step        the bert_base training step of ``bench/configs.py --config bert_geomed`` (batch 64,
               seq 128, geometric median, AdamW) at model.dropout 0 and 0.1, one trainer per
               setting in one process, stepped in turn
+  flash64     B x 12 heads x S x 64 at 16 x 512 and 32 x 256: the flash kernels of
+              flash_attn64.hip at p = 0, their dropout instantiations at p = 0.1, and the head-split
+              softmax composition (``_dropout_attention``: fp32 scores and a [B, H, S, S] mask
+              materialised) that served these shapes before; then the same bert_base step at
+              batch 16, seq 512. One JSON line per shape and one for the step
 Two instances of the p = 0 setting run in every group ("p0" / "p0_again"): their difference is the
 same-setting spread a difference between settings has to exceed. One JSON line per group.
 """
@@ -83,12 +88,13 @@ def run_attention(reps: int, dev) -> dict:
     return _report("attention", t, B=B, H=H, S=S, hd=hd)
 
 
-def run_step(reps: int, dev) -> dict:
+def run_step(reps: int, dev, batch=None, seq_len=None) -> dict:
     from configs import CONFIGS
     from consensusml_amd import TrainConfig
     from consensusml_amd.parallel.dist import DistInfo
     from consensusml_amd.trainer.trainer import ConsensusTrainer
-    c = CONFIGS["bert_geomed"]
+    c = dict(CONFIGS["bert_geomed"])
+    c["batch"], c["seq_len"] = batch or c["batch"], seq_len or c["seq_len"]
 
     def trainer(p):
         cfg = TrainConfig()
@@ -102,21 +108,46 @@ def run_step(reps: int, dev) -> dict:
     return _report("step", t, config="bert_geomed", batch=c["batch"], seq_len=c["seq_len"])
 
 
+def run_flash64(reps: int, dev) -> list:
+    from consensusml_amd.ops import transformer as T
+    H, hd, out = 12, 64, []
+    for B, S in ((16, 512), (32, 256)):
+        g = torch.Generator(device=dev).manual_seed(2)
+        qkv = torch.randn(B, S, 3 * H * hd, generator=g, device=dev).bfloat16().requires_grad_(True)
+        do = torch.randn(B, S, H * hd, generator=g, device=dev).bfloat16()
+
+        def fused(p):
+            torch.autograd.grad(T.fused_qkv_attention(qkv, H, hd, dropout=p), qkv, do)
+
+        def composed():
+            o = T._dropout_attention(qkv, H, hd, False, None, T._drop(0.1, True, None))
+            torch.autograd.grad(o, qkv, do)
+        t = alternate({"p0": lambda: fused(0.0), "fused_p01": lambda: fused(0.1),
+                       "unfused_p01": composed, "p0_again": lambda: fused(0.0)}, reps)
+        out.append(_report("flash64", t, B=B, H=H, S=S, hd=hd))
+        torch.cuda.empty_cache()
+    out.append(run_step(reps, dev, batch=16, seq_len=512))
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--groups", nargs="*", default=["add_norm", "attention", "step"])
+    ap.add_argument("--groups", nargs="*", default=["add_norm", "attention", "step", "flash64"])
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--json-out", default=None)
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
-    runs = {"add_norm": run_add_norm, "attention": run_attention, "step": run_step}
+    runs = {"add_norm": run_add_norm, "attention": run_attention, "step": run_step,
+            "flash64": run_flash64}
     for grp in a.groups:
-        line = json.dumps(runs[grp](a.reps, dev))
-        print(line, flush=True)
-        if a.json_out:
-            with open(a.json_out, "a") as fh:
-                fh.write(line + "\n")
+        res = runs[grp](a.reps, dev)
+        for r in res if isinstance(res, list) else [res]:
+            line = json.dumps(r)
+            print(line, flush=True)
+            if a.json_out:
+                with open(a.json_out, "a") as fh:
+                    fh.write(line + "\n")
         torch.cuda.empty_cache()
 
 

@@ -32,14 +32,17 @@ EXT_SUFFIX = sysconfig.get_config_var("EXT_SUFFIX") or ".so"
 # extra hipcc flags of single kernel sources (csrc/kernels/*.hip are all compiled; a new file
 # needs no entry). flash_attn64.hip: scalar fp32 VALU only, no packed fp32 pairs in its softmax
 # rescale and store scaling; flash_attn_doc.hip (flash_attn.hip's document-masked instantiations
-# and the bounds kernel) likewise
+# and the bounds kernel) and flash_attn64_drop.hip (flash_attn64.hip's dropout instantiations)
+# likewise
 _NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 SRC_FLAGS = {
     "flash_attn64.hip": _NO_PK_F32,
     "flash_attn_doc.hip": _NO_PK_F32,
+    "flash_attn64_drop.hip": _NO_PK_F32,
 }
 # sources that include another source (besides the headers every object depends on)
-SRC_DEPS = {"flash_attn_doc.hip": ["flash_attn.hip"]}
+SRC_DEPS = {"flash_attn_doc.hip": ["flash_attn.hip"],
+            "flash_attn64_drop.hip": ["flash_attn64.hip"]}
 
 
 def _torch_paths():

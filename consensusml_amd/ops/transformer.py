@@ -487,20 +487,29 @@ class _Flash64Fn(torch.autograd.Function):
     """Flash attention for head dim 64 on csrc/kernels/flash_attn64.hip, fused layouts on both
     sides: qkv [B, S, 3 H 64] -> o [B, S, H 64]; the backward's two kernels write every element of
     dqkv themselves. ``lens`` (int32 [B] on the device, or None) selects the kernels' length
-    variants: rows past a sequence's length are never read and come back zero in o, lse and dqkv."""
+    variants: rows past a sequence's length are never read and come back zero in o, lse and dqkv.
+    ``drop`` = (seed, offset, thr) selects the dropout instantiations
+    (csrc/kernels/flash_attn64_drop.hip, S % 8 == 0): all three kernels regenerate the keep bits in
+    registers, lse stays the undropped log-sum-exp, and the forward also returns o in fp32 for
+    the backward's D = rowsum(dO * O) (bf16 O, which carries 1 / (1 - p_eff), is too coarse for
+    the cancellation in dS = P (M dP - D) of a row with one visible key)."""
 
     @staticmethod
-    def forward(ctx, qkv, H, causal, scale, lens=None):
-        o, lse = lib().flash64_fwd(qkv, H, causal, scale, lens=lens)
-        ctx.save_for_backward(qkv, o, lse, lens)
-        ctx.cfg = (H, causal, scale)
+    def forward(ctx, qkv, H, causal, scale, lens=None, drop=None):
+        seed, offset, thr = drop or (0, 0, 0)
+        o, lse, *o32 = lib().flash64_fwd(qkv, H, causal, scale, lens=lens, seed=seed,
+                                         offset=offset, thr=thr)
+        ctx.save_for_backward(qkv, o, lse, lens, *o32)
+        ctx.cfg = (H, causal, scale, seed, offset, thr)
         return o
 
     @staticmethod
     def backward(ctx, do):
-        qkv, o, lse, lens = ctx.saved_tensors
-        H, causal, scale = ctx.cfg
-        return lib().flash64_bwd(qkv, o, do, lse, H, causal, scale, lens=lens), None, None, None, None
+        qkv, o, lse, lens, *o32 = ctx.saved_tensors
+        H, causal, scale, seed, offset, thr = ctx.cfg
+        return lib().flash64_bwd(qkv, o, do, lse, H, causal, scale, lens=lens, seed=seed,
+                                 offset=offset, thr=thr, o32=o32[0] if o32 else None
+                                 ), None, None, None, None, None
 
 
 def _flash64_ok(qkv: torch.Tensor, hd: int, causal: bool) -> bool:
@@ -570,15 +579,23 @@ def fused_qkv_attention(qkv: torch.Tensor, H: int, hd: int, causal: bool = False
     1 / (1 - p)); ``rng = (seed, offset)`` fixes the mask (default: the next draw of
     ``dropout_stream``), which ``dropout_mask(seed, offset, [B, H, S, S], p)`` returns. Where
     csrc/kernels/attention.hip is eligible (no lens, not causal, S <= 128) the mask is applied
-    inside the kernel and nothing is materialised. Every other case with dropout > 0 — S > 128,
-    ``lens``, causal, CPU, or ``attn_kernel`` off — runs an explicit head-split softmax
-    composition in PyTorch with that mask (the flash kernels have no dropout variant yet).
-    dropout = 0 or ``training=False`` is today's dispatch, bit for bit."""
+    inside the kernel and nothing is materialised. Every other hd = 64 bf16 GPU case with
+    S % 8 == 0 — any S, with or without ``lens``, causal or not — runs the dropout instantiations
+    of the flash kernels (csrc/kernels/flash_attn64_drop.hip): forward, dQ and dK / dV regenerate
+    the keep bits in registers, and the properties of ``lens`` hold unchanged. What is left — CPU,
+    other head dims, S % 8 != 0, ``flash_attn64`` off — runs an explicit head-split softmax
+    composition in PyTorch with that mask. dropout = 0 or ``training=False`` is the dispatch
+    without dropout, bit for bit."""
     B, S, _ = qkv.shape
     drop = _drop(dropout, training, rng)
     if drop is not None:
         if lens is None and not causal and _attn_ok(qkv, H, hd):
             return _AttnFn.apply(qkv, H, 1.0 / math.sqrt(hd), drop)
+        if (hd == 64 and _P().flash_attn64 and _gpu_bf16(qkv) and qkv.is_contiguous()
+                and qkv.data_ptr() % 16 == 0 and S % 8 == 0):
+            if lens is not None:
+                lens = lens.to(device=qkv.device, dtype=torch.int32).contiguous()
+            return _Flash64Fn.apply(qkv, H, bool(causal), 1.0 / math.sqrt(hd), lens, drop)
         return _dropout_attention(qkv, H, hd, bool(causal), lens, drop)
     if lens is not None:
         if (hd == 64 and _P().flash_attn64 and _gpu_bf16(qkv) and qkv.is_contiguous()

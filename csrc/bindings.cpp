@@ -2816,7 +2816,8 @@ std::vector<Tensor> doc_bounds(const Tensor& ids_in) {
 }
 
 // Flash attention, head dim 64, fused layouts (csrc/kernels/flash_attn64.hip): qkv [B, S, 3 H 64]
-// bf16 contiguous -> (o [B, S, H 64], lse fp32 [B, H, S], log2 domain)
+// bf16 contiguous -> (o [B, S, H 64], lse fp32 [B, H, S], log2 domain); with dropout (thr > 0) a
+// third result, o32 fp32 [B, S, H 64] (o before its bf16 rounding), which flash64_bwd then needs
 void check_flash64_qkv(const Tensor& qkv, int64_t H) {
   check_bf16c(qkv, "qkv");
   TORCH_CHECK(H >= 1 && qkv.dim() == 3 && qkv.size(2) == 3 * H * 64 && qkv.size(0) >= 1 &&
@@ -2835,7 +2836,8 @@ const int* flash64_lens(const optional<Tensor>& lens, const Tensor& qkv) {
 }
 
 std::vector<Tensor> flash64_fwd(const Tensor& qkv, int64_t H, bool causal, double scale,
-                                double rescale_thr, int64_t nq, const optional<Tensor>& lens) {
+                                double rescale_thr, int64_t nq, const optional<Tensor>& lens,
+                                int64_t seed, int64_t offset, int64_t thr) {
   check_flash64_qkv(qkv, H);
   const int* lp = flash64_lens(lens, qkv);
   TORCH_CHECK(nq >= 0 && nq <= 2, "flash64_fwd: nq must be 0 (auto), 1 or 2");
@@ -2843,19 +2845,29 @@ std::vector<Tensor> flash64_fwd(const Tensor& qkv, int64_t H, bool causal, doubl
   const c10::DeviceGuard guard(qkv.device());
   Tensor o = at::empty({B, S, H * 64}, qkv.options());
   Tensor lse = at::empty({B, H, S}, qkv.options().dtype(at::kFloat));
+  Tensor o32;
+  if (thr != 0) o32 = at::empty({B, S, H * 64}, lse.options());
   CML_CHECK_HIP(cml::launch_flash64_fwd(qkv.data_ptr(), o.data_ptr(), lse.data_ptr<float>(),
                                         static_cast<int>(B), static_cast<int>(H),
                                         static_cast<int>(S), static_cast<float>(scale), causal,
                                         cur_stream(), static_cast<float>(rescale_thr),
-                                        static_cast<int>(nq), lp));
+                                        static_cast<int>(nq), lp,
+                                        drop_spec(seed, offset, thr, "flash64_fwd"),
+                                        thr != 0 ? o32.data_ptr<float>() : nullptr));
+  if (thr != 0) return {o, lse, o32};
   return {o, lse};
 }
 
 Tensor flash64_bwd(const Tensor& qkv, const Tensor& o, const Tensor& dout_in, const Tensor& lse,
-                   int64_t H, bool causal, double scale, const optional<Tensor>& lens) {
+                   int64_t H, bool causal, double scale, const optional<Tensor>& lens,
+                   int64_t seed, int64_t offset, int64_t thr, const optional<Tensor>& o32) {
   check_flash64_qkv(qkv, H);
   const int* lp = flash64_lens(lens, qkv);
   const int64_t B = qkv.size(0), S = qkv.size(1);
+  TORCH_CHECK(thr == 0 ||
+                  (o32.has_value() && o32->scalar_type() == at::kFloat && o32->is_contiguous() &&
+                   o32->numel() == B * S * H * 64 && o32->device() == qkv.device()),
+              "flash64_bwd: dropout needs flash64_fwd's o32, fp32 [B, S, H 64] on qkv's device");
   Tensor dout = dout_in.contiguous();
   check_bf16c(o, "o");
   check_bf16c(dout, "dout");
@@ -2875,7 +2887,9 @@ Tensor flash64_bwd(const Tensor& qkv, const Tensor& o, const Tensor& dout_in, co
                                         lse.data_ptr<float>(), dsum.data_ptr<float>(),
                                         dqkv.data_ptr(), static_cast<int>(B), static_cast<int>(H),
                                         static_cast<int>(S), static_cast<float>(scale), causal,
-                                        cur_stream(), lp));
+                                        cur_stream(), lp,
+                                        drop_spec(seed, offset, thr, "flash64_bwd"),
+                                        thr != 0 ? o32->data_ptr<float>() : nullptr));
   return dqkv;
 }
 
@@ -3611,10 +3625,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("doc_bounds", &doc_bounds, "document bounds (lo, hi) of packed rows from doc ids");
   m.def("flash64_fwd", &flash64_fwd, "flash attention forward, head dim 64, fused qkv in",
         py::arg("qkv"), py::arg("H"), py::arg("causal"), py::arg("scale"),
-        py::arg("rescale_thr") = 8.0, py::arg("nq") = 0, py::arg("lens") = py::none());
+        py::arg("rescale_thr") = 8.0, py::arg("nq") = 0, py::arg("lens") = py::none(),
+        py::arg("seed") = 0, py::arg("offset") = 0, py::arg("thr") = 0);
   m.def("flash64_bwd", &flash64_bwd, "flash attention backward, head dim 64, fused dqkv out",
         py::arg("qkv"), py::arg("o"), py::arg("dout"), py::arg("lse"), py::arg("H"),
-        py::arg("causal"), py::arg("scale"), py::arg("lens") = py::none());
+        py::arg("causal"), py::arg("scale"), py::arg("lens") = py::none(),
+        py::arg("seed") = 0, py::arg("offset") = 0, py::arg("thr") = 0,
+        py::arg("o32") = py::none());
   m.def("swiglu_fwd", &swiglu_fwd, "silu(a) * b over [a | b]");
   m.def("swiglu_bwd", &swiglu_bwd, "SwiGLU backward");
   m.def("attn_fwd", &attn_fwd, "short-sequence MFMA attention forward (fused qkv in)",

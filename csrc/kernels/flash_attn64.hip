@@ -68,12 +68,53 @@
 //     blocks keep their place in the order (a different order was not tried)
 // VGPRs with lengths: forward 141 / 140 (NQ 1 causal / full), 246 / 252 (NQ 2), dQ 176 / 174,
 // dK / dV 207 / 207; no scratch, LDS as above, two workgroups per CU.
+//
+// Dropout (template flag DROP, instantiated only by flash_attn64_drop.hip, which includes this file
+// under CML_F64_DROP_TU; the DROP = false instruction streams are those of the file without the
+// flag). The arithmetic is attention.hip's: lse, the running max and l come from the undropped
+// scores; with M = keep / (1 - p_eff), O = (M P) V (1 / (1 - p_eff) folded into the final 1 / l),
+// dV = (M P)^T dO (folded into the store scale), dS = P (M dP - D) with D = rowsum(dO * O). That
+// D is taken from o32, the fp32 row the DROP forward stores beside the bf16 one (4 B per element
+// more written, and read once by dQ's prologue): O now carries 1 / (1 - p_eff), so for a query
+// with one visible key M dP - D = 0 cancels only as far as O is exact, and with the bf16 O the
+// remainder (2^-9 of |dO| |O|) was 2.6 times the 1e-3 floor of that sequence's whole gradient.
+// Keep bits: dropout.h's mask over ((b H + h) S + q) S + k, S % 8 == 0, regenerated in
+// every kernel at one Philox call per 8 scores, after the sub-tile skips (a skipped sub-tile draws
+// nothing), applied in the loop that forms the probabilities; no keep image in HBM, no barrier
+// added. Forward / dQ: drop_keep64 (registers + one permlane32_swap). dK / dV: drop_keep_patch
+// (128 B of wave-private LDS per wave: 66.5 KB per workgroup, still two per CU). The forward is
+// built for NQ = 1 only (NQ = 2 sits at 246-252 VGPRs without it).
+// VGPRs with DROP (causal / full; plain, then lengths): forward 154 / 154, 153 / 152; dQ
+// 220 / 219, 220 / 219; dK / dV 211 / 215, 209 / 213; no scratch, two workgroups per CU.
 #include <math.h>
 
+#include <type_traits>
+
 #include "common.h"
+#include "dropout.h"
 #include "kernels.h"
 
 namespace cml {
+
+struct F64Args {
+  const uint16_t* qkv;    // [B, S, 3, H, 64]
+  const uint16_t* o;      // [B, S, H, 64]
+  const uint16_t* dout;   // [B, S, H, 64]
+  uint16_t* out;          // forward: o; backward: dqkv
+  float* lse;             // [B, H, S]
+  float* dsum;            // [B, H, S]
+  int B, H, S;
+  float c;                // scale * log2(e)
+  float scale;
+  float thr;              // forward: deferred-rescale threshold (log2 units)
+  const int* lens;        // [B] rows of each sequence (VL kernels only; clamped into [1, S])
+};
+// the DROP instantiations (flash_attn64_drop.hip): S % 8 == 0, forward with one query group
+hipError_t launch_f64_drop_fwd(const F64Args& a, const DropArgs& d, float* o32, bool causal,
+                               hipStream_t st);
+hipError_t launch_f64_drop_bwd(const F64Args& a, const DropArgs& d, const float* o32, bool causal,
+                               hipStream_t st);
+
 namespace {
 
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
@@ -91,19 +132,13 @@ constexpr int kFwdSmem = 4 * kImg;              // 2 x (K, V)
 constexpr int kKVBuf = 2 * kImg + 1024;         // Q image, dO image, lse [128], D [128]
 constexpr int kKVSmem = 2 * kKVBuf;
 
-struct F64Args {
-  const uint16_t* qkv;    // [B, S, 3, H, 64]
-  const uint16_t* o;      // [B, S, H, 64]
-  const uint16_t* dout;   // [B, S, H, 64]
-  uint16_t* out;          // forward: o; backward: dqkv
-  float* lse;             // [B, H, S]
-  float* dsum;            // [B, H, S]
-  int B, H, S;
-  float c;                // scale * log2(e)
-  float scale;
-  float thr;              // forward: deferred-rescale threshold (log2 units)
-  const int* lens;        // [B] rows of each sequence (VL kernels only; clamped into [1, S])
+// kernel argument: F64Args, for the DROP instantiations with the dropout.h arguments appended
+struct F64DropArgs : F64Args {
+  DropArgs drop;
+  float* o32;   // [B, S, H, 64] fp32: the forward's output before its bf16 rounding, read for D
 };
+template <bool DROP>
+using F64A = std::conditional_t<DROP, F64DropArgs, F64Args>;
 
 __device__ __forceinline__ f32x16 mfma(bf16x8_t a, bf16x8_t b, f32x16 c) {
   return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
@@ -224,9 +259,46 @@ __device__ __forceinline__ void zero_block(uint16_t* p, int64_t ld, int row0, in
       if (row0 + i < S) f[row0 + i] = 0.f;
 }
 
+// ---------------------------------------------------------------------------- dropout keep bits
+// dropout.h group (8 consecutive keys of one query, S % 8 == 0) of query row `row` of head bh at
+// key 0; the group of key k is this + (k >> 3)
+__device__ __forceinline__ uint64_t drop_row(int bh, int S, int row) {
+  return (static_cast<uint64_t>(bh) * S + row) * static_cast<uint32_t>(S >> 3);
+}
+// Forward / dQ: keep bits of the lane's query against the 64 keys [k0, k0 + 64) of a half-tile
+// (g0 = drop_row + (k0 >> 3)). The lane's registers 4j..4j+3 of score tile x are keys
+// k0 + 32 x + 8 j + 4 h + 0..3, so group (x, j) is that quad of lane r and of lane r + 32. The
+// lane draws the four groups of x = h (byte j of its word = group j), then one permlane32_swap
+// hands both lanes of a query both words: every group is drawn once, nothing goes through LDS.
+// kw[x] bit 8 j + e = keep of register 4 j + e of tile x (already shifted to the lane's nibble).
+__device__ __forceinline__ void drop_keep64(const DropArgs& d, uint64_t g0, int h,
+                                            uint32_t (&kw)[2]) {
+  uint32_t mine = 0;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) mine |= drop_keep8(d, g0 + 4 * h + j) << (8 * j);
+  const auto x = __builtin_amdgcn_permlane32_swap(mine, mine, false, false);
+  kw[0] = x[0] >> (4 * h);   // the word of lanes 0-31: tile 0
+  kw[1] = x[1] >> (4 * h);   // the word of lanes 32-63: tile 1
+}
+// dK / dV: keep bits of a 32-query x 32-key sub-tile (queries q0 + 0..31, key groups from kg8 =
+// first key >> 3) as one 32-bit word per query (bit r = key r) in a wave-private 128-byte patch.
+// 128 groups, two per lane: lane l draws key groups 2 (l & 1) + 0 / 1 of query l >> 1 and writes
+// their 16 bits at byte 2 l, i.e. half (l & 1) of word l >> 1. The words of the four queries
+// 8 g + 4 h + 0..3 (registers 4g..4g+3 of the lane) are then one ds_read_b128 at 32 g + 16 h.
+// Wave-private: the wave's own LDS operations complete in order, so lgkmcnt(0) is the only wait.
+__device__ __forceinline__ void drop_keep_patch(const DropArgs& d, uint64_t bh_base, int S, int q0,
+                                                int kg8, int lane, char* patch) {
+  const uint64_t g = bh_base + static_cast<uint64_t>(q0 + (lane >> 1)) * static_cast<uint32_t>(S >> 3) +
+                     static_cast<uint32_t>(kg8 + 2 * (lane & 1));
+  const uint32_t bits = drop_keep8(d, g) | (drop_keep8(d, g + 1) << 8);
+  *reinterpret_cast<uint16_t*>(patch + 2 * lane) = static_cast<uint16_t>(bits);
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+}
+
 // ------------------------------------------------------------------------------------- forward
-template <bool CAUSAL, int NQ, bool VL>
-__global__ __launch_bounds__(kThreads, 2) void f64_fwd_kernel(F64Args a) {
+template <bool CAUSAL, int NQ, bool VL, bool DROP = false>
+__global__ __launch_bounds__(kThreads, 2) void f64_fwd_kernel(F64A<DROP> a) {
+  static_assert(!DROP || NQ == 1, "the DROP forward is built for one query group per wave");
   constexpr int BQ = 128 * NQ;
   extern __shared__ __attribute__((aligned(16))) char smem[];   // 2 x (K image, V image)
   const int lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
@@ -336,11 +408,19 @@ __global__ __launch_bounds__(kThreads, 2) void f64_fwd_kernel(F64Args a) {
             for (int i = 0; i < 16; ++i) o[n][dt][i] *= alpha;
         }
         float ls = 0.f;
+        uint32_t kw[2];
+        if constexpr (DROP)
+          drop_keep64(a.drop, drop_row(bh, S, qmin + 32 * n + r) + (k0 >> 3), h, kw);
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
           s[n][0][i] = fexp2(fmaf(s[n][0][i], a.c, -m[n]));
           s[n][1][i] = fexp2(fmaf(s[n][1][i], a.c, -m[n]));
           ls += s[n][0][i] + s[n][1][i];
+          if constexpr (DROP) {   // l keeps the undropped sum; the P of the P V product is dropped
+            const int bit = 8 * (i >> 2) + (i & 3);
+            if (!((kw[0] >> bit) & 1u)) s[n][0][i] = 0.f;
+            if (!((kw[1] >> bit) & 1u)) s[n][1][i] = 0.f;
+          }
         }
         l[n] += ls;
       }
@@ -374,16 +454,32 @@ __global__ __launch_bounds__(kThreads, 2) void f64_fwd_kernel(F64Args a) {
     // rows [L, S) of a partial block: +0 and lse = 0 (a dead wave's l is 0: its 1 / lt is never
     // stored)
     const bool pad = VL && qrow >= L;
-    store_row(a.out + ((static_cast<int64_t>(b) * S + min(qrow, S - 1)) * H + hh) * kD, o[n],
-              1.f / lt, h, qrow < S, pad);
+    uint16_t* orow = a.out + ((static_cast<int64_t>(b) * S + min(qrow, S - 1)) * H + hh) * kD;
+    float inv = 1.f / lt;
+    if constexpr (DROP) inv *= a.drop.scale;   // kept probabilities / (1 - p_eff)
+    store_row(orow, o[n], inv, h, qrow < S, pad);
+    if constexpr (DROP) {
+      // the unrounded row for the backward's D (registers 4g..4g+3: 16 B per lane, lanes r and
+      // r + 32 adjacent); padded rows are never read back, so they are not written
+      if (qrow < S && !pad) {
+        float* r32 = a.o32 + ((static_cast<int64_t>(b) * S + qrow) * H + hh) * kD + 4 * h;
+#pragma unroll
+        for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+          for (int g = 0; g < 4; ++g)
+            *reinterpret_cast<float4*>(r32 + 32 * dt + 8 * g) =
+                make_float4(o[n][dt][4 * g] * inv, o[n][dt][4 * g + 1] * inv,
+                            o[n][dt][4 * g + 2] * inv, o[n][dt][4 * g + 3] * inv);
+      }
+    }
     if (h == 0 && qrow < S)
       a.lse[static_cast<int64_t>(bh) * S + qrow] = pad ? 0.f : m[n] + __log2f(lt);
   }
 }
 
 // ------------------------------------------------------------------------------ backward: dQ
-template <bool CAUSAL, bool VL>
-__global__ __launch_bounds__(kThreads, 2) void f64_dq_kernel(F64Args a) {
+template <bool CAUSAL, bool VL, bool DROP = false>
+__global__ __launch_bounds__(kThreads, 2) void f64_dq_kernel(F64A<DROP> a) {
   constexpr int BQ = 128;
   extern __shared__ __attribute__((aligned(16))) char smem[];   // 2 x (K image, V image)
   const int lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
@@ -426,10 +522,22 @@ __global__ __launch_bounds__(kThreads, 2) void f64_dq_kernel(F64Args a) {
       const uint4 ov = *reinterpret_cast<const uint4*>(op + 16 * ks);
       df[ks] = __builtin_bit_cast(bf16x8_t, dv);
       const uint32_t d4[4] = {dv.x, dv.y, dv.z, dv.w}, o4[4] = {ov.x, ov.y, ov.z, ov.w};
+      if constexpr (DROP) {   // D from the fp32 row: see the header comment
+        const float* o32 = a.o32 + orow + 16 * ks;
+        const float4 oa = *reinterpret_cast<const float4*>(o32);
+        const float4 ob = *reinterpret_cast<const float4*>(o32 + 4);
+        const float of[8] = {oa.x, oa.y, oa.z, oa.w, ob.x, ob.y, ob.z, ob.w};
 #pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        part = fmaf(__uint_as_float(d4[e] << 16), __uint_as_float(o4[e] << 16), part);
-        part = fmaf(__uint_as_float(d4[e] & 0xffff0000u), __uint_as_float(o4[e] & 0xffff0000u), part);
+        for (int e = 0; e < 4; ++e) {
+          part = fmaf(__uint_as_float(d4[e] << 16), of[2 * e], part);
+          part = fmaf(__uint_as_float(d4[e] & 0xffff0000u), of[2 * e + 1], part);
+        }
+      } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          part = fmaf(__uint_as_float(d4[e] << 16), __uint_as_float(o4[e] << 16), part);
+          part = fmaf(__uint_as_float(d4[e] & 0xffff0000u), __uint_as_float(o4[e] & 0xffff0000u), part);
+        }
       }
     }
     dsum = part + __shfl_xor(part, 32, 64);
@@ -463,6 +571,8 @@ __global__ __launch_bounds__(kThreads, 2) void f64_dq_kernel(F64Args a) {
       constexpr bool kOne = CAUSAL && VL;
       const int qlast = kOne ? qc : qrow;
       const bool edge = CAUSAL ? (k0 + 63 > (kOne ? min(qmin, L - 1) : qmin)) : (k0 + 64 > L);
+      uint32_t kw[2];
+      if constexpr (DROP) drop_keep64(a.drop, drop_row(bh, S, qrow) + (k0 >> 3), h, kw);
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
         float e0 = fexp2(fmaf(s0[i], a.c, -lse)), e1 = fexp2(fmaf(s1[i], a.c, -lse));
@@ -470,6 +580,11 @@ __global__ __launch_bounds__(kThreads, 2) void f64_dq_kernel(F64Args a) {
           const int key = k0 + acc_row(i, h);
           if ((CAUSAL && key > qlast) || (!kOne && key >= L)) e0 = 0.f;
           if ((CAUSAL && key + 32 > qlast) || (!kOne && key + 32 >= L)) e1 = 0.f;
+        }
+        if constexpr (DROP) {   // dP <- M dP, M = keep / (1 - p_eff); e0 / e1 stay undropped
+          const int bit = 8 * (i >> 2) + (i & 3);
+          p0[i] = (kw[0] >> bit) & 1u ? p0[i] * a.drop.scale : 0.f;
+          p1[i] = (kw[1] >> bit) & 1u ? p1[i] * a.drop.scale : 0.f;
         }
         s0[i] = e0 * (p0[i] - dsum);   // dS^T
         s1[i] = e1 * (p1[i] - dsum);
@@ -494,8 +609,8 @@ __global__ __launch_bounds__(kThreads, 2) void f64_dq_kernel(F64Args a) {
 // --------------------------------------------------------------------------- backward: dK, dV
 // 4 waves x 32 keys; the lane's K and V rows in registers (B operands of S = Q K^T and
 // dP = dO V^T), Q / dO tiles of 128 queries with their lse / D in LDS.
-template <bool CAUSAL, bool VL>
-__global__ __launch_bounds__(kThreads, 2) void f64_dkdv_kernel(F64Args a) {
+template <bool CAUSAL, bool VL, bool DROP = false>
+__global__ __launch_bounds__(kThreads, 2) void f64_dkdv_kernel(F64A<DROP> a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
   const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -567,12 +682,20 @@ __global__ __launch_bounds__(kThreads, 2) void f64_dkdv_kernel(F64Args a) {
       }
       // s[i] = S[query qq0 + acc_row(i, h)][key]; registers 4g..4g+3: 4 consecutive queries
       const bool edge = (CAUSAL && qq0 < kmin + 31) || qq0 + 32 > L;
+      // the sub-tile's keep words (after the skip: a skipped sub-tile draws nothing); the patch
+      // follows the two staging buffers, 128 B per wave
+      char* patch = smem + kKVSmem + 128 * w;
+      if constexpr (DROP)
+        drop_keep_patch(a.drop, drop_row(bh, S, 0), S, qq0, kmin >> 3, lane, patch);
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
         const int ql = 32 * qs + 8 * g + 4 * h;
         const float4 Ls = *reinterpret_cast<const float4*>(lsel + ql);
         const float4 Dd = *reinterpret_cast<const float4*>(dsl + ql);
         const float Lv[4] = {Ls.x, Ls.y, Ls.z, Ls.w}, Dv[4] = {Dd.x, Dd.y, Dd.z, Dd.w};
+        uint4 kq = {};
+        if constexpr (DROP) kq = *reinterpret_cast<const uint4*>(patch + 32 * g + 16 * h);
+        const uint32_t Kv[4] = {kq.x, kq.y, kq.z, kq.w};
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           const int i = 4 * g + e;
@@ -581,8 +704,14 @@ __global__ __launch_bounds__(kThreads, 2) void f64_dkdv_kernel(F64Args a) {
             const int qi = qq0 + 8 * g + 4 * h + e;
             if ((CAUSAL && qi < key) || qi >= L) p = 0.f;
           }
-          s[i] = p;
-          dp[i] = p * (dp[i] - Dv[e]);
+          if constexpr (DROP) {   // dV takes keep * P, dS = P (M dP - D) the undropped P
+            const bool keep = (Kv[e] >> r) & 1u;
+            s[i] = keep ? p : 0.f;
+            dp[i] = p * ((keep ? dp[i] * a.drop.scale : 0.f) - Dv[e]);
+          } else {
+            s[i] = p;
+            dp[i] = p * (dp[i] - Dv[e]);
+          }
         }
       }
 #pragma unroll
@@ -599,15 +728,18 @@ __global__ __launch_bounds__(kThreads, 2) void f64_dkdv_kernel(F64Args a) {
   }
   uint16_t* row = a.out + (static_cast<int64_t>(b) * S + min(key, S - 1)) * ld + (H + hh) * kD;
   store_row(row, dk, a.scale, h, key < S, pad);
-  store_row(row + H * kD, dv, 1.f, h, key < S, pad);
+  float vs = 1.f;
+  if constexpr (DROP) vs = a.drop.scale;   // dV = (keep P)^T dO / (1 - p_eff)
+  store_row(row + H * kD, dv, vs, h, key < S, pad);
 }
 
-typedef void (*F64Kernel)(F64Args);
-
-hipError_t launch_f64(F64Kernel kern, const F64Args& a, int smem, int rows, hipStream_t st) {
-  // dynamic LDS at / above the default limit: set once per kernel. One slot per instantiation
-  // this file launches: forward {causal, full} x {NQ 1, 2}, dQ and dK / dV {causal, full}, each
-  // with and without lengths (8 + 8); a 17th would just set its attribute on every launch.
+template <typename A>
+hipError_t launch_f64(void (*kern)(A), const A& a, int smem, int rows, hipStream_t st) {
+  // dynamic LDS at / above the default limit: set once per kernel. One slot per instantiation a
+  // compilation launches (the table is per compilation and argument type). flash_attn64.hip:
+  // forward {causal, full} x {NQ 1, 2}, dQ and dK / dV {causal, full}, each with and without
+  // lengths (8 + 8). flash_attn64_drop.hip: the DROP forward (NQ 1), dQ and dK / dV in the same
+  // four forms (4 + 4 + 4). A 17th would just set its attribute on every launch.
   static const void* done[16] = {};
   const void* f = reinterpret_cast<const void*>(kern);
   bool set = false;
@@ -627,6 +759,7 @@ hipError_t launch_f64(F64Kernel kern, const F64Args& a, int smem, int rows, hipS
   return hipGetLastError();
 }
 
+#ifndef CML_F64_DROP_TU
 // 32-query groups per forward wave: 2 when its grid still gives every CU >= 3 workgroups (causal:
 // >= 4) and S wastes no half block of 256 queries, else 1. Measured at 12 heads (256 CUs,
 // profiles/flash64/README.md): at 1.5-2 workgroups per CU NQ = 1 is 12-17 % faster; at 3 NQ = 2
@@ -649,12 +782,47 @@ bool f64_shape_ok(int B, int H, int S) {
          static_cast<int64_t>((S + kBK - 1) / kBK) * B * H < (1LL << 31);
 }
 
+#endif  // !CML_F64_DROP_TU
+
 }  // namespace
 
+#ifdef CML_F64_DROP_TU
+hipError_t launch_f64_drop_fwd(const F64Args& a, const DropArgs& d, float* o32, bool causal,
+                               hipStream_t st) {
+  const F64DropArgs x{a, d, o32};
+  if (a.lens != nullptr)
+    return causal ? launch_f64(f64_fwd_kernel<true, 1, true, true>, x, kFwdSmem, 128, st)
+                  : launch_f64(f64_fwd_kernel<false, 1, true, true>, x, kFwdSmem, 128, st);
+  return causal ? launch_f64(f64_fwd_kernel<true, 1, false, true>, x, kFwdSmem, 128, st)
+                : launch_f64(f64_fwd_kernel<false, 1, false, true>, x, kFwdSmem, 128, st);
+}
+
+hipError_t launch_f64_drop_bwd(const F64Args& a, const DropArgs& d, const float* o32, bool causal,
+                               hipStream_t st) {
+  const F64DropArgs x{a, d, const_cast<float*>(o32)};
+  constexpr int kv = kKVSmem + 4 * 128;   // + one keep-word patch per wave
+  hipError_t e;
+  if (a.lens != nullptr) {
+    e = causal ? launch_f64(f64_dq_kernel<true, true, true>, x, kFwdSmem, 128, st)
+               : launch_f64(f64_dq_kernel<false, true, true>, x, kFwdSmem, 128, st);
+    if (e != hipSuccess) return e;
+    return causal ? launch_f64(f64_dkdv_kernel<true, true, true>, x, kv, kBK, st)
+                  : launch_f64(f64_dkdv_kernel<false, true, true>, x, kv, kBK, st);
+  }
+  e = causal ? launch_f64(f64_dq_kernel<true, false, true>, x, kFwdSmem, 128, st)
+             : launch_f64(f64_dq_kernel<false, false, true>, x, kFwdSmem, 128, st);
+  if (e != hipSuccess) return e;
+  return causal ? launch_f64(f64_dkdv_kernel<true, false, true>, x, kv, kBK, st)
+                : launch_f64(f64_dkdv_kernel<false, false, true>, x, kv, kBK, st);
+}
+#else
 hipError_t launch_flash64_fwd(const void* qkv, void* o, float* lse, int B, int H, int S,
                               float scale, bool causal, hipStream_t st, float rescale_thr,
-                              int nq, const int* lens) {
+                              int nq, const int* lens, const DropSpec& drop, float* o32) {
   if (!f64_shape_ok(B, H, S) || nq < 0 || nq > 2) return hipErrorInvalidValue;
+  // dropout: a Philox group is 8 keys of one query (S % 8 == 0); one query group per wave only
+  if (drop.thr && (!drop_valid(drop) || S % 8 != 0 || nq == 2 || o32 == nullptr))
+    return hipErrorInvalidValue;
   F64Args a{};
   a.qkv = static_cast<const uint16_t*>(qkv);
   a.out = static_cast<uint16_t*>(o);
@@ -664,6 +832,7 @@ hipError_t launch_flash64_fwd(const void* qkv, void* o, float* lse, int B, int H
   a.c = scale * 1.4426950408889634f;
   a.thr = rescale_thr < 0.f ? 0.f : rescale_thr;
   a.lens = lens;
+  if (drop.thr) return launch_f64_drop_fwd(a, drop_args(drop), o32, causal, st);   // f64_nq not asked
   // the grid and the pick of NQ come from S with or without lengths: the host never reads lens
   const bool two = (nq ? nq : f64_nq(B, H, S, causal)) == 2;
   if (lens != nullptr) {
@@ -682,8 +851,10 @@ hipError_t launch_flash64_fwd(const void* qkv, void* o, float* lse, int B, int H
 
 hipError_t launch_flash64_bwd(const void* qkv, const void* o, const void* dout, const float* lse,
                               float* dsum, void* dqkv, int B, int H, int S, float scale,
-                              bool causal, hipStream_t st, const int* lens) {
+                              bool causal, hipStream_t st, const int* lens, const DropSpec& drop,
+                              const float* o32) {
   if (!f64_shape_ok(B, H, S)) return hipErrorInvalidValue;
+  if (drop.thr && (!drop_valid(drop) || S % 8 != 0 || o32 == nullptr)) return hipErrorInvalidValue;
   F64Args a{};
   a.qkv = static_cast<const uint16_t*>(qkv);
   a.o = static_cast<const uint16_t*>(o);
@@ -695,6 +866,7 @@ hipError_t launch_flash64_bwd(const void* qkv, const void* o, const void* dout, 
   a.scale = scale;
   a.c = scale * 1.4426950408889634f;
   a.lens = lens;
+  if (drop.thr) return launch_f64_drop_bwd(a, drop_args(drop), o32, causal, st);
   // dQ first: it also writes D = rowsum(dO * O), which the dK / dV kernel reads
   if (lens != nullptr) {
     hipError_t e = causal ? launch_f64(f64_dq_kernel<true, true>, a, kFwdSmem, 128, st)
@@ -709,5 +881,6 @@ hipError_t launch_flash64_bwd(const void* qkv, const void* o, const void* dout, 
   return causal ? launch_f64(f64_dkdv_kernel<true, false>, a, kKVSmem, kBK, st)
                 : launch_f64(f64_dkdv_kernel<false, false>, a, kKVSmem, kBK, st);
 }
+#endif  // CML_F64_DROP_TU
 
 }  // namespace cml

@@ -459,12 +459,22 @@ hipError_t launch_doc_bounds(const void* ids, int id_bytes, int* lo, int* hi, in
 // rows [0, lens[b]) of its batch entry (clamped into [1, S] by the kernels, never read on the
 // host); o / lse / dqkv / dsum are zero on the padded rows and nothing depends on what qkv, o or
 // dout hold there. nullptr: every sequence is S rows (the kernels without the length variant).
+// drop.thr > 0 (csrc/kernels/flash_attn64_drop.hip): dropout on the probabilities as in
+// launch_attn_fwd / bwd, mask index ((b * H + h) * S + q) * S + k regenerated in registers by all
+// three kernels, lse the undropped log-sum-exp; needs S % 8 == 0 and nq != 2 (else
+// hipErrorInvalidValue). drop.thr = 0: the kernels without dropout, as before. o32 [B, S, H * 64]
+// fp32 (required with drop.thr > 0, unused without): the forward also writes o before its bf16
+// rounding and the backward takes D = rowsum(dO * O) from it. O carries 1 / (1 - p_eff), so a
+// one-key row's dS = M dP - D cancels only as far as O is exact; bf16 O left an error there of
+// the size of the whole gradient. Padded rows of o32 are neither written nor read.
 hipError_t launch_flash64_fwd(const void* qkv, void* o, float* lse, int B, int H, int S,
                               float scale, bool causal, hipStream_t stream,
-                              float rescale_thr = 8.f, int nq = 0, const int* lens = nullptr);
+                              float rescale_thr = 8.f, int nq = 0, const int* lens = nullptr,
+                              const DropSpec& drop = {}, float* o32 = nullptr);
 hipError_t launch_flash64_bwd(const void* qkv, const void* o, const void* dout, const float* lse,
                               float* dsum, void* dqkv, int B, int H, int S, float scale,
-                              bool causal, hipStream_t stream, const int* lens = nullptr);
+                              bool causal, hipStream_t stream, const int* lens = nullptr,
+                              const DropSpec& drop = {}, const float* o32 = nullptr);
 // SwiGLU over h = [a | b] ([M, 2F]): y = silu(a) * b; backward writes dh [M, 2F].
 hipError_t launch_swiglu_fwd(const void* h, void* y, int64_t M, int F, hipStream_t stream);
 hipError_t launch_swiglu_bwd(const void* dy, const void* h, void* dh, int64_t M, int F,
