@@ -274,7 +274,7 @@ class FaultConfig:
 
 @dataclass
 class ModelConfig:
-    name: str = "mlp"            # mlp | resnet50 | bert_base | llama3_8b | llama_tiny | bert_tiny
+    name: str = "mlp"            # mlp | resnet50 | bert_base | llama3_8b | llama3_2_1b | llama_tiny | bert_tiny
     num_classes: int = 1000
     image_size: int = 224
     seq_len: int = 128

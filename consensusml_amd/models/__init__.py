@@ -2,7 +2,7 @@
 
 ``build_task(cfg, device, dtype)`` returns the model (cast to the compute dtype, channels_last
 for CNNs), a synthetic batch generator and the loss. Families: 2-layer MLP (BASELINE config 1),
-ResNet-50, BERT-base (MLM), Llama-3-8B (causal LM), plus tiny variants for tests.
+ResNet-50, BERT-base (MLM), Llama-3-8B and Llama-3.2-1B (causal LM), plus tiny variants for tests.
 """
 from __future__ import annotations
 
@@ -16,7 +16,7 @@ from ..config import ModelConfig
 from ..ops.transformer import cross_entropy
 from .mlp import MLP
 from .resnet import resnet50, resnet_tiny
-from .transformer import bert_base, bert_tiny, llama3_8b, llama_tiny
+from .transformer import bert_base, bert_tiny, llama3_2_1b, llama3_8b, llama_tiny
 
 
 @dataclass
@@ -88,8 +88,9 @@ def build_task(cfg: ModelConfig, device: torch.device, dtype: torch.dtype = torc
             labels = torch.randint(0, V, (b, S), generator=gen, device=device)
             return ids, labels
         return Task(name, model, make, _ce, samples_per_item=S, batched_workers=True)
-    if name in ("llama3_8b", "llama_tiny"):
-        model = (llama3_8b() if name == "llama3_8b" else llama_tiny()).to(device, dtype)
+    if name in ("llama3_8b", "llama3_2_1b", "llama_tiny"):
+        mk = {"llama3_8b": llama3_8b, "llama3_2_1b": llama3_2_1b, "llama_tiny": llama_tiny}[name]
+        model = mk().to(device, dtype)
         V = model.c.vocab
         S = cfg.seq_len
 
@@ -101,4 +102,4 @@ def build_task(cfg: ModelConfig, device: torch.device, dtype: torch.dtype = torc
 
 
 __all__ = ["Task", "build_task", "MLP", "resnet50", "resnet_tiny", "bert_base", "bert_tiny",
-           "llama3_8b", "llama_tiny"]
+           "llama3_8b", "llama3_2_1b", "llama_tiny"]

@@ -618,6 +618,13 @@ def _flash_ok(*ts: torch.Tensor) -> bool:
             and all(t.is_contiguous() and t.data_ptr() % 16 == 0 for t in ts))
 
 
+def _flash_gqa64_ok(lo, *ts: torch.Tensor) -> bool:
+    """hd = 64 on csrc/kernels/flash_attn64_gqa.hip: under the ``flash_attn64`` switch, and never
+    with document bounds (that layout has no document variant)."""
+    return (lo is None and _P().flash_attn64 and _gpu_bf16(*ts)
+            and all(t.is_contiguous() and t.data_ptr() % 16 == 0 for t in ts))
+
+
 def doc_bounds(doc_ids: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
     """Document bounds of packed rows. ``doc_ids`` is an integer ``[B, S]`` tensor; a document is
     a maximal run of equal consecutive ids within a row (a repeated id later in the row starts a
@@ -660,7 +667,8 @@ class _FlashFn(torch.autograd.Function):
     k / v [B, KV, S, 128] -> o [B, S, H * 128]. The backward's per-query-head dk / dv are summed
     over each kv head's group here (the fused QKV path, ``_RopeFlashFn``, sums them inside the RoPE
     backward kernel instead). lo / hi (int32 [B, S] on the device, or None) select the kernels'
-    document variants."""
+    document variants. Head dim 64 (csrc/kernels/flash_attn64_gqa.hip, no lo / hi): dk / dv come
+    back with KV heads, summed over the group inside the dK / dV kernel, and pass through."""
 
     @staticmethod
     def forward(ctx, q, k, v, causal, scale, lo=None, hi=None):
@@ -675,7 +683,7 @@ class _FlashFn(torch.autograd.Function):
         dq, dkh, dvh = lib().flash_bwd(q, k, v, o, do, lse, ctx.causal, ctx.scale, lo=lo, hi=hi)
         B, H, S, D = q.shape
         KV = k.shape[1]
-        if H != KV:
+        if dkh.shape[1] != KV:   # per query head (hd 128): the group sum
             dkh = dkh.view(B, KV, H // KV, S, D).float().sum(2).to(q.dtype)
             dvh = dvh.view(B, KV, H // KV, S, D).float().sum(2).to(q.dtype)
         return dq, dkh, dvh, None, None, None, None
@@ -699,30 +707,33 @@ def flash_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, causal: b
                     bounds: Optional[Tuple[torch.Tensor, torch.Tensor]] = None) -> torch.Tensor:
     """Multi-head attention with grouped-query heads (H % KV == 0): q [B, H, S, hd], k / v
     [B, KV, S, hd] -> [B, S, H * hd] (the output projection's input rows). bf16 GPU tensors with
-    hd = 128 run the flash kernels of csrc/kernels/flash_attn.hip (forward and backward);
-    anything else runs SDPA.
+    hd = 128 run the flash kernels of csrc/kernels/flash_attn.hip (forward and backward), with
+    hd = 64 and no ``bounds`` those of csrc/kernels/flash_attn64_gqa.hip (any S, any group size;
+    ``CML_FLASH_ATTN64=0`` / ``PerfPolicy.flash_attn64`` off: SDPA); anything else runs SDPA.
 
     ``bounds = doc_bounds(doc_ids)``: rows are several documents packed to S tokens, and a query
     attends only to the earlier keys of its own document (causal only: ``causal=False`` raises
     ValueError). The kernels' document variants neither stage nor compute key tiles outside a
-    query block's documents; the SDPA path takes the same mask as a boolean ``attn_mask``."""
+    query block's documents; the SDPA path takes the same mask as a boolean ``attn_mask``. With
+    ``bounds``, hd = 64 stays on that SDPA path."""
     hd = q.shape[-1]
     scale = float(scale) if scale is not None else 1.0 / math.sqrt(hd)
     lo, hi = _dev_bounds(bounds, causal, q.device)
-    if hd == 128 and _flash_ok(q, k, v):
+    if (hd == 128 and _flash_ok(q, k, v)) or (hd == 64 and _flash_gqa64_ok(lo, q, k, v)):
         return _FlashFn.apply(q, k, v, bool(causal), scale, lo, hi)
     return _sdpa_rows(q, k, v, causal, scale, lo)
 
 
 class _RopeFlashFn(torch.autograd.Function):
-    """QKV split + RoPE + flash attention from the fused projection ``qkv [B, S, (H + 2 KV) 128]``
-    to ``o [B, S, H 128]``. Backward: the flash backward, then ONE RoPE-backward pass that also
-    sums the per-query-head dk / dv of each kv head's group (transformer.hip rope_bwd, grp) and
-    writes dqkv in the fused layout. lo / hi as in ``_FlashFn``."""
+    """QKV split + RoPE + flash attention from the fused projection ``qkv [B, S, (H + 2 KV) hd]``
+    to ``o [B, S, H hd]``, hd 128 or 64. Backward: the flash backward, then ONE RoPE-backward pass
+    that writes dqkv in the fused layout. At hd 128 that pass also sums the per-query-head dk / dv
+    of each kv head's group (transformer.hip rope_bwd, grp); at hd 64 the dK / dV kernel has
+    summed them already (flash_attn64_gqa.hip) and grp is 1. lo / hi as in ``_FlashFn``."""
 
     @staticmethod
     def forward(ctx, qkv, cos, sin, H, KV, causal, scale, lo=None, hi=None):
-        q, k, v = lib().rope_fwd(qkv, cos, sin, H, KV, 128)
+        q, k, v = lib().rope_fwd(qkv, cos, sin, H, KV, qkv.shape[2] // (H + 2 * KV))
         o, lse = lib().flash_fwd(q, k, v, causal, scale, lo=lo)
         ctx.save_for_backward(q, k, v, o, lse, cos, sin, lo, hi)
         ctx.cfg = (H, KV, causal, scale)
@@ -733,7 +744,7 @@ class _RopeFlashFn(torch.autograd.Function):
         q, k, v, o, lse, cos, sin, lo, hi = ctx.saved_tensors
         H, KV, causal, scale = ctx.cfg
         dq, dkh, dvh = lib().flash_bwd(q, k, v, o, do, lse, causal, scale, lo=lo, hi=hi)
-        dqkv = lib().rope_bwd(dq, dkh, dvh, cos, sin, H // KV)
+        dqkv = lib().rope_bwd(dq, dkh, dvh, cos, sin, dkh.shape[1] // KV)
         return dqkv, None, None, None, None, None, None, None, None
 
 
@@ -742,13 +753,15 @@ def qkv_attention(qkv: torch.Tensor, H: int, KV: int, hd: int,
                   causal: bool = True,
                   bounds: Optional[Tuple[torch.Tensor, torch.Tensor]] = None) -> torch.Tensor:
     """Attention straight from the fused projection ``qkv [B, S, (H + 2 KV) hd]`` (RoPE on q / k
-    when cos / sin are given) to ``[B, S, H hd]``. bf16 GPU tensors with hd = 128 run
-    ``_RopeFlashFn`` (own kernels end to end); otherwise qkv_split + SDPA. ``bounds``: the
-    document mask of ``flash_attention`` (RoPE positions stay absolute: within a document the
-    scores depend on position differences only)."""
+    when cos / sin are given) to ``[B, S, H hd]``. bf16 GPU tensors with hd = 128, or with
+    hd = 64 and no ``bounds`` (``flash_attn64`` on), run ``_RopeFlashFn`` (own kernels end to
+    end); otherwise qkv_split + SDPA. ``bounds``: the document mask of ``flash_attention`` (RoPE
+    positions stay absolute: within a document the scores depend on position differences only);
+    with it hd = 64 keeps the qkv_split + SDPA path."""
     scale = 1.0 / math.sqrt(hd)
     lo, hi = _dev_bounds(bounds, causal, qkv.device)
-    if hd == 128 and _flash_ok(qkv) and (cos is None or (cos.is_cuda and sin.is_cuda)):
+    if (((hd == 128 and _flash_ok(qkv)) or (hd == 64 and _flash_gqa64_ok(lo, qkv)))
+            and (cos is None or (cos.is_cuda and sin.is_cuda))):
         return _RopeFlashFn.apply(qkv, cos, sin, H, KV, bool(causal), scale, lo, hi)
     q, k, v = qkv_split(qkv, H, KV, hd, cos, sin)
     return _sdpa_rows(q, k, v, causal, scale, lo)

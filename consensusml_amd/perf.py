@@ -114,7 +114,9 @@ class PerfPolicy:
     flash_attn64: bool = True             # flash_attn64.hip for head-dim-64 attention from the
                                           # fused QKV layout past S = 128 (BERT at 256 / 384 / 512)
                                           # and causal at any S; False: head split + SDPA
-                                          # (profiles/flash64/README.md)
+                                          # (profiles/flash64/README.md). Also flash_attn64_gqa.hip
+                                          # for head-major head-dim-64 GQA (Llama-3.2-1B) without
+                                          # document bounds (profiles/flash64_gqa/README.md)
     multi_copy: bool = True               # multi-tensor HIP copy for gradient capture
     batched_workers: bool = True          # virtual workers as one batched fwd/bwd (BERT)
     own_gemm: bool = True                 # gemm.hip for transformer linears with >= 128 tiles

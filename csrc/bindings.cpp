@@ -2721,15 +2721,17 @@ Tensor rope_bwd(const Tensor& dq_in, const Tensor& dk_in, const Tensor& dv_in,
   return dqkv;
 }
 
-// Flash attention (csrc/kernels/flash_attn.hip): q [B, H, S, 128], k / v [B, KV, S, 128] bf16
-// contiguous -> (o [B, S, H * 128], lse fp32 [B, H, S])
+// Flash attention: q [B, H, S, hd], k / v [B, KV, S, hd] bf16 contiguous -> (o [B, S, H * hd],
+// lse fp32 [B, H, S]). hd = 128: csrc/kernels/flash_attn.hip; hd = 64:
+// csrc/kernels/flash_attn64_gqa.hip (no document bounds; dk / dv come back group-summed)
 void check_flash_qkv(const Tensor& q, const Tensor& k, const Tensor& v) {
   check_bf16c(q, "q");
   check_bf16c(k, "k");
   check_bf16c(v, "v");
   TORCH_CHECK(q.dim() == 4 && k.dim() == 4 && k.sizes() == v.sizes() && q.size(0) == k.size(0) &&
-                  q.size(2) == k.size(2) && q.size(3) == 128 && k.size(3) == 128,
-              "flash: q [B, H, S, 128], k / v [B, KV, S, 128]");
+                  q.size(2) == k.size(2) && (q.size(3) == 128 || q.size(3) == 64) &&
+                  k.size(3) == q.size(3),
+              "flash: q [B, H, S, hd], k / v [B, KV, S, hd], hd 128 or 64");
   TORCH_CHECK(q.size(1) % k.size(1) == 0, "flash: H % KV == 0");
   TORCH_CHECK(q.get_device() == k.get_device() && q.get_device() == v.get_device(),
               "flash: q / k / v on one device");
@@ -2751,10 +2753,18 @@ std::vector<Tensor> flash_fwd(const Tensor& q, const Tensor& k, const Tensor& v,
                               double scale, double rescale_thr, const optional<Tensor>& lo) {
   check_flash_qkv(q, k, v);
   const int* lo_p = flash_bound(lo, q, causal);
-  const int64_t B = q.size(0), H = q.size(1), S = q.size(2), KV = k.size(1);
+  const int64_t B = q.size(0), H = q.size(1), S = q.size(2), KV = k.size(1), hd = q.size(3);
+  TORCH_CHECK(hd == 128 || !lo.has_value(), "flash_fwd: no document bounds (lo) at head dim 64");
   const c10::DeviceGuard guard(q.device());
-  Tensor o = at::empty({B, S, H * 128}, q.options());
+  Tensor o = at::empty({B, S, H * hd}, q.options());
   Tensor lse = at::empty({B, H, S}, q.options().dtype(at::kFloat));
+  if (hd == 64) {
+    CML_CHECK_HIP(cml::launch_flash64_gqa_fwd(
+        q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr<float>(),
+        static_cast<int>(B), static_cast<int>(H), static_cast<int>(KV), static_cast<int>(S),
+        static_cast<float>(scale), causal, cur_stream(), static_cast<float>(rescale_thr)));
+    return {o, lse};
+  }
   CML_CHECK_HIP(cml::launch_flash_fwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(),
                                       lse.data_ptr<float>(), static_cast<int>(B), static_cast<int>(H),
                                       static_cast<int>(KV), static_cast<int>(S),
@@ -2763,7 +2773,8 @@ std::vector<Tensor> flash_fwd(const Tensor& q, const Tensor& k, const Tensor& v,
   return {o, lse};
 }
 
-// -> (dq [B, H, S, 128], dk / dv per query head [B, H, S, 128])
+// -> (dq [B, H, S, 128], dk / dv per query head [B, H, S, 128]); head dim 64: (dq [B, H, S, 64],
+// dk / dv [B, KV, S, 64] already summed over each kv head's query heads)
 std::vector<Tensor> flash_bwd(const Tensor& q, const Tensor& k, const Tensor& v, const Tensor& o,
                               const Tensor& dout_in, const Tensor& lse, bool causal, double scale,
                               const optional<Tensor>& lo, const optional<Tensor>& hi) {
@@ -2771,12 +2782,14 @@ std::vector<Tensor> flash_bwd(const Tensor& q, const Tensor& k, const Tensor& v,
   TORCH_CHECK(lo.has_value() == hi.has_value(), "flash_bwd: lo and hi come together");
   const int* lo_p = flash_bound(lo, q, causal);
   const int* hi_p = flash_bound(hi, q, causal);
-  const int64_t B = q.size(0), H = q.size(1), S = q.size(2), KV = k.size(1);
+  const int64_t B = q.size(0), H = q.size(1), S = q.size(2), KV = k.size(1), hd = q.size(3);
+  TORCH_CHECK(hd == 128 || !lo.has_value(),
+              "flash_bwd: no document bounds (lo / hi) at head dim 64");
   Tensor dout = dout_in.contiguous();
   check_bf16c(o, "o");
   check_bf16c(dout, "dout");
-  TORCH_CHECK(o.numel() == B * S * H * 128 && dout.numel() == o.numel() && o.is_contiguous(),
-              "flash_bwd: o / dout [B, S, H * 128]");
+  TORCH_CHECK(o.numel() == B * S * H * hd && dout.numel() == o.numel() && o.is_contiguous(),
+              "flash_bwd: o / dout [B, S, H * hd]");
   TORCH_CHECK((reinterpret_cast<uintptr_t>(o.data_ptr()) & 15) == 0 &&
                   (reinterpret_cast<uintptr_t>(dout.data_ptr()) & 15) == 0,
               "flash_bwd: 16-B aligned o / dout");
@@ -2785,9 +2798,18 @@ std::vector<Tensor> flash_bwd(const Tensor& q, const Tensor& k, const Tensor& v,
               "flash_bwd: lse fp32 [B, H, S]");
   const c10::DeviceGuard guard(q.device());
   Tensor dq = at::empty_like(q);
+  Tensor dsum = at::empty({B, H, S}, lse.options());
+  if (hd == 64) {
+    Tensor dk = at::empty_like(k), dv = at::empty_like(v);
+    CML_CHECK_HIP(cml::launch_flash64_gqa_bwd(
+        q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), dout.data_ptr(),
+        lse.data_ptr<float>(), dsum.data_ptr<float>(), dq.data_ptr(), dk.data_ptr(), dv.data_ptr(),
+        static_cast<int>(B), static_cast<int>(H), static_cast<int>(KV), static_cast<int>(S),
+        static_cast<float>(scale), causal, cur_stream()));
+    return {dq, dk, dv};
+  }
   Tensor dk = at::empty({B, H, S, 128}, q.options());
   Tensor dv = at::empty({B, H, S, 128}, q.options());
-  Tensor dsum = at::empty({B, H, S}, lse.options());
   CML_CHECK_HIP(cml::launch_flash_bwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(),
                                       dout.data_ptr(), lse.data_ptr<float>(), dsum.data_ptr<float>(),
                                       dq.data_ptr(), dk.data_ptr(), dv.data_ptr(),
@@ -3615,10 +3637,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("rope_bwd", &rope_bwd, "inverse of rope_fwd (grp > 1: sums per-query-head dk / dv)",
         py::arg("dq"), py::arg("dk"), py::arg("dv"), py::arg("cos"), py::arg("sin"),
         py::arg("grp") = 1);
-  m.def("flash_fwd", &flash_fwd, "flash attention forward, head dim 128, GQA, causal / full",
+  m.def("flash_fwd", &flash_fwd, "flash attention forward, head dim 128 / 64, GQA, causal / full",
         py::arg("q"), py::arg("k"), py::arg("v"), py::arg("causal"), py::arg("scale"),
         py::arg("rescale_thr") = 8.0, py::arg("lo") = py::none());
-  m.def("flash_bwd", &flash_bwd, "flash attention backward (dq, per-query-head dk / dv)",
+  m.def("flash_bwd", &flash_bwd,
+        "flash attention backward (dq, dk / dv per query head; head dim 64: per kv head)",
         py::arg("q"), py::arg("k"), py::arg("v"), py::arg("o"), py::arg("dout"), py::arg("lse"),
         py::arg("causal"), py::arg("scale"), py::arg("lo") = py::none(),
         py::arg("hi") = py::none());

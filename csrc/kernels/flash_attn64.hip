@@ -759,7 +759,7 @@ hipError_t launch_f64(void (*kern)(A), const A& a, int smem, int rows, hipStream
   return hipGetLastError();
 }
 
-#ifndef CML_F64_DROP_TU
+#if !defined(CML_F64_DROP_TU) && !defined(CML_F64_GQA_TU)
 // 32-query groups per forward wave: 2 when its grid still gives every CU >= 3 workgroups (causal:
 // >= 4) and S wastes no half block of 256 queries, else 1. Measured at 12 heads (256 CUs,
 // profiles/flash64/README.md): at 1.5-2 workgroups per CU NQ = 1 is 12-17 % faster; at 3 NQ = 2
@@ -782,11 +782,14 @@ bool f64_shape_ok(int B, int H, int S) {
          static_cast<int64_t>((S + kBK - 1) / kBK) * B * H < (1LL << 31);
 }
 
-#endif  // !CML_F64_DROP_TU
+#endif  // !CML_F64_DROP_TU && !CML_F64_GQA_TU
 
 }  // namespace
 
-#ifdef CML_F64_DROP_TU
+#if defined(CML_F64_GQA_TU)
+// flash_attn64_gqa.hip takes the helpers above for its own kernels and launchers: nothing of this
+// file is instantiated in that compilation
+#elif defined(CML_F64_DROP_TU)
 hipError_t launch_f64_drop_fwd(const F64Args& a, const DropArgs& d, float* o32, bool causal,
                                hipStream_t st) {
   const F64DropArgs x{a, d, o32};
@@ -881,6 +884,6 @@ hipError_t launch_flash64_bwd(const void* qkv, const void* o, const void* dout, 
   return causal ? launch_f64(f64_dkdv_kernel<true, false>, a, kKVSmem, kBK, st)
                 : launch_f64(f64_dkdv_kernel<false, false>, a, kKVSmem, kBK, st);
 }
-#endif  // CML_F64_DROP_TU
+#endif  // CML_F64_GQA_TU / CML_F64_DROP_TU
 
 }  // namespace cml

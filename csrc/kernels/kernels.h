@@ -475,6 +475,20 @@ hipError_t launch_flash64_bwd(const void* qkv, const void* o, const void* dout, 
                               float* dsum, void* dqkv, int B, int H, int S, float scale,
                               bool causal, hipStream_t stream, const int* lens = nullptr,
                               const DropSpec& drop = {}, const float* o32 = nullptr);
+// Flash attention, head dim 64, grouped-query heads (H % KV == 0, any group size), causal or
+// full, any S >= 1, in launch_flash_fwd / bwd's head-major layouts: q [B, H, S, 64], k / v
+// [B, KV, S, 64] -> o [B, S, H * 64], lse fp32 [B, H, S] (log2 domain). Backward: dq
+// [B, H, S, 64] and dk / dv [B, KV, S, 64], ALREADY summed over each kv head's query heads inside
+// the dK / dV kernel (fixed order, no atomics: launch_rope_bwd takes them with grp = 1); dsum
+// [B, H, S] fp32 scratch. No lengths, dropout or document bounds on this layout.
+// csrc/kernels/flash_attn64_gqa.hip. rescale_thr as in launch_flash_fwd.
+hipError_t launch_flash64_gqa_fwd(const void* q, const void* k, const void* v, void* o, float* lse,
+                                  int B, int H, int KV, int S, float scale, bool causal,
+                                  hipStream_t stream, float rescale_thr = 8.f);
+hipError_t launch_flash64_gqa_bwd(const void* q, const void* k, const void* v, const void* o,
+                                  const void* dout, const float* lse, float* dsum, void* dq,
+                                  void* dk, void* dv, int B, int H, int KV, int S, float scale,
+                                  bool causal, hipStream_t stream);
 // SwiGLU over h = [a | b] ([M, 2F]): y = silu(a) * b; backward writes dh [M, 2F].
 hipError_t launch_swiglu_fwd(const void* h, void* y, int64_t M, int F, hipStream_t stream);
 hipError_t launch_swiglu_bwd(const void* dy, const void* h, void* dh, int64_t M, int F,
