@@ -34,18 +34,20 @@ EXT_SUFFIX = sysconfig.get_config_var("EXT_SUFFIX") or ".so"
 # rescale and store scaling; flash_attn_doc.hip (flash_attn.hip's document-masked instantiations
 # and the bounds kernel) and flash_attn64_drop.hip (flash_attn64.hip's dropout instantiations)
 # likewise, and flash_attn64_gqa.hip (the head-major grouped-query kernels on flash_attn64.hip's
-# helpers)
+# helpers) with flash_attn64_gqa_win.hip (their sliding-window kernels)
 _NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 SRC_FLAGS = {
     "flash_attn64.hip": _NO_PK_F32,
     "flash_attn_doc.hip": _NO_PK_F32,
     "flash_attn64_drop.hip": _NO_PK_F32,
     "flash_attn64_gqa.hip": _NO_PK_F32,
+    "flash_attn64_gqa_win.hip": _NO_PK_F32,
 }
 # sources that include another source (besides the headers every object depends on)
 SRC_DEPS = {"flash_attn_doc.hip": ["flash_attn.hip"],
             "flash_attn64_drop.hip": ["flash_attn64.hip"],
-            "flash_attn64_gqa.hip": ["flash_attn64.hip"]}
+            "flash_attn64_gqa.hip": ["flash_attn64.hip"],
+            "flash_attn64_gqa_win.hip": ["flash_attn64.hip"]}
 
 
 def _torch_paths():

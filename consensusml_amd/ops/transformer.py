@@ -668,43 +668,71 @@ class _FlashFn(torch.autograd.Function):
     over each kv head's group here (the fused QKV path, ``_RopeFlashFn``, sums them inside the RoPE
     backward kernel instead). lo / hi (int32 [B, S] on the device, or None) select the kernels'
     document variants. Head dim 64 (csrc/kernels/flash_attn64_gqa.hip, no lo / hi): dk / dv come
-    back with KV heads, summed over the group inside the dK / dV kernel, and pass through."""
+    back with KV heads, summed over the group inside the dK / dV kernel, and pass through.
+    window > 0 (head dim 64 only): the sliding-window kernels of flash_attn64_gqa_win.hip."""
 
     @staticmethod
-    def forward(ctx, q, k, v, causal, scale, lo=None, hi=None):
-        o, lse = lib().flash_fwd(q, k, v, causal, scale, lo=lo)
+    def forward(ctx, q, k, v, causal, scale, lo=None, hi=None, window=0):
+        o, lse = lib().flash_fwd(q, k, v, causal, scale, lo=lo, window=window)
         ctx.save_for_backward(q, k, v, o, lse, lo, hi)
-        ctx.causal, ctx.scale = causal, scale
+        ctx.causal, ctx.scale, ctx.window = causal, scale, window
         return o
 
     @staticmethod
     def backward(ctx, do):
         q, k, v, o, lse, lo, hi = ctx.saved_tensors
-        dq, dkh, dvh = lib().flash_bwd(q, k, v, o, do, lse, ctx.causal, ctx.scale, lo=lo, hi=hi)
+        dq, dkh, dvh = lib().flash_bwd(q, k, v, o, do, lse, ctx.causal, ctx.scale, lo=lo, hi=hi,
+                                       window=ctx.window)
         B, H, S, D = q.shape
         KV = k.shape[1]
         if dkh.shape[1] != KV:   # per query head (hd 128): the group sum
             dkh = dkh.view(B, KV, H // KV, S, D).float().sum(2).to(q.dtype)
             dvh = dvh.view(B, KV, H // KV, S, D).float().sum(2).to(q.dtype)
-        return dq, dkh, dvh, None, None, None, None
+        return dq, dkh, dvh, None, None, None, None, None
 
 
-def _sdpa_rows(q, k, v, causal: bool, scale: float, lo=None) -> torch.Tensor:
+def _sdpa_rows(q, k, v, causal: bool, scale: float, lo=None, window=None) -> torch.Tensor:
     """Reference composition of flash_attention (any device / dtype): [B, S, H * hd]. lo: the
-    document mask ``lo[b, i] <= j <= i`` as a boolean attn_mask, broadcast over the heads."""
+    document mask ``lo[b, i] <= j <= i`` as a boolean attn_mask, broadcast over the heads.
+    window (causal): ``i - window < j <= i`` in the same mask, together with lo when both come."""
     B, H, S, hd = q.shape
     mask = None
     if lo is not None:
         pos = torch.arange(S, device=q.device)
         mask = ((lo[:, :, None] <= pos) & (pos <= pos[:, None]))[:, None]
+    if window is not None:
+        pos = torch.arange(S, device=q.device)
+        win = (pos <= pos[:, None]) & (pos > pos[:, None] - window)
+        mask = win if mask is None else mask & win
     o = F.scaled_dot_product_attention(q, k, v, attn_mask=mask, is_causal=causal and mask is None,
                                        scale=scale, enable_gqa=H != k.shape[1])
     return o.transpose(1, 2).reshape(B, S, H * hd)
 
 
+def _window(window, causal: bool, S: int):
+    """The checked window of flash_attention / qkv_attention: None when absent or >= S (the plain
+    causal mask)."""
+    if window is None:
+        return None
+    if window < 1:
+        raise ValueError(f"window must be >= 1, got {window}")
+    if not causal:
+        raise ValueError("a sliding window is causal only: causal=False with window")
+    return int(window) if window < S else None
+
+
+def _window_bounds(B: int, S: int, window: int, dev: torch.device):
+    """The window as the (lo, hi) of the head-dim-128 document kernels: lo[i] = max(0, i - W + 1),
+    hi[j] = min(S, j + W), int32 [B, S] on dev."""
+    pos = torch.arange(S, device=dev, dtype=torch.int32)
+    return ((pos - (window - 1)).clamp_min(0).expand(B, S).contiguous(),
+            (pos + window).clamp_max(S).expand(B, S).contiguous())
+
+
 def flash_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, causal: bool = True,
                     scale: Optional[float] = None,
-                    bounds: Optional[Tuple[torch.Tensor, torch.Tensor]] = None) -> torch.Tensor:
+                    bounds: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
+                    window: Optional[int] = None) -> torch.Tensor:
     """Multi-head attention with grouped-query heads (H % KV == 0): q [B, H, S, hd], k / v
     [B, KV, S, hd] -> [B, S, H * hd] (the output projection's input rows). bf16 GPU tensors with
     hd = 128 run the flash kernels of csrc/kernels/flash_attn.hip (forward and backward), with
@@ -715,10 +743,28 @@ def flash_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, causal: b
     attends only to the earlier keys of its own document (causal only: ``causal=False`` raises
     ValueError). The kernels' document variants neither stage nor compute key tiles outside a
     query block's documents; the SDPA path takes the same mask as a boolean ``attn_mask``. With
-    ``bounds``, hd = 64 stays on that SDPA path."""
+    ``bounds``, hd = 64 stays on that SDPA path.
+
+    ``window = W`` (>= 1, causal only; both violations raise ValueError): sliding-window attention,
+    query i attends keys ``max(0, i - W + 1) .. i``; ``W >= S`` is plain causal attention, bit
+    for bit. bf16 GPU tensors with hd = 64 and no ``bounds`` run the window kernels of
+    csrc/kernels/flash_attn64_gqa_win.hip, which neither stage nor compute the key tiles below a
+    query block's window (work S W instead of S^2 / 2). hd = 128 without ``bounds`` runs the
+    document kernels of flash_attn.hip under ``lo[i] = max(0, i - W + 1)``, ``hi[j] = min(S, j + W)``
+    (they ask only for non-decreasing bounds, not for run boundaries). Everything else, ``window``
+    together with ``bounds`` included (``max(lo[b, i], i - W + 1) <= j <= i``), runs SDPA with the
+    window folded into the boolean mask."""
     hd = q.shape[-1]
     scale = float(scale) if scale is not None else 1.0 / math.sqrt(hd)
     lo, hi = _dev_bounds(bounds, causal, q.device)
+    win = _window(window, causal, q.shape[2])
+    if win is not None:
+        if lo is None and hd == 64 and _flash_gqa64_ok(None, q, k, v):
+            return _FlashFn.apply(q, k, v, True, scale, None, None, win)
+        if lo is None and hd == 128 and _flash_ok(q, k, v):
+            return _FlashFn.apply(q, k, v, True, scale,
+                                  *_window_bounds(q.shape[0], q.shape[2], win, q.device))
+        return _sdpa_rows(q, k, v, causal, scale, lo, win)
     if (hd == 128 and _flash_ok(q, k, v)) or (hd == 64 and _flash_gqa64_ok(lo, q, k, v)):
         return _FlashFn.apply(q, k, v, bool(causal), scale, lo, hi)
     return _sdpa_rows(q, k, v, causal, scale, lo)
@@ -729,39 +775,52 @@ class _RopeFlashFn(torch.autograd.Function):
     to ``o [B, S, H hd]``, hd 128 or 64. Backward: the flash backward, then ONE RoPE-backward pass
     that writes dqkv in the fused layout. At hd 128 that pass also sums the per-query-head dk / dv
     of each kv head's group (transformer.hip rope_bwd, grp); at hd 64 the dK / dV kernel has
-    summed them already (flash_attn64_gqa.hip) and grp is 1. lo / hi as in ``_FlashFn``."""
+    summed them already (flash_attn64_gqa.hip) and grp is 1. lo / hi / window as in ``_FlashFn``."""
 
     @staticmethod
-    def forward(ctx, qkv, cos, sin, H, KV, causal, scale, lo=None, hi=None):
+    def forward(ctx, qkv, cos, sin, H, KV, causal, scale, lo=None, hi=None, window=0):
         q, k, v = lib().rope_fwd(qkv, cos, sin, H, KV, qkv.shape[2] // (H + 2 * KV))
-        o, lse = lib().flash_fwd(q, k, v, causal, scale, lo=lo)
+        o, lse = lib().flash_fwd(q, k, v, causal, scale, lo=lo, window=window)
         ctx.save_for_backward(q, k, v, o, lse, cos, sin, lo, hi)
-        ctx.cfg = (H, KV, causal, scale)
+        ctx.cfg = (H, KV, causal, scale, window)
         return o
 
     @staticmethod
     def backward(ctx, do):
         q, k, v, o, lse, cos, sin, lo, hi = ctx.saved_tensors
-        H, KV, causal, scale = ctx.cfg
-        dq, dkh, dvh = lib().flash_bwd(q, k, v, o, do, lse, causal, scale, lo=lo, hi=hi)
+        H, KV, causal, scale, window = ctx.cfg
+        dq, dkh, dvh = lib().flash_bwd(q, k, v, o, do, lse, causal, scale, lo=lo, hi=hi,
+                                       window=window)
         dqkv = lib().rope_bwd(dq, dkh, dvh, cos, sin, dkh.shape[1] // KV)
-        return dqkv, None, None, None, None, None, None, None, None
+        return dqkv, None, None, None, None, None, None, None, None, None
 
 
 def qkv_attention(qkv: torch.Tensor, H: int, KV: int, hd: int,
                   cos: Optional[torch.Tensor] = None, sin: Optional[torch.Tensor] = None,
                   causal: bool = True,
-                  bounds: Optional[Tuple[torch.Tensor, torch.Tensor]] = None) -> torch.Tensor:
+                  bounds: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
+                  window: Optional[int] = None) -> torch.Tensor:
     """Attention straight from the fused projection ``qkv [B, S, (H + 2 KV) hd]`` (RoPE on q / k
     when cos / sin are given) to ``[B, S, H hd]``. bf16 GPU tensors with hd = 128, or with
     hd = 64 and no ``bounds`` (``flash_attn64`` on), run ``_RopeFlashFn`` (own kernels end to
     end); otherwise qkv_split + SDPA. ``bounds``: the document mask of ``flash_attention`` (RoPE
     positions stay absolute: within a document the scores depend on position differences only);
-    with it hd = 64 keeps the qkv_split + SDPA path."""
+    with it hd = 64 keeps the qkv_split + SDPA path. ``window``: the sliding window of
+    ``flash_attention``, routed the same way (hd = 64 without ``bounds``: the window kernels;
+    hd = 128 without ``bounds``: the document kernels under window bounds; else SDPA)."""
     scale = 1.0 / math.sqrt(hd)
     lo, hi = _dev_bounds(bounds, causal, qkv.device)
-    if (((hd == 128 and _flash_ok(qkv)) or (hd == 64 and _flash_gqa64_ok(lo, qkv)))
-            and (cos is None or (cos.is_cuda and sin.is_cuda))):
+    win = _window(window, causal, qkv.shape[1])
+    own_rope = cos is None or (cos.is_cuda and sin.is_cuda)
+    if win is not None:
+        if lo is None and own_rope and hd == 64 and _flash_gqa64_ok(None, qkv):
+            return _RopeFlashFn.apply(qkv, cos, sin, H, KV, True, scale, None, None, win)
+        if lo is None and own_rope and hd == 128 and _flash_ok(qkv):
+            return _RopeFlashFn.apply(qkv, cos, sin, H, KV, True, scale,
+                                      *_window_bounds(qkv.shape[0], qkv.shape[1], win, qkv.device))
+        q, k, v = qkv_split(qkv, H, KV, hd, cos, sin)
+        return _sdpa_rows(q, k, v, causal, scale, lo, win)
+    if ((hd == 128 and _flash_ok(qkv)) or (hd == 64 and _flash_gqa64_ok(lo, qkv))) and own_rope:
         return _RopeFlashFn.apply(qkv, cos, sin, H, KV, bool(causal), scale, lo, hi)
     q, k, v = qkv_split(qkv, H, KV, hd, cos, sin)
     return _sdpa_rows(q, k, v, causal, scale, lo)

@@ -116,7 +116,8 @@ class PerfPolicy:
                                           # and causal at any S; False: head split + SDPA
                                           # (profiles/flash64/README.md). Also flash_attn64_gqa.hip
                                           # for head-major head-dim-64 GQA (Llama-3.2-1B) without
-                                          # document bounds (profiles/flash64_gqa/README.md)
+                                          # document bounds (profiles/flash64_gqa/README.md), and
+                                          # its sliding-window kernels, flash_attn64_gqa_win.hip
     multi_copy: bool = True               # multi-tensor HIP copy for gradient capture
     batched_workers: bool = True          # virtual workers as one batched fwd/bwd (BERT)
     own_gemm: bool = True                 # gemm.hip for transformer linears with >= 128 tiles

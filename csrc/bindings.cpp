@@ -2723,7 +2723,9 @@ Tensor rope_bwd(const Tensor& dq_in, const Tensor& dk_in, const Tensor& dv_in,
 
 // Flash attention: q [B, H, S, hd], k / v [B, KV, S, hd] bf16 contiguous -> (o [B, S, H * hd],
 // lse fp32 [B, H, S]). hd = 128: csrc/kernels/flash_attn.hip; hd = 64:
-// csrc/kernels/flash_attn64_gqa.hip (no document bounds; dk / dv come back group-summed)
+// csrc/kernels/flash_attn64_gqa.hip (no document bounds; dk / dv come back group-summed).
+// window > 0 (head dim 64, causal, no bounds): query i attends keys max(0, i - window + 1) .. i
+// on csrc/kernels/flash_attn64_gqa_win.hip; window >= S is the plain causal path, bit for bit
 void check_flash_qkv(const Tensor& q, const Tensor& k, const Tensor& v) {
   check_bf16c(q, "q");
   check_bf16c(k, "k");
@@ -2739,6 +2741,14 @@ void check_flash_qkv(const Tensor& q, const Tensor& k, const Tensor& v) {
     TORCH_CHECK((reinterpret_cast<uintptr_t>(t->data_ptr()) & 15) == 0, "flash: 16-B aligned q / k / v");
 }
 
+void check_flash_window(int64_t window, bool causal, bool bounds, int64_t hd) {
+  TORCH_CHECK(window >= 0, "flash: window >= 0 (0 = off)");
+  if (window == 0) return;
+  TORCH_CHECK(causal, "flash: a sliding window is causal only");
+  TORCH_CHECK(!bounds, "flash: window together with document bounds (lo / hi) is not supported");
+  TORCH_CHECK(hd == 64, "flash: window is a head-dim-64 path (head dim 128 takes lo / hi bounds)");
+}
+
 // lo / hi: int32 [B, S] document bounds (doc_bounds) on q's device, never read on the host
 const int* flash_bound(const optional<Tensor>& t, const Tensor& q, bool causal) {
   if (!t.has_value()) return nullptr;
@@ -2750,14 +2760,24 @@ const int* flash_bound(const optional<Tensor>& t, const Tensor& q, bool causal) 
 }
 
 std::vector<Tensor> flash_fwd(const Tensor& q, const Tensor& k, const Tensor& v, bool causal,
-                              double scale, double rescale_thr, const optional<Tensor>& lo) {
+                              double scale, double rescale_thr, const optional<Tensor>& lo,
+                              int64_t window) {
   check_flash_qkv(q, k, v);
+  check_flash_window(window, causal, lo.has_value(), q.size(3));
   const int* lo_p = flash_bound(lo, q, causal);
   const int64_t B = q.size(0), H = q.size(1), S = q.size(2), KV = k.size(1), hd = q.size(3);
   TORCH_CHECK(hd == 128 || !lo.has_value(), "flash_fwd: no document bounds (lo) at head dim 64");
   const c10::DeviceGuard guard(q.device());
   Tensor o = at::empty({B, S, H * hd}, q.options());
   Tensor lse = at::empty({B, H, S}, q.options().dtype(at::kFloat));
+  if (hd == 64 && window > 0 && window < S) {
+    CML_CHECK_HIP(cml::launch_flash64_gqa_win_fwd(
+        q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr<float>(),
+        static_cast<int>(B), static_cast<int>(H), static_cast<int>(KV), static_cast<int>(S),
+        static_cast<int>(window), static_cast<float>(scale), cur_stream(),
+        static_cast<float>(rescale_thr)));
+    return {o, lse};
+  }
   if (hd == 64) {
     CML_CHECK_HIP(cml::launch_flash64_gqa_fwd(
         q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr<float>(),
@@ -2777,8 +2797,10 @@ std::vector<Tensor> flash_fwd(const Tensor& q, const Tensor& k, const Tensor& v,
 // dk / dv [B, KV, S, 64] already summed over each kv head's query heads)
 std::vector<Tensor> flash_bwd(const Tensor& q, const Tensor& k, const Tensor& v, const Tensor& o,
                               const Tensor& dout_in, const Tensor& lse, bool causal, double scale,
-                              const optional<Tensor>& lo, const optional<Tensor>& hi) {
+                              const optional<Tensor>& lo, const optional<Tensor>& hi,
+                              int64_t window) {
   check_flash_qkv(q, k, v);
+  check_flash_window(window, causal, lo.has_value() || hi.has_value(), q.size(3));
   TORCH_CHECK(lo.has_value() == hi.has_value(), "flash_bwd: lo and hi come together");
   const int* lo_p = flash_bound(lo, q, causal);
   const int* hi_p = flash_bound(hi, q, causal);
@@ -2801,6 +2823,14 @@ std::vector<Tensor> flash_bwd(const Tensor& q, const Tensor& k, const Tensor& v,
   Tensor dsum = at::empty({B, H, S}, lse.options());
   if (hd == 64) {
     Tensor dk = at::empty_like(k), dv = at::empty_like(v);
+    if (window > 0 && window < S) {
+      CML_CHECK_HIP(cml::launch_flash64_gqa_win_bwd(
+          q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), dout.data_ptr(),
+          lse.data_ptr<float>(), dsum.data_ptr<float>(), dq.data_ptr(), dk.data_ptr(),
+          dv.data_ptr(), static_cast<int>(B), static_cast<int>(H), static_cast<int>(KV),
+          static_cast<int>(S), static_cast<int>(window), static_cast<float>(scale), cur_stream()));
+      return {dq, dk, dv};
+    }
     CML_CHECK_HIP(cml::launch_flash64_gqa_bwd(
         q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), dout.data_ptr(),
         lse.data_ptr<float>(), dsum.data_ptr<float>(), dq.data_ptr(), dk.data_ptr(), dv.data_ptr(),
@@ -3639,12 +3669,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("grp") = 1);
   m.def("flash_fwd", &flash_fwd, "flash attention forward, head dim 128 / 64, GQA, causal / full",
         py::arg("q"), py::arg("k"), py::arg("v"), py::arg("causal"), py::arg("scale"),
-        py::arg("rescale_thr") = 8.0, py::arg("lo") = py::none());
+        py::arg("rescale_thr") = 8.0, py::arg("lo") = py::none(), py::arg("window") = 0);
   m.def("flash_bwd", &flash_bwd,
         "flash attention backward (dq, dk / dv per query head; head dim 64: per kv head)",
         py::arg("q"), py::arg("k"), py::arg("v"), py::arg("o"), py::arg("dout"), py::arg("lse"),
         py::arg("causal"), py::arg("scale"), py::arg("lo") = py::none(),
-        py::arg("hi") = py::none());
+        py::arg("hi") = py::none(), py::arg("window") = 0);
   m.def("doc_bounds", &doc_bounds, "document bounds (lo, hi) of packed rows from doc ids");
   m.def("flash64_fwd", &flash64_fwd, "flash attention forward, head dim 64, fused qkv in",
         py::arg("qkv"), py::arg("H"), py::arg("causal"), py::arg("scale"),

@@ -489,6 +489,17 @@ hipError_t launch_flash64_gqa_bwd(const void* q, const void* k, const void* v, c
                                   const void* dout, const float* lse, float* dsum, void* dq,
                                   void* dk, void* dv, int B, int H, int KV, int S, float scale,
                                   bool causal, hipStream_t stream);
+// The same layouts and outputs under a causal sliding window: query i attends keys
+// max(0, i - window + 1) .. i, window >= 1 (window >= S is the plain causal mask). Key tiles
+// below a query block's window and query tiles past a key block's are neither staged nor
+// computed. csrc/kernels/flash_attn64_gqa_win.hip.
+hipError_t launch_flash64_gqa_win_fwd(const void* q, const void* k, const void* v, void* o,
+                                      float* lse, int B, int H, int KV, int S, int window,
+                                      float scale, hipStream_t stream, float rescale_thr = 8.f);
+hipError_t launch_flash64_gqa_win_bwd(const void* q, const void* k, const void* v, const void* o,
+                                      const void* dout, const float* lse, float* dsum, void* dq,
+                                      void* dk, void* dv, int B, int H, int KV, int S, int window,
+                                      float scale, hipStream_t stream);
 // SwiGLU over h = [a | b] ([M, 2F]): y = silu(a) * b; backward writes dh [M, 2F].
 hipError_t launch_swiglu_fwd(const void* h, void* y, int64_t M, int F, hipStream_t stream);
 hipError_t launch_swiglu_bwd(const void* dy, const void* h, void* dh, int64_t M, int F,
